@@ -10,13 +10,21 @@ scaling: every rank owns 2^20 items) and the step ends with one RCCL all-gather 
 output points, as north_star specifies.
 
 Rank 0 prints ONE JSON line with the driver's fields plus
-  roofline     executed 32x32 multiply-accumulates per second against the v_mad_u64_u32 issue
-               peak MEASURED on this device by libecc_amd/lib/ubench, and
-               the HBM view (algorithmic bytes / s against 8 TB/s) beside it;
-  cpu_baseline the reference's own prj_pt_mul + prj_pt_unique (oracle/_ref, "reference") or the
-               C restatement ("port") timed on this box's host cores on a bounded sample.
-Before anything is timed a random subset of the GPU output is compared byte-for-byte with the
-CPU oracle; a mismatch aborts the run.
+  roofline     executed 32x32 multiply-accumulates per second of the timed kernels, and the HBM
+               view (algorithmic bytes / s against 8 TB/s) beside it;
+  cpu_baseline null unless --full.
+A plain run sets up, warms up, times the K steps and prints the line, nothing else.  --full adds
+what takes runs or checks of its own, as every run did before the option existed:
+  * before anything is timed a random subset of the GPU output is compared byte-for-byte with the
+    CPU oracle (the parity gate); a mismatch aborts the run;
+  * the roofline's peak is the v_mad_u64_u32 issue peak MEASURED on this device by
+    libecc_amd/lib/ubench (SURVEY.md section 8d) instead of the nominal quarter-rate figure;
+  * cpu_baseline: the reference's own prj_pt_mul + prj_pt_unique (oracle/_ref, "reference") or
+    the C restatement ("port") timed on the host cores on a bounded sample;
+  * the HBM bytes per launch from two rocprofv3 --pmc child runs, and the `secondary` records
+    (the other BASELINE configs and the libecc-typed boundary), one fresh process each.
+--dump-outputs DIR writes what the last timed step computed (a fixed, seeded sample of the output
+points and their status bytes) as DIR/*.npy, so that two builds can be compared output for output.
 """
 import argparse
 import ctypes
@@ -197,7 +205,7 @@ def secondary_lines(ub):
     common = ["--steps", "10", "--warmup", "2"]
     jobs = [("configs[2] secp384r1", [sys.executable, os.path.abspath(__file__), "--curve", "SECP384R1"]),
             ("configs[2] secp521r1", [sys.executable, os.path.abspath(__file__), "--curve", "SECP521R1"])]
-    jobs = [(n, c + ["--no-secondary", "--parity-items", "65536"] + common) for n, c in jobs]
+    jobs = [(n, c + ["--full", "--no-secondary", "--parity-items", "65536"] + common) for n, c in jobs]
     tool = os.path.join(ROOT, "tools", "bench_protocols.py")
     for name, w in (("configs[3] ECDSA verify secp256r1", "ecdsa_verify"), ("configs[4] Ed25519 verify", "ed25519_verify"),
                     ("configs[4] X25519", "x25519")):
@@ -458,6 +466,27 @@ def traffic_child(args):
     ctx.close()
 
 
+DUMP_SEED = 0xD0
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, d_out, d_status, plen):
+    """What the last timed step handed its caller, as DIR/<name>.npy: `points` (items x plen, affine X || Y, one byte per
+    float32 -- exact), `status` (the status byte of each item) and `index` (the item's position in the batch).  Batches whose
+    outputs exceed DUMP_BYTES are represented by a fixed, seeded sample of 2^16 items (fewer on the widest curves)."""
+    n = d_status.numel()
+    per_item = 4 * plen + 4 + 8
+    k = min(n, 1 << 16, DUMP_BYTES // per_item)
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    sel = torch.from_numpy(idx).to(d_out.device)
+    pts = d_out.view(n, plen).index_select(0, sel).cpu().numpy()
+    st = d_status.index_select(0, sel).cpu().numpy()
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "points.npy"), pts.astype(np.float32))
+    np.save(os.path.join(dirname, "status.npy"), st.astype(np.float32))
+    np.save(os.path.join(dirname, "index.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -474,6 +503,11 @@ def main():
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak",
                     help="weak (default, the driver's contract): every rank owns 2^batch-log2 items; strong: 2^batch-log2 items in total, "
                          "split into contiguous shards of 2^batch-log2 / N per rank (BASELINE.json's metric read literally: batch = 2^20 at 1/2/4/8 GPUs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity gate, the measured MAD peak, the CPU baseline, the PMC traffic passes and the secondary records "
+                         "(the --no-* options above switch single parts off again)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (seeded sample of points and status bytes) as DIR/*.npy")
     args = ap.parse_args()
 
     if args.traffic_child:
@@ -521,8 +555,8 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
 
     from oracles import CURVES, Oracle, build_oracle
-    # the CPU checker is compiled on first use: let rank 0 do it alone, the others wait
-    if rank == 0:
+    # the CPU checker (parity gate, --full) is compiled on first use: let rank 0 do it alone, the others wait
+    if rank == 0 and args.full:
         build_oracle()
     if dist is not None:
         dist.barrier()
@@ -586,15 +620,17 @@ def main():
 
     # ---- parity gate: >= 2^16 random items of the timed batch AND a 4096-item edge slice, byte for
     #      byte against the unmodified reference on all host threads (oracle/_ref); without it, the C restatement on
-    #      a smaller sample ----
+    #      a smaller sample; --full only: a plain run keeps the untimed first step and checks nothing ----
     step()
     drain()
     torch.cuda.synchronize()
-    out_h = d_outs[0].cpu().numpy().tobytes()
-    pts_h = d_points.cpu().numpy().tobytes()
-    st_h = d_status.cpu().numpy().tobytes()
-    assert set(st_h) == {0}, "unexpected status in the synthetic batch"
-    gate, gate_timing = parity_gate(curve, cv, scalars_h, pts_h, out_h, slen, plen, B, args.parity_items if rank == 0 else 256)
+    gate, gate_timing = "not run (a plain run measures only; --full checks the batch against the CPU reference)", None
+    if args.full:
+        out_h = d_outs[0].cpu().numpy().tobytes()
+        pts_h = d_points.cpu().numpy().tobytes()
+        st_h = d_status.cpu().numpy().tobytes()
+        assert set(st_h) == {0}, "unexpected status in the synthetic batch"
+        gate, gate_timing = parity_gate(curve, cv, scalars_h, pts_h, out_h, slen, plen, B, args.parity_items if rank == 0 else 256)
     setup_s = time.time() - t_setup
 
     # ---- warmup, then exactly K timed steps ----
@@ -629,6 +665,16 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
+    # the last timed step's outputs as its caller holds them: N > 1, the gathered points and every rank's status bytes
+    if args.dump_outputs:
+        d_out, d_st = d_outs[0], d_status
+        if world > 1:
+            d_out = og.gathered
+            d_st = torch.empty(world * B, dtype=torch.uint8, device=dev)
+            dist.all_gather_into_tensor(d_st, d_status)
+        if rank == 0:
+            dump_outputs(args.dump_outputs, d_out, d_st, plen)
+
     # which device every rank ran on (the RCCL world, as the job saw it)
     props = torch.cuda.get_device_properties(dev)
     mine = f"rank {rank}: cuda:{local_rank} {props.name} ({getattr(props, 'gcnArchName', '?')}, {props.multi_processor_count} CUs)"
@@ -650,10 +696,12 @@ def main():
             kt, launch_ms, kmads = None, step_ms, mads
         mad_rate = B * kmads / (launch_ms * 1e-3)      # executed lane-MADs per second of the dominant kernel
         # the MAD issue peak is a per-GPU number: measured on rank 0's GPU after the timed region
-        peak_v, ub = measured_mad_peak()
+        peak_v, ub = measured_mad_peak() if args.full else (None, None)
         sg = getattr(work_model, "loop_sgpr_share", 0.0) if kt is not None else 0.0
         peak = mix_peak(ub, sg, signed=(cp["p"] == 2**384 - 2**128 - 2**96 + 2**32 - 1)) if ub else None
         nominal_quarter = 256 * 4 * 16 * 2.4e9 / 4.0   # SURVEY.md 8d planning figure (quarter rate)
+        # a plain run measures no peak and reports no fractions of one (--full: the measured peak, else the planning figure)
+        ref_peak = (peak or nominal_quarter) if args.full else None
         alg_bytes = float(slen + 2 * plen)             # scalar + affine point in + affine point out (160 B for P-256)
         hbm_rate = B * alg_bytes / (step_ms * 1e-3)
         line = {
@@ -670,15 +718,15 @@ def main():
                        "world_size": world, "rank_devices": rank_devices},
             "roofline": {
                 "bound": "valu-int-mad (v_mad_u64_u32 issue; not hbm, not mfma -- SURVEY.md 8d)",
-                "achieved": mad_rate / 1e9, "peak": (peak or nominal_quarter) / 1e9, "unit": "GMAD/s (one GPU)",
-                "frac": mad_rate / (peak or nominal_quarter),
+                "achieved": mad_rate / 1e9, "peak": ref_peak / 1e9 if ref_peak else None, "unit": "GMAD/s (one GPU)",
+                "frac": mad_rate / ref_peak if ref_peak else None,
                 "peak_source": ("measured live by libecc_amd/lib/ubench: the v_mad_u64_u32 streams with a VGPR and with an SGPR multiplier, "
-                                "weighted by the kernel's operand mix") if peak else "nominal quarter-rate estimate",
+                                "weighted by the kernel's operand mix") if peak else ("nominal quarter-rate estimate" if ref_peak else "not measured (--full)"),
                 "sgpr_multiplier_share": sg, "peak_vgpr_stream": (peak_v or 0) / 1e9,
                 "frac_of_vgpr_stream": mad_rate / peak_v if peak_v else None,
                 "kernel": kname, "kernel_ms": launch_ms, "kernel_mads_per_item": kmads,
                 "pipeline_ms": ({k_: float(v) for k_, v in zip(knames, kt)} if kt is not None else None),
-                "step_ms": step_ms, "pipeline_frac": (B * mads / (step_ms * 1e-3)) / (peak or nominal_quarter),
+                "step_ms": step_ms, "pipeline_frac": (B * mads / (step_ms * 1e-3)) / ref_peak if ref_peak else None,
                 "field_mults_per_item": mm, "mads_per_item": mads,
                 "ref_equivalent_mads_per_item": ref_equiv_mads(),
                 "traffic": None,
@@ -703,7 +751,7 @@ def main():
                     json.dump(ub, open(args.ubench_json, "w"), indent=1)
                 except OSError:
                     pass
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(curve, scalars_h, pts_h, slen, gate_timing)
         else:
             line["cpu_baseline"] = None
@@ -712,7 +760,7 @@ def main():
     if rank == 0:
         # after the headline region, with this process's device memory released:
         # (i) the HBM bytes per launch from PMC counters, measured on this very batch by two profiled child runs
-        if world == 1 and not args.no_traffic:
+        if args.full and world == 1 and not args.no_traffic:
             t0 = time.time()
             tr, by_kernel, note = pmc_traffic(kname, args.batch_log2, curve)
             line["roofline"]["traffic"] = tr
@@ -721,7 +769,7 @@ def main():
             if tr:
                 line["roofline"]["traffic_over_algorithmic"] = tr / (B * alg_bytes)
         # (ii) the other BASELINE configs, one fresh process each
-        if world == 1 and not args.no_secondary and curve == CURVE:
+        if args.full and world == 1 and not args.no_secondary and curve == CURVE:
             line["secondary"] = secondary_lines(ub)
         print(json.dumps(line))
     if world > 1:

@@ -13,8 +13,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_cfg1_plumbing_cpu():
-    if not os.path.exists("/root/reference/src/libsig.h") and not os.path.exists(os.path.join(ROOT, "tests", "_build", "compat_check_mock")):
-        pytest.skip("needs the reference tree (authoring container) to build the libecc-typed layer")
     import test_compat_host as T
     T._build()
     r = T._run(["cfg1"], ECAMD_COMPAT_THREADS="4")

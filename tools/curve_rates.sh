@@ -4,7 +4,7 @@
 O=$1; shift
 mkdir -p $O
 for c in "$@"; do
-  timeout 300 python bench.py --curve $c --no-secondary --steps ${STEPS:-8} --warmup 2 > $O/bench_$c.json 2> $O/bench_$c.err
+  timeout 300 python bench.py --full --curve $c --no-secondary --steps ${STEPS:-8} --warmup 2 > $O/bench_$c.json 2> $O/bench_$c.err
   python - $O/bench_$c.json <<'PY'
 import json, sys
 try:

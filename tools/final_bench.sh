@@ -5,7 +5,7 @@ O=$R/gpurun_out/${PASS:-final_bench}
 mkdir -p $O
 cd $R
 export TMPDIR=/tmp
-( time timeout 600 python bench.py ) > $O/bench_line.json 2> $O/bench_line.err; tail -n 3 $O/bench_line.err
+( time timeout 600 python bench.py --full ) > $O/bench_line.json 2> $O/bench_line.err; tail -n 3 $O/bench_line.err
 python - $O/bench_line.json <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 ( time timeout ${PYTEST_T:-1100} python -m pytest tests -m gpu -x -q --durations=8 ) > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
 tail -n 14 $O/pytest_gpu.log
 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; tail -n 1 $O/smoke.log
-( time timeout 600 python bench.py ) > $O/bench_line.json 2> $O/bench_line.err; tail -n 3 $O/bench_line.err
+( time timeout 600 python bench.py --full ) > $O/bench_line.json 2> $O/bench_line.err; tail -n 3 $O/bench_line.err
 python - $O/bench_line.json <<'PY'
 import json, sys
 j = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

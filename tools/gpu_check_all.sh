@@ -10,9 +10,9 @@ cd $R
 # 1. the whole GPU suite as the driver runs it (~7 min), smoke, the bench line
 ( time timeout 1500 python -m pytest tests -m gpu -x -q --durations=10 ) > $O/pytest.log 2>&1; echo "pytest rc=$?" >> $O/pytest.log
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1
-timeout 300 python bench.py --ubench-json $O/ubench.json > $O/bench.json 2> $O/bench.err
+timeout 300 python bench.py --full --ubench-json $O/ubench.json > $O/bench.json 2> $O/bench.err
 # 2. the other field sizes (batch 2^20)
-B="python $R/bench.py --no-cpu-baseline --no-traffic --no-secondary --parity-items 4096 --steps 5 --warmup 2"
+B="python $R/bench.py --full --no-cpu-baseline --no-traffic --no-secondary --parity-items 4096 --steps 5 --warmup 2"
 for c in SECP384R1 SECP521R1 WEI448 BRAINPOOLP256R1 BRAINPOOLP512R1 SECP256K1 WEI25519 SECP224R1 SECP192R1; do
   timeout 200 $B --curve $c > $O/bench_$c.json 2> $O/bench_$c.err
 done

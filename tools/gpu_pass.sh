@@ -9,7 +9,7 @@
 #   AB          list of NAME=ENVVAR=VALUE triples: every workload is timed again with that variable set (A/B of a code path)
 #   VARIANTS    names of libecc_amd/lib/variants/libecc_amd_<name>.so builds to time every workload with (tools/build_variant.py)
 #   AB_WORKLOADS the workloads AB / VARIANTS apply to (default: all of WORKLOADS)
-#   BENCH       "1": also run the default `python bench.py` line into bench_line.json
+#   BENCH       "1": also run the `python bench.py --full` line into bench_line.json
 #   EXTRA       a command line run last, verbatim
 set -x
 R=${GRAFT_REPO_ROOT:-/root/repo}
@@ -54,7 +54,7 @@ for w in $WORKLOADS; do
   done
 done
 if [ "$BENCH" = "1" ]; then
-  ( time timeout 600 python bench.py ) > $O/bench_line.json 2> $O/bench_line.err
+  ( time timeout 600 python bench.py --full ) > $O/bench_line.json 2> $O/bench_line.err
   show $O/bench_line.json; tail -n 3 $O/bench_line.err
 fi
 if [ -n "$EXTRA" ]; then

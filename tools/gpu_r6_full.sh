@@ -8,7 +8,7 @@ cd $R
 export TMPDIR=/tmp
 ( time timeout 1800 python -m pytest tests -m gpu -x -q ) > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log
 tail -n 8 $O/pytest_gpu.log
-( time timeout 1200 python bench.py ${BENCH_ARGS} ) > $O/bench_line.json 2> $O/bench_line.err
+( time timeout 1200 python bench.py --full ${BENCH_ARGS} ) > $O/bench_line.json 2> $O/bench_line.err
 tail -n 4 $O/bench_line.err
 python - $O/bench_line.json <<'PY'
 import json, sys

@@ -10,7 +10,7 @@ For every N in the list (<= visible devices):
      multiplies ITS shard with device-resident buffers on its context's stream (`ec_prj_pt_mul_batch_dev`), and
      `ecamd_multi_allgather` -- one RCCL all-gather, issued without any host synchronisation after the producers -- must leave the
      whole output on every device, equal to the single-device result.
-  2. Process layer: `python bench.py --gpus N --steps 3 --warmup 1 --no-secondary --no-traffic` (one rank per GPU over RCCL); its JSON
+  2. Process layer: `python bench.py --gpus N --steps 3 --warmup 1 --full --no-secondary --no-traffic` (one rank per GPU over RCCL); its JSON
      line must report world_size N and N distinct devices.
 Prints one line per check and a JSON summary; exit status 0 iff everything held."""
 import argparse
@@ -108,7 +108,7 @@ def main():
         mc.free()
         m.close()
         if not a.no_bench:
-            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--steps", "3", "--warmup", "1", "--no-secondary",
+            p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(N), "--steps", "3", "--warmup", "1", "--full", "--no-secondary",
                                 "--no-traffic", "--no-cpu-baseline", "--parity-items", "2048"], capture_output=True, text=True, timeout=900)
             line = None
             for ln in p.stdout.splitlines():
