@@ -1419,9 +1419,9 @@ extern "C" int ecamd_curve_words(const ecamd_curve *cv) { return cv ? cv->nw : -
 // ------------------------------------------------------------------------------------------
 // batched prj_pt_mul
 // ------------------------------------------------------------------------------------------
-// secp256r1 fast path scratch (ecamd_p256_kernel.hip): 8 x 64-byte affine records + 70 x 16-byte staging quads per item
-#define P256_TAB_BYTES 512u
-#define P256_SCRATCH_PER_ITEM ((size_t)P256_TAB_BYTES + 70u * 16u)
+// secp256r1 fast path scratch (ecamd_p256_kernel.hip): P256_TAB_BYTES of affine records + P256_STG_QUADS x 16-byte staging quads
+// per item (ecamd_internal.h)
+#define P256_SCRATCH_PER_ITEM ((size_t)P256_TAB_BYTES + P256_STG_QUADS * 16u)
 
 static size_t tbl_bytes_for(const ecamd_curve *cv, uint32_t stride)
 {

@@ -11,6 +11,10 @@
 #define ECAMD_STATUS_JAC 0xFD   /* internal: fast path stored a finite Jacobian result, finalisation pending */
 #define ECAMD_STATUS_REDO 0xFE  /* internal: fast path met an exceptional pair, redo with complete formulas */
 #define ECAMD_MAX_SLOTS_HOST 16 /* == ECAMD_MAX_SLOTS in ecamd_field.h */
+// secp256r1 fast path scratch per item (ecamd_p256_kernel.hip, sized by ecamd_host.cpp): 8 x 64-byte affine table records + 70 staging
+// quads of 16 bytes; both table layouts (signed windows 2P..8P, odd windows 3P..15P) static_assert that they fit
+#define P256_TAB_BYTES 512u
+#define P256_STG_QUADS 70u
 
 struct EcamdSmulArgs {
 	const uint8_t *scalars;  // n x slen, big-endian

@@ -189,6 +189,117 @@ U29_FN FYsel neg_y(const FX &y)
 	return weaken<FYsel>(carry(sub<1, 1>(zero, y)));
 }
 
+// ---- co-Z arithmetic (Meloni; the odd-multiple table of Longa-Miri): two points that share one Z ----
+// The window table [1, 3, ..., 2^w - 1]P is built as 2P then (2j + 1)P = 2P + (2j - 1)P by co-Z additions that keep 2P on
+// the Z of the new entry.  Each step multiplies Z by r = X(2P) - X((2j - 1)P), so Z_j = Z_0 r_1 ... r_j and the affine pass
+// walks the entries down from ONE inverse: 1/Z_{j-1} = r_j / Z_j.
+typedef F<MASK + 16, (2ull << 24), 32> FXc;        // co-Z X: fold() output or multiplication result (value < 2p)
+typedef F<MASK + 16, (4ull << 24), 63> FYc;        // co-Z Y: value < 63/16 p (its top limb stays below 4p's)
+typedef F<MASK + 15, (8ull << 24), 128> FR;         // carry() of X1 - X2 + 4p: the Z ratio of one co-Z addition
+struct CoZ {
+	FXc X;
+	FYc Y;
+};
+
+// dblu: affine P = (x, y) -> 2P and P, both on Z = 2y (3M + 3S; doubling with Z = 1 as in dbl, and P' = (4 x y^2, 8 y^4)
+// falls out of it).  y != 0: the group order is an odd prime, so P has no order 2.
+template <class AX, class AY> U29_FN void dblu(const AX &x, const AY &y, CoZ &D, CoZ &P1, FZ &z)
+{
+	const Fcanon one = constant<Fcanon>(K::ONE);
+	const auto gamma = sqr(y);                           // y^2
+	const auto beta4 = mul(x, mul_small<4>(gamma));      // 4 x y^2
+	const auto t1 = sub<1, 0>(x, one);                   // x - 1 (+2p)
+	const auto t2 = add(x, one);                         // x + 1
+	const auto alpha = carry(mul_small<3>(mul(t1, t2))); // 3 (x^2 - 1)
+	const auto a2 = sqr(alpha);
+	const auto x3 = fold(sub<2, 1>(a2, mul_small<2>(beta4)));
+	const auto g8 = mul_small<2>(sqr(mul_small<2>(gamma)));  // 8 y^4
+	const auto y3 = fold(sub<2, 2>(mul(alpha, sub<1, 1>(beta4, x3)), g8));
+	D.X = weaken<FXc>(x3);
+	D.Y = weaken<FYc>(y3);
+	P1.X = weaken<FXc>(beta4);
+	P1.Y = weaken<FYc>(carry(g8));
+	z = weaken<FZ>(mul_small<2>(y));
+}
+
+// zaddu: co-Z P1 + P2 -> R = P1 + P2 and P1 rescaled, both on Z r with r = X1 - X2 (5M + 2S).  Callers guarantee
+// P1 != +-P2 (X1 != X2): in the table chain P1 = 2P and P2 = (2j - 1)P, and 2P = +-(2j - 1)P would need a point order
+// dividing 2j + 1 or 2j - 3 <= 31, while the group order is a prime far above that.
+U29_FN void zaddu(CoZ &P1, const CoZ &P2, CoZ &R, FR &r)
+{
+	const auto h = carry(sub<2, 1>(P1.X, P2.X));         // X1 - X2 (+4p)
+	const auto c = sqr(h);
+	const auto w1 = mul(P1.X, c);                        // X1 (X1 - X2)^2
+	const auto w2 = mul(P2.X, c);                        // X2 (X1 - X2)^2
+	const auto dy = carry(sub<2, 1>(P1.Y, P2.Y));        // Y1 - Y2 (+4p)
+	const auto d = sqr(dy);
+	const auto a1 = mul(P1.Y, sub<1, 0>(w1, w2));        // Y1 (W1 - W2)
+	const auto x3 = fold(sub<2, 1>(d, add(w1, w2)));     // (Y1 - Y2)^2 - W1 - W2
+	const auto y3 = carry(sub<1, 0>(mul(dy, sub<1, 1>(w1, x3)), a1));
+	R.X = weaken<FXc>(x3);
+	R.Y = weaken<FYc>(y3);
+	P1.X = weaken<FXc>(w1);
+	P1.Y = weaken<FYc>(a1);
+	r = weaken<FR>(h);
+}
+
+// ---- regular odd-digit recoding (Joye-Tunstall) over WB-bit windows ----
+// k' = k, or k + q when k is even (same point, odd scalar; branch-free: the masked mode runs the same code), then
+// k' = sum_{j < t} d_j 2^(WB j) with every d_j odd in [-(2^WB - 1), 2^WB - 1]:  d_j = 2 e_j - (2^WB - 1) where e_j are the
+// WB-bit windows of E = (k' >> 1) + 2^(WB t - 1), t = ceil((max(8 slen, 256) + 1) / WB) (k' < 2^(max(8 slen, 256) + 1)).
+// The top window has e >= 2^(WB-1): its digit is positive.  kw: k in KW little-endian words; e: E in KW + 1 words, LEFT-
+// aligned (the top window in the top WB bits of e[KW]) -- E << s = ((k' - 1) << (s - 1)) + 2^(32 (KW + 1) - 1).  Returns t.
+// KW == 8 serves scalars of at most 32 bytes only, so t (and every shift) is a compile-time constant there.
+struct QOrder {
+	static constexpr u32 W[8] = {0xfc632551u, 0xf3b9cac2u, 0xa7179e84u, 0xbce6faadu, 0xffffffffu, 0xffffffffu, 0x00000000u, 0xffffffffu};
+};
+template <int KW, int WB> U29_FN int recode_odd(u32 *e, const u32 *kw, int slen)
+{
+	constexpr int NW = KW + 1;
+	const u32 even = (kw[0] & 1u) - 1u;  // all ones when k is even
+	u64 c = 0;
+#pragma unroll
+	for (int w = 0; w < KW; w++) {
+		c += (u64)kw[w] + (w < 8 ? (QOrder::W[w] & even) : 0u);
+		e[w] = (u32)c;
+		c >>= 32;
+	}
+	e[KW] = (u32)c;
+	e[0] &= ~1u;  // k' - 1
+	const int nbits = (KW == 8) ? 257 : ((8 * slen > 256 ? 8 * slen : 256) + 1);
+	const int t = (nbits + WB - 1) / WB;
+	const int sh = 32 * NW - WB * t - 1;
+	for (int s = 0; s < (sh >> 5); s++) {
+#pragma unroll
+		for (int w = NW - 1; w > 0; w--) {
+			e[w] = e[w - 1];
+		}
+		e[0] = 0;
+	}
+	const int bs = sh & 31;
+#pragma unroll
+	for (int w = NW - 1; w > 0; w--) {
+		e[w] = (u32)((((u64)e[w] << 32) | e[w - 1]) >> (32 - bs));
+	}
+	e[0] = (u32)(((u64)e[0] << 32) >> (32 - bs));
+	e[NW - 1] |= 0x80000000u;
+	return t;
+}
+// next window of a left-aligned E (top WB bits of e[NW - 1]), E shifted on; idx: table entry of |d| = 2 idx + 1; returns d < 0
+template <int NW, int WB> U29_FN bool odd_digit(u32 *e, u32 &idx)
+{
+	constexpr u32 HALF = 1u << (WB - 1);
+	const u32 win = e[NW - 1] >> (32 - WB);
+#pragma unroll
+	for (int w = NW - 1; w > 0; w--) {
+		e[w] = (e[w] << WB) | (e[w - 1] >> (32 - WB));
+	}
+	e[0] <<= WB;
+	const bool neg = win < HALF;
+	idx = (win & (HALF - 1)) ^ (neg ? HALF - 1 : 0u);
+	return neg;
+}
+
 U29_FN TabEnt to_tab(const Jac &P)
 {
 	TabEnt T;

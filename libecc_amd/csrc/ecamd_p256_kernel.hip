@@ -6,6 +6,7 @@
 //   * group: Jacobian a = -3 doubling (4M + 4S) and addition (12M + 4S) (ecamd_p256.h);
 //   * scalar: signed fixed window w = 4 over k' = k + 0x88...8 (digit = nibble - 8 in [-8, 7]),
 //     left to right, 4 doublings + 1 MIXED addition (8M + 3S) per window, AFFINE table [1..8]P;
+//     variable-base items take odd-digit windows over a co-Z table instead (section A2/B2/C2 below);
 //   * four kernels per batch, all inversions shared by Montgomery's trick over 8 items per lane:
 //       k_p256_table     import + on-curve check, Jacobian multiples 2P..8P
 //       k_p256_affine    table -> affine (one inversion per 56 table entries)
@@ -37,6 +38,7 @@ typedef uint8_t u8;
 #define TAB_ITEM_WORDS (TBL_ENTRIES * TAB_ENT_WORDS)
 #define STG_ENT_QUADS 10         /* staging record: X 0-8, Y 9-17, Z 18-26, (27), prefix product 28-36, (37-39) */
 #define STG_ITEM_QUADS (7 * STG_ENT_QUADS)
+static_assert(TAB_ITEM_WORDS * 4 <= P256_TAB_BYTES && STG_ITEM_QUADS <= P256_STG_QUADS, "scratch exceeds the host's per-item sizing");
 #ifndef FIN_K
 #define FIN_K 8                  /* items per lane in k_p256_finalize */
 #endif
@@ -183,12 +185,13 @@ static __device__ __forceinline__ Fmul prefix_load(u32 *stg, u32 i, int slot)
 }
 
 // ---- per-item affine table records: x || y, eight saturated words each ----
+template <int ITEM_WORDS = TAB_ITEM_WORDS>
 static __device__ __forceinline__ void tab_store(u32 *tab, u32 i, int e, const Fcanon &x, const Fcanon &y)
 {
 	u32 w[16];
 	to_words(w, x);
 	to_words(w + 8, y);
-	uint4 *d = (uint4 *)(tab + (size_t)i * TAB_ITEM_WORDS + e * TAB_ENT_WORDS);
+	uint4 *d = (uint4 *)(tab + (size_t)i * ITEM_WORDS + e * TAB_ENT_WORDS);
 #pragma unroll
 	for (int q = 0; q < 4; q++) {
 		d[q] = make_uint4(w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]);
@@ -208,6 +211,7 @@ static __device__ __forceinline__ void tab_load(const u32 *tab, u32 e, Fcanon &x
 }
 // Constant-address look-ups for secret digits (ecamd_ctx_set_secret_scalars): all eight entries are read, in the same order
 // whatever the digit, and the wanted one is kept by masking (cf. tbl_load_masked in ecamd_kernels.hip)
+template <u32 NENT = TBL_ENTRIES>
 static __device__ __forceinline__ void tab_load_masked(const u32 *tab, u32 idx, Fcanon &x, Fcanon &y)
 {
 	u32 w[16];
@@ -216,7 +220,7 @@ static __device__ __forceinline__ void tab_load_masked(const u32 *tab, u32 idx, 
 		w[k] = 0;
 	}
 #pragma unroll 1
-	for (u32 e = 0; e < TBL_ENTRIES; e++) {
+	for (u32 e = 0; e < NENT; e++) {
 		const uint4 *s = (const uint4 *)(tab + (size_t)e * TAB_ENT_WORDS);
 		const u32 m = 0u - (u32)(e == idx);
 #pragma unroll
@@ -276,21 +280,19 @@ static __device__ __forceinline__ void zero_out(u8 *out)
 // ------------------------------------------------------------------------------------------
 // A. import + Jacobian multiples 2P..8P
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(64) void k_p256_table(EcamdSmulArgs A)
+// import: X||Y big-endian, coordinates < p, on the curve (curves/prj_pt.c:511-552); a rejected item gets status 1 and a
+// zero output here
+typedef MulOut<17>::type PtIn;  // Montgomery form, value < 17/16 p
+static __device__ __forceinline__ bool import_point(const EcamdSmulArgs &A, u32 i, PtIn &xm, PtIn &ym)
 {
-	const u32 i = blockIdx.x * 64 + threadIdx.x;
-	if (i >= A.n) {
-		return;
-	}
-	// ---- import: X||Y big-endian, coordinates < p, on the curve (curves/prj_pt.c:511-552) ----
 	const u8 *pin = A.points + (size_t)i * A.pstride;
 	u32 xw[8], yw[8];
 	load_be256(pin, xw);
 	load_be256(pin + 32, yw);
 	bool ok = lt_p(xw) & lt_p(yw);
 	const Fcanon r2 = constant<Fcanon>(K::R2);
-	const auto xm = mul(from_words(xw), r2);  // Montgomery form, value < 17/16 p
-	const auto ym = mul(from_words(yw), r2);
+	xm = mul(from_words(xw), r2);
+	ym = mul(from_words(yw), r2);
 	{
 		// y^2 == x^3 - 3x + b  <=>  (x^3 + b + 8p - 3x) - y^2 == 0; the difference goes through one
 		// more multiplication (by 1) so that the zero test runs on exact digits
@@ -302,6 +304,18 @@ __global__ __launch_bounds__(64) void k_p256_table(EcamdSmulArgs A)
 	if (!ok) {
 		A.status[i] = 1;
 		zero_out(A.out + (size_t)i * 64);
+	}
+	return ok;
+}
+
+__global__ __launch_bounds__(64) void k_p256_table(EcamdSmulArgs A)
+{
+	const u32 i = blockIdx.x * 64 + threadIdx.x;
+	if (i >= A.n) {
+		return;
+	}
+	PtIn xm, ym;
+	if (!import_point(A, i, xm, ym)) {
 		return;
 	}
 	const Fcanon xa = canonical(xm), ya = canonical(ym);
@@ -543,6 +557,233 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P256_WAVES, 
 		return;
 	}
 	jac_store(A.stg, i, 0, acc);
+	A.status[i] = ECAMD_STATUS_JAC;
+}
+
+// ------------------------------------------------------------------------------------------
+// A2/B2/C2. the per-item-table path: regular odd-digit windows of ODD_WB = 4 bits over a co-Z table
+//   scalar  k' = k or k + q (odd), t windows, every digit odd in [-15, 15] (recode_odd, ecamd_p256.h); k + q is 256 bits, so
+//           a scalar of fewer than 32 bytes still takes t = 65 windows (the signed window took 2 slen);
+//   table   [1, 3, ..., 15]P: dblu, then one co-Z addition (zaddu) per entry -- no exceptional pair possible;
+//   affine  Montgomery's trick over the LAST Z of AFF_K items per lane, then entry by entry down the chain's Z ratios;
+//   loop    top digit (positive) -> accumulator, then t - 1 windows of 4 doublings + 1 mixed addition.  No digit is zero, so
+//           there is no infinity flag and nothing to select: every addition checks its exceptional pair (hz).  For k' < 2q
+//           (scalars of up to 32 bytes) the partial sums before the last window lie in [1, q / 8), so only the last addition can
+//           meet one: when k' = 0 or 2 d0 mod q for the last digit d0 -- k = q - 2 (k' = q - 2, d0 = -1) is such a scalar below
+//           q, besides k = 0 and scalars of q or more; longer (blinded) scalars can meet one at any window.  Such an item goes to
+//           the complete kernel (ECAMD_STATUS_REDO), in the masked mode too, as on the signed-window path.
+//   staging per block of 64 items, quad-major / lane-minor: entry e = 1..NE-1 at quads 7 (e - 1) .. 7 e - 1 (X 0-8, Y 9-17,
+//           r 18-26, 27), the last Z at ODD_ZQ .. + 2 and its prefix product at ODD_ZQ + 3 .. + 5
+// P256_ODD_WINDOWS=0 builds the earlier pipeline (k_p256_table / k_p256_affine / k_p256_loop) for A/B comparisons.
+// ------------------------------------------------------------------------------------------
+#ifndef P256_ODD_WINDOWS
+#define P256_ODD_WINDOWS 1
+#endif
+#define ODD_WB 4                                    /* window bits */
+#define ODD_NE (1 << (ODD_WB - 1))                  /* table entries */
+#define ODD_TAB_ITEM_WORDS (ODD_NE * TAB_ENT_WORDS)
+#define ODD_ENT_QUADS 7
+#define ODD_ZQ ((ODD_NE - 1) * ODD_ENT_QUADS)
+#define ODD_ITEM_QUADS (ODD_ZQ + 6)
+static_assert(ODD_TAB_ITEM_WORDS * 4 <= P256_TAB_BYTES && ODD_ITEM_QUADS <= P256_STG_QUADS, "odd-window scratch exceeds the host's per-item sizing");
+
+static __device__ __forceinline__ uint4 *odd_quad(u32 *stg, u32 i, int q)
+{
+	return (uint4 *)stg + ((size_t)(i >> 6) * ODD_ITEM_QUADS + (size_t)q) * 64 + (i & 63u);
+}
+template <class T> static __device__ __forceinline__ void odd_store9(u32 *stg, u32 i, int q, const T &a)
+{
+	*odd_quad(stg, i, q) = make_uint4(a.l[0], a.l[1], a.l[2], a.l[3]);
+	*odd_quad(stg, i, q + 1) = make_uint4(a.l[4], a.l[5], a.l[6], a.l[7]);
+	*odd_quad(stg, i, q + 2) = make_uint4(a.l[8], 0u, 0u, 0u);
+}
+template <class T> static __device__ __forceinline__ T odd_load9(u32 *stg, u32 i, int q)
+{
+	const uint4 a = *odd_quad(stg, i, q), b = *odd_quad(stg, i, q + 1), c = *odd_quad(stg, i, q + 2);
+	T r;
+	r.l[0] = a.x; r.l[1] = a.y; r.l[2] = a.z; r.l[3] = a.w;
+	r.l[4] = b.x; r.l[5] = b.y; r.l[6] = b.z; r.l[7] = b.w;
+	r.l[8] = c.x;
+	return r;
+}
+static __device__ __forceinline__ void odd_ent_store(u32 *stg, u32 i, int e, const CoZ &T, const FR &r)
+{
+	u32 b[28];
+#pragma unroll
+	for (int w = 0; w < 9; w++) {
+		b[w] = T.X.l[w];
+		b[9 + w] = T.Y.l[w];
+		b[18 + w] = r.l[w];
+	}
+	b[27] = 0;
+#pragma unroll
+	for (int q = 0; q < ODD_ENT_QUADS; q++) {
+		*odd_quad(stg, i, (e - 1) * ODD_ENT_QUADS + q) = make_uint4(b[4 * q], b[4 * q + 1], b[4 * q + 2], b[4 * q + 3]);
+	}
+}
+static __device__ __forceinline__ void odd_ent_load(u32 *stg, u32 i, int e, CoZ &T, FR &r)
+{
+	u32 b[28];
+#pragma unroll
+	for (int q = 0; q < ODD_ENT_QUADS; q++) {
+		const uint4 v = *odd_quad(stg, i, (e - 1) * ODD_ENT_QUADS + q);
+		b[4 * q] = v.x; b[4 * q + 1] = v.y; b[4 * q + 2] = v.z; b[4 * q + 3] = v.w;
+	}
+#pragma unroll
+	for (int w = 0; w < 9; w++) {
+		T.X.l[w] = b[w];
+		T.Y.l[w] = b[9 + w];
+		r.l[w] = b[18 + w];
+	}
+}
+
+// A2. import + the odd multiples 3P .. (2 NE - 1)P on one co-Z chain (dblu + NE - 1 zaddu)
+__global__ __launch_bounds__(64) void k_p256_table_odd(EcamdSmulArgs A)
+{
+	const u32 i = blockIdx.x * 64 + threadIdx.x;
+	if (i >= A.n) {
+		return;
+	}
+	PtIn xm, ym;
+	if (!import_point(A, i, xm, ym)) {
+		return;
+	}
+	tab_store<ODD_TAB_ITEM_WORDS>(A.tbl, i, 0, canonical(xm), canonical(ym));  // entry 0: P itself, already affine
+	// no exceptional pair in the chain: 2P = +-(2j - 1)P would need an order dividing 2j + 1 or 2j - 3, and the group order is a
+	// prime far above 2^WB
+	CoZ D, T;
+	FZ z;
+	dblu(xm, ym, D, T, z);
+#pragma unroll 1
+	for (int e = 1; e < ODD_NE; e++) {
+		CoZ Tn;
+		FR r;
+		zaddu(D, T, Tn, r);
+		z = weaken<FZ>(mul(z, r));
+		odd_ent_store(A.stg, i, e, Tn, r);
+		T = Tn;
+	}
+	odd_store9(A.stg, i, ODD_ZQ, z);
+	A.status[i] = ECAMD_STATUS_TAB;
+}
+
+// B2. table -> affine: one inversion for the last Z of `items` items per lane (nthreads: a multiple of 64, as in k_p256_affine),
+//     then per entry (4M + 1S): x = X z^-2, y = Y z^-3, z^-1 <- z^-1 r
+__global__ __launch_bounds__(64) void k_p256_affine_coz(EcamdSmulArgs A, u32 nthreads, int items)
+{
+	const u32 t = blockIdx.x * 64 + threadIdx.x;
+	if (t >= nthreads) {
+		return;
+	}
+	Fmul c = weaken<Fmul>(constant<Fcanon>(K::ONE));
+#pragma unroll 1
+	for (int j = 0; j < items; j++) {
+		const u32 i = t + (u32)j * nthreads;
+		if (i >= A.n) {
+			break;
+		}
+		if (A.status[i] != ECAMD_STATUS_TAB) {
+			continue;
+		}
+		const FZ z = odd_load9<FZ>(A.stg, i, ODD_ZQ);
+		odd_store9(A.stg, i, ODD_ZQ + 3, c);  // the prefix BEFORE this item
+		c = weaken<Fmul>(mul(c, z));
+	}
+	Fmul tinv = inv(c);
+#pragma unroll 1
+	for (int j = items - 1; j >= 0; j--) {
+		const u32 i = t + (u32)j * nthreads;
+		if (i >= A.n || A.status[i] != ECAMD_STATUS_TAB) {
+			continue;
+		}
+		Fmul zi = weaken<Fmul>(mul(tinv, odd_load9<Fmul>(A.stg, i, ODD_ZQ + 3)));
+		tinv = weaken<Fmul>(mul(tinv, odd_load9<FZ>(A.stg, i, ODD_ZQ)));
+#pragma unroll 1
+		for (int e = ODD_NE - 1; e >= 1; e--) {
+			CoZ T;
+			FR r;
+			odd_ent_load(A.stg, i, e, T, r);
+			const Fmul zi2 = weaken<Fmul>(sqr(zi));
+			const Fmul zi3 = weaken<Fmul>(mul(zi2, zi));
+			tab_store<ODD_TAB_ITEM_WORDS>(A.tbl, i, e, canonical(mul(T.X, zi2)), canonical(mul(T.Y, zi3)));
+			if (e > 1) {
+				zi = weaken<Fmul>(mul(zi, r));
+			}
+		}
+	}
+}
+
+// C2. the odd-digit window loop (KW, MASKED as in k_p256_loop)
+template <int KW, bool MASKED>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P256_WAVES, P256_WAVES))) void k_p256_loop_odd(EcamdSmulArgs A)
+{
+	const u32 i = blockIdx.x * 64 + threadIdx.x;
+	if (i >= A.n || A.status[i] != ECAMD_STATUS_TAB) {
+		return;
+	}
+	const u32 *tabi = A.tbl + (size_t)i * ODD_TAB_ITEM_WORDS;  // this item's affine table
+	const int slen = (int)A.slen;
+	u32 e[KW + 1];
+	int nwin;
+	{
+		u32 kw[KW];
+		const u8 *sc = A.scalars + (size_t)i * A.sstride;
+		if (KW == 8 && slen == 32) {
+			load_be256(sc, kw);
+		} else {
+#pragma unroll
+			for (int w = 0; w < KW; w++) {
+				u32 x = 0;
+#pragma unroll
+				for (int b = 0; b < 4; b++) {
+					const int pos = 4 * w + b;
+					if (pos < slen) {
+						x |= (u32)sc[slen - 1 - pos] << (8 * b);
+					}
+				}
+				kw[w] = x;
+			}
+		}
+		nwin = recode_odd<KW, ODD_WB>(e, kw, slen);
+	}
+	Jac acc;
+	{
+		u32 idx;
+		(void)odd_digit<KW + 1, ODD_WB>(e, idx);  // the top digit is positive
+		Fcanon px, py;
+		if (MASKED) {
+			tab_load_masked<ODD_NE>(tabi, idx, px, py);
+		} else {
+			tab_load(tabi, idx, px, py);
+		}
+		acc.X = weaken<FX>(px);
+		acc.Y = weaken<FY>(py);
+		acc.Z = weaken<FZ>(constant<Fcanon>(K::ONE));
+	}
+	bool bad = false, hz;
+#pragma unroll 1
+	for (int t = 1; t < nwin; t++) {
+#pragma unroll 1
+		for (int d = 0; d < ODD_WB; d++) {
+			acc = dbl(acc);
+		}
+		u32 idx;
+		const bool neg = odd_digit<KW + 1, ODD_WB>(e, idx);
+		Fcanon tx, tyc;
+		if (MASKED) {
+			tab_load_masked<ODD_NE>(tabi, idx, tx, tyc);
+		} else {
+			tab_load(tabi, idx, tx, tyc);
+		}
+		const FYaff ty = sel(neg, neg_aff(tyc), weaken<FYaff>(tyc));
+		acc = madd(acc, tx, ty, hz);
+		bad = bad | hz;
+	}
+	if (bad) {
+		A.status[i] = ECAMD_STATUS_REDO;  // exceptional pair met: the complete-formula kernel recomputes the item
+		return;
+	}
+	jac_store(A.stg, i, 0, acc);  // -> k_p256_finalize (its staging layout: slot 0 of STG_ITEM_QUADS)
 	A.status[i] = ECAMD_STATUS_JAC;
 }
 
@@ -1027,14 +1268,33 @@ hipError_t ecamd_launch_smul_p256(const EcamdSmulArgs &a, hipStream_t s, hipEven
 		(void)hipMemsetAsync(a.status, ECAMD_STATUS_TAB, a.n, s);
 		P256_MARK(1);
 	} else {
-		hipLaunchKernelGGL(k_p256_table, grid, block, 0, s, a);
-		P256_MARK(1);
 		const uint32_t ak = (uint32_t)p256_items_per_inversion(a.n, AFF_K);
 		const uint32_t athreads = (((a.n + ak - 1) / ak) + 63u) & ~63u;
-		hipLaunchKernelGGL(k_p256_affine, dim3((athreads + 63) / 64), block, 0, s, a, athreads, (int)ak);
+		if (P256_ODD_WINDOWS) {
+			hipLaunchKernelGGL(k_p256_table_odd, grid, block, 0, s, a);
+			P256_MARK(1);
+			hipLaunchKernelGGL(k_p256_affine_coz, dim3((athreads + 63) / 64), block, 0, s, a, athreads, (int)ak);
+		} else {
+			hipLaunchKernelGGL(k_p256_table, grid, block, 0, s, a);
+			P256_MARK(1);
+			hipLaunchKernelGGL(k_p256_affine, dim3((athreads + 63) / 64), block, 0, s, a, athreads, (int)ak);
+		}
 	}
 	P256_MARK(2);
-	if (a.lut && a.lut_kind == 1) {
+	if (!a.lut && P256_ODD_WINDOWS) {
+		// the per-item table path: odd-digit windows (secret scalars: masked look-ups; blinded scalars: KW = 17)
+		if (a.masked) {
+			if (a.slen <= 32) {
+				hipLaunchKernelGGL((k_p256_loop_odd<8, true>), grid, block, 0, s, a);
+			} else {
+				hipLaunchKernelGGL((k_p256_loop_odd<17, true>), grid, block, 0, s, a);
+			}
+		} else if (a.slen <= 32) {
+			hipLaunchKernelGGL((k_p256_loop_odd<8, false>), grid, block, 0, s, a);
+		} else {
+			hipLaunchKernelGGL((k_p256_loop_odd<17, false>), grid, block, 0, s, a);
+		}
+	} else if (a.lut && a.lut_kind == 1) {
 		hipLaunchKernelGGL(k_p256_comb, grid, block, 0, s, a);
 	} else if (a.lut && a.lut_kind == 3) {
 		hipLaunchKernelGGL(k_p256_comb4m, grid, block, 0, s, a);
