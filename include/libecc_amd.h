@@ -197,6 +197,23 @@ int ec_fp_op_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int op, uint32_t n,
  */
 int ec_ecdsa_verify_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const uint8_t *pubkeys_aff,
 			  const uint8_t *sigs, const uint8_t *digests, uint32_t digest_len, uint8_t *result);
+/*
+ * ECDSA public-key recovery, batch of independent (signature, digest) pairs: per item
+ *   ecdsa_public_key_from_sig(pub1, pub2, params, sig, 2*qlen, h, hlen)              sig/ecdsa.c (decdsa_public_key_from_sig: sig/decdsa.c)
+ *     -> __ecdsa_public_key_from_sig                                                 sig/ecdsa_common.c:867-1049
+ *   ec_pub_key_export_to_aff_buf(pub1 / pub2, out, 2*clen)                           sig/ec_key.c
+ * the call libecc's self tests make after every ECDSA / DECDSA signature (tests/ec_self_tests_core.c:423, :839).
+ * sigs: n x 2*qlen (r || s big-endian), digests: n x digest_len (1 .. 128 bytes).  pub1_aff / pub2_aff: n x 2*clen, the affine
+ * X || Y of the reference's two candidate keys Y1 = [v](r, y1) + [u]G and Y2 = [v](r, y2) + [u]G, u = -(e / r), v = s / r mod q,
+ * (y1, y2) the roots in aff_pt_y_from_x's order.  status1[i] / status2[i]: ECAMD_ERR in both (zero bytes) where the reference
+ * returns -1 -- r or s outside [1, q - 1], r >= p, r no abscissa of the curve (the reference's "restart" with r + 2q never
+ * succeeds: :908-925 with fp_set_nn, fp/fp.c:204-220) --; otherwise, per key, ECAMD_OK or ECAMD_INF (zero bytes: that key is
+ * the point at infinity, which the reference returns without complaint).  No recovery id: the reference has none.  On curves with
+ * a cofactor the signer's key is mostly not among the two, as the reference's own comment says; the bytes are the reference's.
+ * Every multiplier is public, so the call runs its public-scalar kernels whatever ecamd_ctx_set_secret_scalars says.
+ */
+int ec_ecdsa_recover_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const uint8_t *sigs, const uint8_t *digests,
+			   uint32_t digest_len, uint8_t *pub1_aff, uint8_t *pub2_aff, uint8_t *status1, uint8_t *status2);
 /* The same with a choice of public-key format: ECAMD_PT_PROJECTIVE keys are n x 3*clen, X || Y || Z as ec_pub_key_export_to_buf
  * writes pub_key->y (sig/ec_key.c:254): imported like prj_pt_import_from_buf, normalised on the device.  A key that is the point
  * at infinity is a key for libecc (its import accepts (0 : 1 : 0)); verification against it is W' = uG, reproduced here. */
@@ -482,6 +499,10 @@ int ec_structured_key_pair_import_batch(ecamd_ctx *ctx, const ecamd_curve *curve
 int ec_ecdsa_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const void *d_pubkeys_aff,
 			      const void *d_sigs, const void *d_digests, uint32_t digest_len, void *d_result,
 			      void *hip_stream);
+/* ec_ecdsa_recover_batch with device pointers: enqueue only, in pieces of at most ecamd_ctx_set_max_chunk items. */
+int ec_ecdsa_recover_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const void *d_sigs, const void *d_digests,
+			       uint32_t digest_len, void *d_pub1_aff, void *d_pub2_aff, void *d_status1, void *d_status2,
+			       void *hip_stream);
 int ec_eddsa_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const void *d_pubkeys,
 			      const void *d_sigs, const void *d_hram, uint32_t hram_len, void *d_result,
 			      void *hip_stream);

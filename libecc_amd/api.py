@@ -28,6 +28,7 @@ EXPORTED_SYMBOLS = [
     "ecamd_multi_allgather_streams", "ecamd_multi_eddsa_sign_R_batch", "ecamd_multi_eddsa_sign_S_batch",
     "ecamd_multi_set_secret_scalars", "ecamd_multi_wipe_scratch", "ecamd_ctx_wipe_scratch", "ecamd_ctx_stream", "ecamd_host_alloc", "ecamd_host_free", "ecamd_ctx_dominant_kernel_ms", "ecamd_ctx_set_msm_seed", "ecamd_ctx_discard_msm_seed", "ecamd_multi_set_msm_seed", "ec_eddsa_verify_ph_prj_batch", "ecamd_multi_eddsa_verify_ph_prj_batch", "ec_nn_random_mod_batch", "ec_ecdsa_sign_msg_batch", "ec_key_pair_gen_raw_batch", "ecamd_multi_ecdsa_sign_msg_batch", "ecamd_multi_key_pair_gen_raw_batch", "ec_eddsa_verify_msg_prj_batch", "ecamd_multi_eddsa_verify_msg_prj_batch", "ecamd_ctx_set_host_ready_hook", "ecamd_multi_set_host_ready_hook", "ecamd_multi_prj_pt_add_batch",
     "ec_schnorr_verify_all_batch", "ec_schnorr_verify_all_batch_dev", "ec_schnorr_verify_msg_all_batch", "ec_eddsa_verify_msg_prj_all_batch", "ecamd_multi_eddsa_verify_msg_prj_all_batch", "ecamd_multi_schnorr_verify_msg_all_batch", "ec_schnorr_verify_all_available", "ecamd_multi_schnorr_verify_all_batch", "ecamd_debug_schnorr_msm", "ecamd_debug_schnorr_msm_words",
+    "ec_ecdsa_recover_batch", "ec_ecdsa_recover_batch_dev",
 ]
 
 
@@ -104,6 +105,8 @@ def load_library():
         L.ec_structured_sig_import_batch.argtypes = [vp, u32, u8p, u32, C.c_int, C.c_int, u8p, u8p]
         L.ec_structured_key_pair_import_batch.argtypes = [vp, vp, u32, u8p, u32, C.c_int, u8p, u8p, u8p]
         L.ec_ecdsa_verify_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp]
+        L.ec_ecdsa_recover_batch.argtypes = [vp, vp, u32, u8p, u8p, u32, u8p, u8p, u8p, u8p]
+        L.ec_ecdsa_recover_batch_dev.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp]
         L.ec_eddsa_verify_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp]
         L.ec_eddsa_sign_R_batch.argtypes = [vp, vp, u32, u8p, u8p, u8p]
         L.ec_eddsa_sign_S_batch.argtypes = [vp, vp, u32, u8p, u8p, u8p, u8p]
@@ -284,6 +287,16 @@ class Curve:
         _chk(self.L, self.L.ec_ecdsa_verify_batch(self.ctx.h, self.h, n, pubs, sigs, digests, hlen, res),
              "ec_ecdsa_verify_batch")
         return res.raw[:n]
+
+    def ecdsa_recover(self, sigs, digests, hlen):
+        """ecdsa_public_key_from_sig: (pub1, pub2, status1, status2), the reference's two candidate keys (affine X || Y) per
+        (signature, digest) pair; ECAMD_ERR in both statuses where the reference returns -1, ECAMD_INF for a key at infinity"""
+        n = len(sigs) // (2 * self.qlen)
+        p1, p2 = C.create_string_buffer(max(1, 2 * self.clen * n)), C.create_string_buffer(max(1, 2 * self.clen * n))
+        s1, s2 = C.create_string_buffer(max(1, n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_ecdsa_recover_batch(self.ctx.h, self.h, n, sigs, digests, hlen, p1, p2, s1, s2),
+             "ec_ecdsa_recover_batch")
+        return p1.raw[:2 * self.clen * n], p2.raw[:2 * self.clen * n], s1.raw[:n], s2.raw[:n]
 
     @staticmethod
     def msg_slots(msgs, stride=None):
@@ -501,6 +514,10 @@ class Curve:
     def ecdsa_verify_dev(self, n, d_pubs, d_sigs, d_digests, hlen, d_result, stream=None):
         _chk(self.L, self.L.ec_ecdsa_verify_batch_dev(self.ctx.h, self.h, n, d_pubs, d_sigs, d_digests, hlen, d_result,
                                                        stream), "ec_ecdsa_verify_batch_dev")
+
+    def ecdsa_recover_dev(self, n, d_sigs, d_digests, hlen, d_pub1, d_pub2, d_st1, d_st2, stream=None):
+        _chk(self.L, self.L.ec_ecdsa_recover_batch_dev(self.ctx.h, self.h, n, d_sigs, d_digests, hlen, d_pub1, d_pub2, d_st1,
+                                                        d_st2, stream), "ec_ecdsa_recover_batch_dev")
 
     def eddsa_verify_dev(self, n, d_pubs, d_sigs, d_hram, d_result, stream=None, hram_len=64):
         _chk(self.L, self.L.ec_eddsa_verify_batch_dev(self.ctx.h, self.h, n, d_pubs, d_sigs, d_hram, hram_len, d_result,

@@ -6000,6 +6000,152 @@ extern "C" int ec_point_decompress_batch(ecamd_ctx *ctx, const ecamd_curve *cv, 
 }
 
 // ------------------------------------------------------------------------------------------
+// batched ECDSA public-key recovery: ecdsa_public_key_from_sig / decdsa_public_key_from_sig (sig/ecdsa.c, sig/decdsa.c ->
+// __ecdsa_public_key_from_sig, sig/ecdsa_common.c:867-1049) + ec_pub_key_export_to_aff_buf (sig/ec_key.c) of the two keys
+// ------------------------------------------------------------------------------------------
+// The reference: three prj_pt_mul and two prj_pt_add per item (:988-994).  Here, per chunk of at most max_chunk items:
+//   k_recover_prep    range checks, e, u = -(e / r), v = s / r mod q, x = r as a field element (r >= p: the reference's -1)
+//   k_y_from_x        the two roots in fp_sqrt's order; an x that is no abscissa is the reference's -1 (its "restart" with
+//                     r + 2q can only fail: the comparison at :921 refuses a candidate below p, fp_set_nn one that is not)
+//   k_recover_point   R = (x, y1)
+//   A = [u]G          ONE fixed-base pass (the generator's comb table where the handle has one)
+//   B = [v]R          ONE variable-base window loop; (x, y2) = -R, so [v](x, y2) = -B is never computed
+//   k_recover_fin     Y1 = A + B, Y2 = A - B, two chords with the denominator x_B - x_A, inverted together for eight items
+//   k_recover_redo    the items with A or B at infinity or x_A = x_B, on the complete formulas (nothing marked: a near-empty launch)
+// Every multiplier is a function of the signature and the digest: public, whatever ecamd_ctx_set_secret_scalars says.
+// stage: 3 u, 4 v, 5 A, 6 B, 7 stA, 8 stB, 9 flags, 10 status of k_y_from_x, 11 x, 12 y1, 13 y2, 14 R.  Only enqueues.
+static int ecdsa_recover_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const uint8_t *d_sig, const uint8_t *d_dig,
+				    uint32_t hlen, uint8_t *d_pub1, uint8_t *d_pub2, uint8_t *d_st1, uint8_t *d_st2, hipStream_t s)
+{
+	ecamd_curve *cv = const_cast<ecamd_curve *>(cv_in);
+	if (sqrt_setup(cv)) {
+		return -1;
+	}
+	PublicScalars pub_scope(ctx);
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	const size_t need[15] = {0, 0, 0, chunk * ql, chunk * ql, chunk * plen, chunk * plen, chunk, chunk, chunk, chunk,
+				 chunk * cl, chunk * cl, chunk * cl, chunk * plen};
+	for (int i = 3; i < 15; i++) {
+		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
+			return -1;
+		}
+	}
+	uint8_t **S = ctx->stage;
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		EcamdRecoverPrepArgs P;
+		memset(&P, 0, sizeof(P));
+		P.sigs = d_sig + (size_t)off * 2 * ql;
+		P.digests = d_dig + (size_t)off * hlen;
+		P.u = S[3];
+		P.v = S[4];
+		P.x = S[11];
+		P.flags = S[9];
+		P.n = m;
+		P.qlen = (uint32_t)ql;
+		P.clen = (uint32_t)cl;
+		P.hlen = hlen;
+		P.qbits = (uint32_t)cv->qbits;
+		P.qslot = cv->qslot;
+		big_to_be(P.p_be, (int)cl, cv->p);
+		HIPCHK(ecamd_launch_recover_prep(cv->qnw, P, s));
+		EcamdYfromXArgs Y = cv->sqrt_tmpl;
+		Y.x = S[11];
+		Y.xstride = (uint32_t)cl;
+		Y.y1 = S[12];
+		Y.y2 = S[13];
+		Y.aff = S[12];
+		Y.status = S[10];
+		Y.n = m;
+		Y.mode = 0;
+		HIPCHK(ecamd_launch_y_from_x(cv->nw, Y, s));
+		EcamdRecoverPointArgs R;
+		R.x = S[11];
+		R.y1 = S[12];
+		R.flags = S[9];
+		R.yst = S[10];
+		R.R = S[14];
+		R.n = m;
+		R.clen = (uint32_t)cl;
+		HIPCHK(ecamd_launch_recover_point(R, s));
+		if (smul_dev_locked(ctx, cv, m, S[3], (uint32_t)ql, nullptr, S[5], S[7], s) ||   // A = [u]G (:988)
+		    smul_dev_locked(ctx, cv, m, S[4], (uint32_t)ql, S[14], S[6], S[8], s)) {     // B = [v](x, y1) (:990)
+			return -1;
+		}
+		EcamdRecoverFinArgs F;
+		F.A = S[5];
+		F.stA = S[7];
+		F.B = S[6];
+		F.stB = S[8];
+		F.flags = S[9];
+		F.yst = S[10];
+		F.out1 = d_pub1 + (size_t)off * plen;
+		F.out2 = d_pub2 + (size_t)off * plen;
+		F.st1 = d_st1 + off;
+		F.st2 = d_st2 + off;
+		F.n = m;
+		F.clen = (uint32_t)cl;
+		F.slot = cv->slot;
+		HIPCHK(ecamd_launch_recover_fin(cv->nw, F, s));
+		HIPCHK(ecamd_launch_recover_redo(cv->nw, F, s));
+	}
+	return 0;
+}
+
+static int ecdsa_recover_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const void *sigs, const void *digests,
+				 uint32_t hlen, const void *o1, const void *o2, const void *s1, const void *s2)
+{
+	if (!ctx || !cv || cv->ctx != ctx || (n && (!sigs || !digests || !o1 || !o2 || !s1 || !s2))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	if (hlen == 0 || hlen > 128) {
+		return fail(std::string(fn) + ": digest length must be in 1..128");
+	}
+	return 0;
+}
+
+extern "C" int ec_ecdsa_recover_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const void *d_sigs, const void *d_digests,
+					  uint32_t hlen, void *d_pub1_aff, void *d_pub2_aff, void *d_status1, void *d_status2, void *hip_stream)
+{
+	if (ecdsa_recover_args_ok("ec_ecdsa_recover_batch_dev", ctx, cv, n, d_sigs, d_digests, hlen, d_pub1_aff, d_pub2_aff, d_status1, d_status2)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return ecdsa_recover_dev_locked(ctx, cv, n, (const uint8_t *)d_sigs, (const uint8_t *)d_digests, hlen, (uint8_t *)d_pub1_aff,
+					(uint8_t *)d_pub2_aff, (uint8_t *)d_status1, (uint8_t *)d_status2, s);
+}
+
+extern "C" int ec_ecdsa_recover_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *sigs, const uint8_t *digests,
+				      uint32_t hlen, uint8_t *pub1_aff, uint8_t *pub2_aff, uint8_t *status1, uint8_t *status2)
+{
+	if (ecdsa_recover_args_ok("ec_ecdsa_recover_batch", ctx, cv, n, sigs, digests, hlen, pub1_aff, pub2_aff, status1, status2)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t plen = (size_t)2 * cv->clen;
+	const std::vector<HostArr> arrs = {{sigs, nullptr, (size_t)2 * cv->qlen}, {digests, nullptr, hlen}, {nullptr, pub1_aff, plen},
+					   {nullptr, pub2_aff, plen}, {nullptr, status1, 1}, {nullptr, status2, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+						       hipStream_t s, const std::function<int()> &) {
+		return ecdsa_recover_dev_locked(ctx, cv, m, ip[0], ip[1], hlen, op[2], op[3], op[4], op[5], s);
+	});
+}
+
+// ------------------------------------------------------------------------------------------
 // structured signatures and private keys: 3 header bytes in front of the raw bytes (sig/sig_algs.c:702-780, sig/ec_key.c:312-360)
 // ------------------------------------------------------------------------------------------
 extern "C" int ec_structured_sig_import_batch(const ecamd_curve *cv, uint32_t n, const uint8_t *structured, uint32_t structured_len,

@@ -101,6 +101,38 @@ hipError_t ecamd_launch_ecdsa_sign(int nw, const EcamdEcdsaSignArgs &a, hipStrea
 hipError_t ecamd_launch_ecdsa_prep(int nw, const EcamdEcdsaPrepArgs &a, hipStream_t s);
 hipError_t ecamd_launch_ecdsa_fin(int nw, const EcamdEcdsaFinArgs &a, hipStream_t s);
 
+// ---- ECDSA public-key recovery (sig/ecdsa_common.c:867-1049 of the reference), ecamd_recover_kernels.h ----
+struct EcamdRecoverPrepArgs {
+	const uint8_t *sigs;     // n x 2*qlen, r || s big-endian
+	const uint8_t *digests;  // n x hlen
+	uint8_t *u, *v;          // n x qlen big-endian: -(e/r) mod q, s/r mod q (zeros where flagged)
+	uint8_t *x;              // n x clen big-endian: r as a field element (zeros where flagged)
+	uint8_t *flags;          // n: 0 ok, 1 the reference returns -1 (r or s not in [1, q-1], or r >= p)
+	uint32_t n, qlen, clen, hlen, qbits;
+	int qslot;               // constant slot holding the Montgomery context of the generator order q
+	uint8_t p_be[72];        // the field prime, clen bytes big-endian
+};
+struct EcamdRecoverPointArgs {
+	const uint8_t *x, *y1;   // n x clen each (k_recover_prep, k_y_from_x)
+	const uint8_t *flags, *yst;
+	uint8_t *R;              // n x 2*clen: x || y1, zeros where flags or yst is set
+	uint32_t n, clen;
+};
+struct EcamdRecoverFinArgs {
+	const uint8_t *A, *stA;  // [u]G affine + status
+	const uint8_t *B, *stB;  // [v](x, y1) affine + status
+	const uint8_t *flags;    // k_recover_prep
+	const uint8_t *yst;      // k_y_from_x: non-zero where x is no abscissa of the curve
+	uint8_t *out1, *out2;    // n x 2*clen affine X || Y: A + B, A - B
+	uint8_t *st1, *st2;      // n each: ECAMD_OK / ECAMD_ERR / ECAMD_INF; k_recover_fin leaves ECAMD_STATUS_REDO for k_recover_redo
+	uint32_t n, clen;
+	int slot;
+};
+hipError_t ecamd_launch_recover_prep(int qnw, const EcamdRecoverPrepArgs &a, hipStream_t s);
+hipError_t ecamd_launch_recover_point(const EcamdRecoverPointArgs &a, hipStream_t s);
+hipError_t ecamd_launch_recover_fin(int nw, const EcamdRecoverFinArgs &a, hipStream_t s);
+hipError_t ecamd_launch_recover_redo(int nw, const EcamdRecoverFinArgs &a, hipStream_t s);
+
 // nw: 32-bit words per field element; must be one of ecamd_supported_nw()
 int ecamd_nw_supported(int nw);
 hipError_t ecamd_upload_curve(int nw, int slot, const void *curvek, size_t bytes);

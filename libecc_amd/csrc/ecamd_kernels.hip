@@ -2853,3 +2853,6 @@ hipError_t ecamd_launch_prj_export(const EcamdPrjOutArgs &a, hipStream_t s)
 	hipLaunchKernelGGL(k_prj_export, dim3((a.n + 255) / 256), dim3(256), 0, s, a);
 	return hipGetLastError();
 }
+
+// ECDSA public-key recovery: k_recover_prep / _point / _fin / _redo and their launchers
+#include "ecamd_recover_kernels.h"

@@ -3,9 +3,10 @@
 BASELINE.json configs[3] (secp256r1 ECDSA batch verification) and configs[4] (Ed25519 verification,
 X25519).  Same launch contract and JSON line as bench.py (one process per GPU under
 torch.distributed.run, weak scaling, contiguous shards, one RCCL all-gather of the per-rank result
-bytes per step); not the driver's headline bench.
+bytes per step); not the driver's headline bench.  --workload ecdsa_recover is the exception: one GPU, recovery beside the
+verification of the same signatures in alternating windows (recover_row).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -26,9 +27,101 @@ import libecc_amd  # noqa: E402
 SEED = 0x5EC9256
 
 
+def recover_row(a, ctx, dev, stream, rng, B):
+    """ECDSA public-key recovery (ec_ecdsa_recover_batch_dev), inputs resident in HBM, beside the ECDSA verification of the SAME
+    signatures in the same run: the two are timed in alternating windows of a.steps calls, so what the pair prints is a ratio taken
+    under one clock and one neighbourhood.  Gates: every recovered pair holds the signer's key (prime-order curves), every recovered
+    signer key verifies, 256 random items identical to the unmodified reference where it is built.  One GPU only (no all-gather: the
+    row is a ratio on one device); run it with --steps 10 or more, so that a window is a quarter of a second of work."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload ecdsa_recover measures one GPU: run it with --gpus 1, outside torch.distributed.run")
+    import oracles as O
+    curve = a.curve
+    cv = ctx.curve(curve)
+    q = O.CURVES[curve]["q"]
+    ql, cl = O.qlen(curve), O.clen(curve)
+    hl = 32
+    raw = rng.integers(0, 256, size=(2, B, ql + 8), dtype=np.uint8)
+
+    def scal(rows):
+        return b"".join(((int.from_bytes(rows[i].tobytes(), "big") % (q - 1)) + 1).to_bytes(ql, "big") for i in range(B))
+
+    def t(b):
+        return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+    privs, nonces = scal(raw[0]), scal(raw[1])
+    dg = rng.integers(0, 256, size=hl * B, dtype=np.uint8).tobytes()
+    pubs, st = cv.scalar_mult(privs)
+    assert set(st) == {0}
+    sigs, st = cv.ecdsa_sign(privs, nonces, dg, hl)
+    assert set(st) == {0}
+    d_pub, d_sig, d_dg = t(pubs), t(sigs), t(dg)
+    d_res = torch.empty(B, dtype=torch.uint8, device=dev)
+    d_k1, d_k2 = (torch.empty(2 * cl * B, dtype=torch.uint8, device=dev) for _ in range(2))
+    d_s1, d_s2 = (torch.empty(B, dtype=torch.uint8, device=dev) for _ in range(2))
+
+    def verify():
+        cv.ecdsa_verify_dev(B, d_pub.data_ptr(), d_sig.data_ptr(), d_dg.data_ptr(), hl, d_res.data_ptr(), stream.cuda_stream)
+
+    def recover():
+        cv.ecdsa_recover_dev(B, d_sig.data_ptr(), d_dg.data_ptr(), hl, d_k1.data_ptr(), d_k2.data_ptr(), d_s1.data_ptr(), d_s2.data_ptr(),
+                             stream.cuda_stream)
+    # ---- gates ----
+    verify()
+    recover()
+    torch.cuda.synchronize()
+    if bytes(d_res.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: an honest signature was rejected")
+    k1, k2 = d_k1.cpu().numpy().reshape(B, 2 * cl), d_k2.cpu().numpy().reshape(B, 2 * cl)
+    s1, s2 = d_s1.cpu().numpy(), d_s2.cpu().numpy()
+    pk = np.frombuffer(pubs, dtype=np.uint8).reshape(B, 2 * cl)
+    first = (k1 == pk).all(axis=1)
+    if O.CURVES[curve]["order"] == q and not ((first | (k2 == pk).all(axis=1)).all() and (s1 == 0).all() and (s2 == 0).all()):
+        raise SystemExit("PARITY FAILURE: a signer's key is not among the two recovered keys")
+    gate = "the signer's key among the two recovered keys for all 2^%d items (the first one %.1f %% of the time)" % (a.batch_log2, 100.0 * first.mean())
+    if O.have_ref() and a.ref_items > 0:
+        import recover_ref as RR
+        idx = [int(i) for i in np.sort(np.random.default_rng(2).choice(B, size=min(B, 256), replace=False))]
+        exp = RR.ref_recover_threaded(curve, b"".join(sigs[2 * ql * i:2 * ql * (i + 1)] for i in idx), b"".join(dg[hl * i:hl * (i + 1)] for i in idx), hl)
+        got = (k1[idx].tobytes(), k2[idx].tobytes(), s1[idx].tobytes(), s2[idx].tobytes())
+        if got != exp:
+            raise SystemExit("PARITY FAILURE: GPU output differs from the unmodified reference binary")
+        gate += "; 256 random items identical to the unmodified reference's ecdsa_public_key_from_sig"
+    # ---- timing: alternating windows ----
+    for _ in range(a.warmup):
+        verify()
+        recover()
+    torch.cuda.synchronize()
+    tv, tr = [], []
+    for _ in range(3):
+        for fn, acc in ((verify, tv), (recover, tr)):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            acc.append((time.perf_counter() - t0) / a.steps)
+    # ---- per-kernel time of ONE recovery call from the library's own events around its scalar-multiplication pipelines ----
+    kern = None
+    try:
+        ctx.enable_kernel_timing(True)
+        recover()
+        torch.cuda.synchronize()
+        kern = ctx.kernel_times()
+        ctx.enable_kernel_timing(False)
+    except Exception as e:
+        kern = {"error": str(e)}
+    mv, mr = float(np.median(tv)), float(np.median(tr))
+    print(json.dumps({"metric": "ECDSA public keys recovered/sec (%s, batch=2^%d, device-resident)" % (curve.lower(), a.batch_log2),
+                      "value": B / mr, "unit": "recoveries/s", "recover_ms": [1e3 * x for x in tr],
+                      "ecdsa_verify_same_run": {"value": B / mv, "unit": "verifications/s", "verify_ms": [1e3 * x for x in tv]},
+                      "recover_over_verify": mv / mr, "gate": gate, "last_smul_kernel_ms": kern,
+                      "config": {"workload": "ecdsa_recover", "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+    cv.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -73,6 +166,8 @@ def main():
 
     t_setup = time.time()
     ref_subset = work = gate_ref = None
+    if a.workload == "ecdsa_recover":
+        return recover_row(a, ctx, dev, stream, rng, B)
     if a.workload == "ecdsa_verify":
         curve = a.curve
         cv = ctx.curve(curve)
