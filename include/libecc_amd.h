@@ -263,6 +263,38 @@ int ec_eddsa_verify_ph_prj_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint3
 int ec_ecdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const uint8_t *privs,
 			const uint8_t *nonces, const uint8_t *digests, uint32_t digest_len, uint8_t *sigs,
 			uint8_t *status);
+/*
+ * ECGDSA, ECRDSA and SM2: the three other schemes of libecc's table whose verification has ECDSA's shape -- range checks, two
+ * public multipliers from a little algebra mod q, W' = [u]G + [v]Y, a comparison of W'.x mod q -- and whose signing is one
+ * fixed-base [k]G plus algebra with the private key.  alg: libecc's ec_alg_type numbers (lib_ecc_types.h); any other value is
+ * a call-level error (-1).  Per item, verification is
+ *   ec_pub_key_import_from_aff_buf(pub, params, pubkeys + i*2*clen, 2*clen, alg)     sig/ec_key.c:181
+ *   ec_verify(sig, 2*qlen, pub, m, mlen, alg, hash, adata, adata_len)                sig/sig_algs.c:655
+ * with result[i] = 0 / 1 for its 0 / -1, for every input: a key that does not import (coordinate >= p, off the curve, outside
+ * the subgroup on a cofactor curve), r or s outside [1, q - 1], SM2's r + s = q, W' at infinity.  Signing is the tail of
+ * _ec_sign (_ecgdsa_sign_finalize sig/ecgdsa.c:181-376, _ecrdsa_sign_finalize sig/ecrdsa.c:196-378, _sm2_sign_finalize
+ * sig/sm2.c:310-483) with the nonce k supplied by the caller, as for ec_ecdsa_sign_batch; status[i] = 1 with zero signature
+ * bytes where ec_key_pair_import_from_priv_key_buf refuses the private key (x >= q; ECGDSA x = 0, its public key being
+ * [1/x]G; SM2 x >= q - 1, where 1 + x has no inverse) or _ec_sign fails on it (SM2 x = 0: a key at infinity has no Z), k is not in [1, q - 1], or the reference restarts (r = 0, s = 0).
+ * Private keys are x itself (ECGDSA's public key is [1/x]G, the other two [x]G).
+ * `digests` are the bytes the scheme's finalize turns into an integer, digest_len (1 .. 128) each; hashing stays with the caller:
+ *   ECGDSA, ECRDSA  H(m)
+ *   SM2             H(Z || m),  Z = H(ENTL || ID || a || b || xG || yG || xY || yY)                 sig/sm2.c:121-205
+ *                   (ENTL: the bit length of the signer's id ID on two bytes, big-endian; the curve's a and b, the generator
+ *                   and the signer's key Y as big-endian field elements of clen bytes; libecc passes ID as `adata`)
+ * and are read by the scheme's rule: ECGDSA big-endian, the leftmost |q| bits when longer (ECDSA's rule); ECRDSA byte-reversed
+ * (libecc's default build, without USE_ISO14888_3_ECRDSA), the whole digest mod q, 0 becoming 1; SM2 big-endian, the whole
+ * digest mod q.  libecc accepts any of its hashes with the three schemes, and so do these calls.
+ * Layouts, chunking by ecamd_ctx_set_max_chunk, n = 0 and argument errors as ec_ecdsa_verify_batch / ec_ecdsa_sign_batch.
+ * Verification multiplies by public values only, whatever ecamd_ctx_set_secret_scalars says; signing's [k]G honours it.
+ */
+#define ECAMD_SIG_ECGDSA 6
+#define ECAMD_SIG_ECRDSA 7
+#define ECAMD_SIG_SM2 8
+int ec_sig_verify_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const uint8_t *pubkeys_aff,
+			const uint8_t *sigs, const uint8_t *digests, uint32_t digest_len, uint8_t *result);
+int ec_sig_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const uint8_t *privs,
+		      const uint8_t *nonces, const uint8_t *digests, uint32_t digest_len, uint8_t *sigs, uint8_t *status);
 /* nn_get_random_mod (nn/nn_rand.c:92-150) given its random bytes.  The reference draws 2 * qlen bytes with get_random straight into the
  * limb array of an nn (they read as a little-endian integer on the little-endian hosts libecc and this library run on), reduces modulo
  * q - 1 and adds one.  raw: n x 2*qlen bytes from the caller's own randomness source; out: n x qlen big-endian, each in [1, q - 1].  The
@@ -514,6 +546,12 @@ int ec_ecdsa_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n
 			    void *d_status, void *hip_stream);
 int ec_ecccdh_derive_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const void *d_privs,
 			       const void *d_peers_aff, void *d_secrets, void *d_status, void *hip_stream);
+/* ec_sig_verify_batch / ec_sig_sign_batch with device pointers: enqueue only. */
+int ec_sig_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const void *d_pubkeys_aff,
+			    const void *d_sigs, const void *d_digests, uint32_t digest_len, void *d_result, void *hip_stream);
+int ec_sig_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const void *d_privs,
+			  const void *d_nonces, const void *d_digests, uint32_t digest_len, void *d_sigs, void *d_status,
+			  void *hip_stream);
 
 /*
  * ---- several GPUs from C ----

@@ -29,7 +29,11 @@ EXPORTED_SYMBOLS = [
     "ecamd_multi_set_secret_scalars", "ecamd_multi_wipe_scratch", "ecamd_ctx_wipe_scratch", "ecamd_ctx_stream", "ecamd_host_alloc", "ecamd_host_free", "ecamd_ctx_dominant_kernel_ms", "ecamd_ctx_set_msm_seed", "ecamd_ctx_discard_msm_seed", "ecamd_multi_set_msm_seed", "ec_eddsa_verify_ph_prj_batch", "ecamd_multi_eddsa_verify_ph_prj_batch", "ec_nn_random_mod_batch", "ec_ecdsa_sign_msg_batch", "ec_key_pair_gen_raw_batch", "ecamd_multi_ecdsa_sign_msg_batch", "ecamd_multi_key_pair_gen_raw_batch", "ec_eddsa_verify_msg_prj_batch", "ecamd_multi_eddsa_verify_msg_prj_batch", "ecamd_ctx_set_host_ready_hook", "ecamd_multi_set_host_ready_hook", "ecamd_multi_prj_pt_add_batch",
     "ec_schnorr_verify_all_batch", "ec_schnorr_verify_all_batch_dev", "ec_schnorr_verify_msg_all_batch", "ec_eddsa_verify_msg_prj_all_batch", "ecamd_multi_eddsa_verify_msg_prj_all_batch", "ecamd_multi_schnorr_verify_msg_all_batch", "ec_schnorr_verify_all_available", "ecamd_multi_schnorr_verify_all_batch", "ecamd_debug_schnorr_msm", "ecamd_debug_schnorr_msm_words",
     "ec_ecdsa_recover_batch", "ec_ecdsa_recover_batch_dev",
+    "ec_sig_verify_batch", "ec_sig_verify_batch_dev", "ec_sig_sign_batch", "ec_sig_sign_batch_dev",
 ]
+
+# libecc's ec_alg_type numbers of the schemes ec_sig_verify_batch / ec_sig_sign_batch serve (ECAMD_SIG_* in include/libecc_amd.h)
+SIG_ECGDSA, SIG_ECRDSA, SIG_SM2 = 6, 7, 8
 
 
 class EcamdError(RuntimeError):
@@ -105,6 +109,10 @@ def load_library():
         L.ec_structured_sig_import_batch.argtypes = [vp, u32, u8p, u32, C.c_int, C.c_int, u8p, u8p]
         L.ec_structured_key_pair_import_batch.argtypes = [vp, vp, u32, u8p, u32, C.c_int, u8p, u8p, u8p]
         L.ec_ecdsa_verify_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp]
+        L.ec_sig_verify_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p]
+        L.ec_sig_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u8p]
+        L.ec_sig_verify_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, u32, vp, vp]
+        L.ec_sig_sign_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, u32, vp, vp, vp]
         L.ec_ecdsa_recover_batch.argtypes = [vp, vp, u32, u8p, u8p, u32, u8p, u8p, u8p, u8p]
         L.ec_ecdsa_recover_batch_dev.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp]
         L.ec_eddsa_verify_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp]
@@ -361,6 +369,22 @@ class Curve:
              "ec_ecdsa_sign_batch")
         return sigs.raw[:2 * self.qlen * n], st.raw[:n]
 
+    def sig_verify(self, alg, pubs, sigs, digests, hlen):
+        """ECGDSA / ECRDSA / SM2 verification (alg: SIG_ECGDSA, SIG_ECRDSA, SIG_SM2): 0 accept / 1 reject per item.  digests are the
+        bytes the scheme turns into e: H(m), and H(Z || m) for SM2"""
+        n = len(pubs) // (2 * self.clen)
+        res = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_sig_verify_batch(self.ctx.h, self.h, alg, n, pubs, sigs, digests, hlen, res), "ec_sig_verify_batch")
+        return res.raw[:n]
+
+    def sig_sign(self, alg, privs, nonces, digests, hlen):
+        """ECGDSA / ECRDSA / SM2 signatures (r || s) with caller-supplied nonces, and a status byte per item"""
+        n = len(privs) // self.qlen
+        sigs = C.create_string_buffer(max(1, 2 * self.qlen * n))
+        st = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_sig_sign_batch(self.ctx.h, self.h, alg, n, privs, nonces, digests, hlen, sigs, st), "ec_sig_sign_batch")
+        return sigs.raw[:2 * self.qlen * n], st.raw[:n]
+
     def random_mod(self, raw):
         """nn_get_random_mod given its 2 * qlen random bytes per item: LE(raw) mod (q - 1) + 1, big-endian"""
         n = len(raw) // (2 * self.qlen)
@@ -514,6 +538,14 @@ class Curve:
     def ecdsa_verify_dev(self, n, d_pubs, d_sigs, d_digests, hlen, d_result, stream=None):
         _chk(self.L, self.L.ec_ecdsa_verify_batch_dev(self.ctx.h, self.h, n, d_pubs, d_sigs, d_digests, hlen, d_result,
                                                        stream), "ec_ecdsa_verify_batch_dev")
+
+    def sig_verify_dev(self, alg, n, d_pubs, d_sigs, d_digests, hlen, d_result, stream=None):
+        _chk(self.L, self.L.ec_sig_verify_batch_dev(self.ctx.h, self.h, alg, n, d_pubs, d_sigs, d_digests, hlen, d_result, stream),
+             "ec_sig_verify_batch_dev")
+
+    def sig_sign_dev(self, alg, n, d_privs, d_nonces, d_digests, hlen, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_sig_sign_batch_dev(self.ctx.h, self.h, alg, n, d_privs, d_nonces, d_digests, hlen, d_sigs, d_status,
+                                                   stream), "ec_sig_sign_batch_dev")
 
     def ecdsa_recover_dev(self, n, d_sigs, d_digests, hlen, d_pub1, d_pub2, d_st1, d_st2, stream=None):
         _chk(self.L, self.L.ec_ecdsa_recover_batch_dev(self.ctx.h, self.h, n, d_sigs, d_digests, hlen, d_pub1, d_pub2, d_st1,

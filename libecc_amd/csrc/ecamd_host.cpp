@@ -909,7 +909,9 @@ static int smul_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, co
 			   const uint8_t *d_points, uint8_t *d_out, uint8_t *d_status, hipStream_t s,
 			   uint32_t sstride = 0xffffffffu, bool redo_only = false, const uint8_t *d_scalars2 = nullptr);
 static int prep_scratch_ok(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n);
-static hipError_t launch_ecdsa_prep(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEcdsaPrepArgs &P, hipStream_t s);
+#define SIG_ECDSA 1   /* libecc's ec_alg_type number of ECDSA: the `alg` of the verification paths when they serve ECDSA */
+static hipError_t launch_ecdsa_prep(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEcdsaPrepArgs &P, hipStream_t s, int alg = SIG_ECDSA,
+				    uint8_t *target = nullptr);
 
 // w-bit digits of a (nl of them, the last one takes whatever is left): 29 bits on every radix-2^29 unit but the Goldilocks one
 // (flavour 5), which runs on 28-bit limbs so that 2^224 falls on a limb boundary (ecamd_u29g.h)
@@ -2114,6 +2116,21 @@ extern "C" int ec_fp_op_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int op, uin
 // ------------------------------------------------------------------------------------------
 // batched ECDSA verification (digest supplied by the caller)
 // ------------------------------------------------------------------------------------------
+// `alg` (SIG_ECDSA, or ECAMD_SIG_ECGDSA / ECRDSA / SM2) selects the front end of the three verification paths below; for the
+// three other schemes the back ends compare W'.x with the front end's comparison target (stage 29, in the layout of a signature
+// array) instead of the caller's signatures.  ECDSA: exactly the launches there were before `alg` existed.
+static const uint8_t *sig_target(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *d_sig, uint8_t **target)
+{
+	*target = nullptr;
+	if (alg == SIG_ECDSA) {
+		return d_sig;
+	}
+	if (ensure(&ctx->stage[29], &ctx->stage_bytes[29], (size_t)n * 2 * cv->qlen)) {
+		return nullptr;
+	}
+	*target = ctx->stage[29];
+	return ctx->stage[29];
+}
 // The reference's structure: two independent scalar multiplications and one addition per item.
 // All pointers are device pointers; intermediates live in stage[3..11].
 // d_pub == NULL: every public key is the point at infinity (libecc imports (0 : 1 : 0) as a key, and its verification
@@ -2122,13 +2139,13 @@ extern "C" int ec_fp_op_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int op, uin
 // kernel) and get a result -- the redo pass of the interleaved secp256r1 loop, entirely on the device.  Only enqueues.
 static int ecdsa_two_smul_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_pub,
 			      const uint8_t *d_sig, const uint8_t *d_dig, uint32_t hlen, uint8_t *d_res, hipStream_t s,
-			      const uint8_t *d_only = nullptr)
+			      const uint8_t *d_only = nullptr, int alg = SIG_ECDSA)
 {
 	if (n > ctx->max_chunk) {  // bound the scratch: pieces of max_chunk items, in order on the stream
 		for (uint32_t off = 0; off < n; off += ctx->max_chunk) {
 			const uint32_t m = (n - off) < ctx->max_chunk ? (n - off) : ctx->max_chunk;
 			if (ecdsa_two_smul_dev(ctx, cv, m, d_pub ? d_pub + (size_t)off * 2 * cv->clen : nullptr, d_sig + (size_t)off * 2 * cv->qlen,
-					       d_dig + (size_t)off * hlen, hlen, d_res + off, s, d_only ? d_only + off : nullptr)) {
+					       d_dig + (size_t)off * hlen, hlen, d_res + off, s, d_only ? d_only + off : nullptr, alg)) {
 				return -1;
 			}
 		}
@@ -2156,10 +2173,12 @@ static int ecdsa_two_smul_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n,
 	P.qbits = (uint32_t)cv->qbits;
 	P.qslot = cv->qslot;
 	P.only = d_only;
-	if (prep_scratch_ok(ctx, cv, n)) {
+	uint8_t *target;
+	const uint8_t *cmp_sig = sig_target(ctx, cv, alg, n, d_sig, &target);
+	if (!cmp_sig || prep_scratch_ok(ctx, cv, n)) {
 		return -1;
 	}
-	HIPCHK(launch_ecdsa_prep(ctx, cv, P, s));
+	HIPCHK(launch_ecdsa_prep(ctx, cv, P, s, alg, target));
 	const bool redo = d_only != nullptr;
 	if (redo) {
 		// the marks select the lanes of the complete-formula kernel (A.only_redo); the other items keep what they have
@@ -2196,7 +2215,7 @@ static int ecdsa_two_smul_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n,
 	Fn.stA = S[7];
 	Fn.B = S[6];
 	Fn.stB = S[8];
-	Fn.sigs = d_sig;
+	Fn.sigs = cmp_sig;
 	Fn.flags = S[9];
 	Fn.result = d_res;
 	Fn.n = n;
@@ -2235,8 +2254,16 @@ static int prep_scratch_ok(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n)
 	}
 	return ensure(&ctx->prep_scratch, &ctx->prep_scratch_bytes, (size_t)n * (size_t)ecamd_g29_nl(big_bitlen(cv->q), 0) * 4);
 }
-static hipError_t launch_ecdsa_prep(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEcdsaPrepArgs &P, hipStream_t s)
+// alg != SIG_ECDSA: the front end of ECGDSA / ECRDSA / SM2 (k_sig_prep, saturated words), which also writes the comparison target
+static hipError_t launch_ecdsa_prep(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEcdsaPrepArgs &P, hipStream_t s, int alg, uint8_t *target)
 {
+	if (alg != SIG_ECDSA) {
+		EcamdSigPrepArgs SP;
+		SP.p = P;
+		SP.target = target;
+		SP.alg = alg;
+		return ecamd_launch_sig_prep(cv->qnw, SP, s);
+	}
 	if (prep_g29(cv) && ctx->prep_scratch) {
 		const int qbits = big_bitlen(cv->q);
 		static const int kp_env = getenv("ECAMD_PREP_KP") ? atoi(getenv("ECAMD_PREP_KP")) : 0;   // A/B hook
@@ -2249,10 +2276,11 @@ static hipError_t launch_ecdsa_prep(ecamd_ctx *ctx, const ecamd_curve *cv, const
 // k_ecdsa_prep of a chunk on the side stream: it starts when everything enqueued on s so far is done (the stage buffers it
 // writes are read by the previous chunk's loop) and the caller makes the consumer of u1 / u2 wait for side_done.
 // Returns the event to wait for, or nullptr when the kernel was enqueued on s itself.
-static hipEvent_t ecdsa_prep_beside(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEcdsaPrepArgs &P, hipStream_t s, hipError_t *err)
+static hipEvent_t ecdsa_prep_beside(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEcdsaPrepArgs &P, hipStream_t s, hipError_t *err,
+				    int alg = SIG_ECDSA, uint8_t *target = nullptr)
 {
 	if (!ctx->side_ok) {
-		*err = launch_ecdsa_prep(ctx, cv, P, s);
+		*err = launch_ecdsa_prep(ctx, cv, P, s, alg, target);
 		return nullptr;
 	}
 	*err = hipEventRecord(ctx->side_fork, s);
@@ -2260,7 +2288,7 @@ static hipEvent_t ecdsa_prep_beside(ecamd_ctx *ctx, const ecamd_curve *cv, const
 		*err = hipStreamWaitEvent(ctx->side_stream, ctx->side_fork, 0);
 	}
 	if (*err == hipSuccess) {
-		*err = launch_ecdsa_prep(ctx, cv, P, ctx->side_stream);
+		*err = launch_ecdsa_prep(ctx, cv, P, ctx->side_stream, alg, target);
 	}
 	if (*err == hipSuccess) {
 		*err = hipEventRecord(ctx->side_done, ctx->side_stream);
@@ -2295,11 +2323,15 @@ static bool fused_verify_ok(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n)
 // two-multiplication path (x mod q == r over the candidates r + j q < p).  Items whose loop met an exceptional pair come back
 // marked and are verified again by ecdsa_two_smul_dev (complete formulas), entirely on the device.
 static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_pub, const uint8_t *d_sig,
-			     const uint8_t *d_dig, uint32_t hlen, uint8_t *d_res, hipStream_t s)
+			     const uint8_t *d_dig, uint32_t hlen, uint8_t *d_res, hipStream_t s, int alg = SIG_ECDSA)
 {
 	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen;
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
 	PublicScalars pub_scope(ctx);
+	uint8_t *target;
+	if (!sig_target(ctx, cv, alg, chunk, d_sig, &target)) {
+		return -1;
+	}
 	// stage: 3 u1, 4 u2, 5 W' affine, 7 its status, 8 "the other point is infinity", 9 flags
 	const size_t need[10] = {0, 0, 0, chunk * ql, chunk * ql, chunk * plen, 0, chunk, chunk, chunk};
 	for (int i = 3; i < 10; i++) {
@@ -2335,7 +2367,7 @@ static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 		if (prep_scratch_ok(ctx, cv, m)) {
 			return -1;
 		}
-		HIPCHK(launch_ecdsa_prep(ctx, cv, P, s));
+		HIPCHK(launch_ecdsa_prep(ctx, cv, P, s, alg, target));
 		if (smul_dev_locked(ctx, cv, m, S[4], (uint32_t)ql, d_pub + (size_t)off * plen, S[5], S[7], s, 0xffffffffu, false, S[3])) {
 			return -1;
 		}
@@ -2345,7 +2377,7 @@ static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 		Fn.stA = S[7];
 		Fn.B = S[5];            // never read: its status says infinity
 		Fn.stB = S[8];
-		Fn.sigs = d_sig + (size_t)off * 2 * ql;
+		Fn.sigs = target ? target : d_sig + (size_t)off * 2 * ql;
 		Fn.flags = S[9];
 		Fn.result = d_res + off;
 		Fn.n = m;
@@ -2360,16 +2392,16 @@ static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 		HIPCHK(ecamd_launch_ecdsa_fin(cv->nw, Fn, s));
 	}
 	// the redo pass: only the marked items (with nothing marked: near-empty launches)
-	return ecdsa_two_smul_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s, d_res);
+	return ecdsa_two_smul_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s, d_res, alg);
 }
 
 static int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_pub,
 				   const uint8_t *d_sig, const uint8_t *d_dig, uint32_t hlen, uint8_t *d_res, hipStream_t s,
-				   const std::function<int()> *between = nullptr)
+				   const std::function<int()> *between = nullptr, int alg = SIG_ECDSA)
 {
 	if (!cv->is_p256 || !cv->d_gtab) {
-		if (fused_verify_ok(ctx, cv, n) ? ecdsa_fused_g_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s)
-						: ecdsa_two_smul_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s)) {
+		if (fused_verify_ok(ctx, cv, n) ? ecdsa_fused_g_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s, alg)
+						: ecdsa_two_smul_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s, nullptr, alg)) {
 			return -1;
 		}
 		if (between && (*between)()) {
@@ -2388,6 +2420,10 @@ static int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 		if (rc) {
 			return -1;
 		}
+	}
+	uint8_t *target;
+	if (!sig_target(ctx, cv, alg, chunk, d_sig, &target)) {
+		return -1;
 	}
 	// stage: 3 u1, 4 u2, 5 flags, 7 zeroed points of rejected keys + key status
 	const size_t need[8] = {0, 0, 0, (size_t)chunk * 32, (size_t)chunk * 32, chunk, 0, (size_t)chunk * 64 + chunk};
@@ -2415,7 +2451,7 @@ static int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 		if (prep_scratch_ok(ctx, cv, m)) {
 			return -1;
 		}
-		const hipEvent_t prep_done = ecdsa_prep_beside(ctx, cv, P, s, &perr);
+		const hipEvent_t prep_done = ecdsa_prep_beside(ctx, cv, P, s, &perr, alg, target);
 		HIPCHK(perr);
 		EcamdSmulArgs K;
 		memset(&K, 0, sizeof(K));
@@ -2429,14 +2465,14 @@ static int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 		K.clen = 32;
 		K.slot = cv->slot;
 		hipEvent_t *dom = (ctx->timing && off == 0) ? ctx->ev_dom : nullptr;
-		HIPCHK(ecamd_launch_verify_p256(K, S[3], S[4], d_sig + (size_t)off * 64, S[5],
+		HIPCHK(ecamd_launch_verify_p256(K, S[3], S[4], target ? target : d_sig + (size_t)off * 64, S[5],
 						cv->d_comb ? cv->d_comb : cv->d_gtab, cv->d_comb ? 1 : 0, cv->qdig, d_res + off, s, dom, prep_done));
 		ctx->ev_dom_valid = ctx->ev_dom_valid || (dom != nullptr);
 	}
 	// exceptional pairs inside the interleaved loop (never for honest signatures) come back as ECAMD_STATUS_REDO: those
 	// items are verified again the reference's way -- two complete-formula multiplications -- by kernels whose other
 	// lanes exit at once (with nothing marked: five near-empty launches)
-	if (ecdsa_two_smul_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s, d_res)) {
+	if (ecdsa_two_smul_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s, d_res, alg)) {
 		return -1;
 	}
 	if (between && (*between)()) {
@@ -2768,6 +2804,143 @@ extern "C" int ec_ecdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
 					       hipStream_t s, const std::function<int()> &) {
 		return ecdsa_sign_dev_locked(ctx, cv, m, ip[0], ip[1], ip[2], hlen, op[3], op[4], s);
+	});
+}
+
+// ------------------------------------------------------------------------------------------
+// batched ECGDSA / ECRDSA / SM2 (include/libecc_amd.h: ec_sig_*): the ECDSA verification paths with the scheme's front end
+// (k_sig_prep) and the ECDSA signing path with the scheme's back end (k_sig_sign)
+// ------------------------------------------------------------------------------------------
+static int sig_alg_ok(const char *fn, int alg)
+{
+	if (alg != ECAMD_SIG_ECGDSA && alg != ECAMD_SIG_ECRDSA && alg != ECAMD_SIG_SM2) {
+		return fail(std::string(fn) + ": alg must be ECAMD_SIG_ECGDSA, ECAMD_SIG_ECRDSA or ECAMD_SIG_SM2");
+	}
+	return 0;
+}
+
+extern "C" int ec_sig_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const void *d_pubkeys, const void *d_sigs,
+				       const void *d_digests, uint32_t hlen, void *d_result, void *hip_stream)
+{
+	if (sig_alg_ok("ec_sig_verify_batch_dev", alg) ||
+	    ecdsa_verify_args_ok("ec_sig_verify_batch_dev", ctx, cv, n, d_pubkeys, d_sigs, d_digests, d_result, hlen)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return ecdsa_verify_dev_locked(ctx, cv, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_digests, hlen,
+				       (uint8_t *)d_result, s, nullptr, alg);
+}
+
+extern "C" int ec_sig_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *pubkeys, const uint8_t *sigs,
+				   const uint8_t *digests, uint32_t hlen, uint8_t *result)
+{
+	if (sig_alg_ok("ec_sig_verify_batch", alg) || ecdsa_verify_args_ok("ec_sig_verify_batch", ctx, cv, n, pubkeys, sigs, digests, result, hlen)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t plen = (size_t)2 * cv->clen, slen2 = (size_t)2 * cv->qlen;
+	const std::vector<HostArr> arrs = {{pubkeys, nullptr, plen}, {sigs, nullptr, slen2}, {digests, nullptr, hlen}, {nullptr, result, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+					       hipStream_t s, const std::function<int()> &between) {
+		return ecdsa_verify_dev_locked(ctx, cv, m, ip[0], ip[1], ip[2], hlen, op[3], s, &between, alg);
+	});
+}
+
+// Device core of signing: every pointer a device pointer; [k]G and its status live in stage[3], stage[4] as for ECDSA.
+static int sig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
+			       const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
+{
+	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen;
+	if (n > ctx->max_chunk) {  // bound the scratch: pieces of max_chunk items, in order on the stream
+		for (uint32_t off = 0; off < n; off += ctx->max_chunk) {
+			const uint32_t m = (n - off) < ctx->max_chunk ? (n - off) : ctx->max_chunk;
+			if (sig_sign_dev_locked(ctx, cv, alg, m, d_privs + off * ql, d_nonces + off * ql, d_digests + (size_t)off * hlen, hlen,
+						d_sigs + off * 2 * ql, d_status + off, s)) {
+				return -1;
+			}
+		}
+		return 0;
+	}
+	if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], n * plen) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], n)) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	if (smul_dev_locked(ctx, cv, n, d_nonces, (uint32_t)ql, nullptr, S[3], S[4], s)) {  // [k]G, secret-scalar mode as the context says
+		return -1;
+	}
+	EcamdSigSignArgs A;
+	A.a.privs = d_privs;
+	A.a.nonces = d_nonces;
+	A.a.digests = d_digests;
+	A.a.kG = S[3];
+	A.a.stkG = S[4];
+	A.a.sigs = d_sigs;
+	A.a.status = d_status;
+	A.a.n = n;
+	A.a.clen = (uint32_t)cv->clen;
+	A.a.qlen = (uint32_t)cv->qlen;
+	A.a.hlen = hlen;
+	A.a.qbits = (uint32_t)cv->qbits;
+	{
+		uint32_t j = 0;
+		Big t = cv->q;
+		while (big_cmp(t, cv->p) < 0 && j < 64) {
+			t = big_add(t, cv->q);
+			j++;
+		}
+		A.a.jmax = j;
+	}
+	A.a.qslot = cv->qslot;
+	A.alg = alg;
+	HIPCHK(ecamd_launch_sig_sign(cv->qnw, A, s));
+	return 0;
+}
+
+extern "C" int ec_sig_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const void *d_privs, const void *d_nonces,
+				     const void *d_digests, uint32_t hlen, void *d_sigs, void *d_status, void *hip_stream)
+{
+	if (sig_alg_ok("ec_sig_sign_batch_dev", alg) ||
+	    ecdsa_sign_args_ok("ec_sig_sign_batch_dev", ctx, cv, n, d_privs, d_nonces, d_digests, d_sigs, d_status, hlen)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return sig_sign_dev_locked(ctx, cv, alg, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_digests, hlen,
+				   (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+}
+
+extern "C" int ec_sig_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *privs, const uint8_t *nonces,
+				 const uint8_t *digests, uint32_t hlen, uint8_t *sigs, uint8_t *status)
+{
+	if (sig_alg_ok("ec_sig_sign_batch", alg) || ecdsa_sign_args_ok("ec_sig_sign_batch", ctx, cv, n, privs, nonces, digests, sigs, status, hlen)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {digests, nullptr, hlen},
+					   {nullptr, sigs, 2 * ql}, {nullptr, status, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+					       hipStream_t s, const std::function<int()> &) {
+		return sig_sign_dev_locked(ctx, cv, alg, m, ip[0], ip[1], ip[2], hlen, op[3], op[4], s);
 	});
 }
 

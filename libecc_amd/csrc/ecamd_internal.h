@@ -101,6 +101,21 @@ hipError_t ecamd_launch_ecdsa_sign(int nw, const EcamdEcdsaSignArgs &a, hipStrea
 hipError_t ecamd_launch_ecdsa_prep(int nw, const EcamdEcdsaPrepArgs &a, hipStream_t s);
 hipError_t ecamd_launch_ecdsa_fin(int nw, const EcamdEcdsaFinArgs &a, hipStream_t s);
 
+// ---- ECGDSA / ECRDSA / SM2 (sig/ecgdsa.c, sig/ecrdsa.c, sig/sm2.c of the reference), ecamd_sigfam_kernels.h ----
+// The verification front end fills what k_ecdsa_prep fills (p.u1: the multiplier of G, p.u2: of Y, p.flags) and the comparison
+// target; the ECDSA back ends then run unchanged with `target` in the place of the signatures.
+struct EcamdSigPrepArgs {
+	EcamdEcdsaPrepArgs p;
+	uint8_t *target;         // n x 2*qlen: item i's r* big-endian in its first qlen bytes (where a signature has r); the rest is not written
+	int alg;                 // ECAMD_SIG_ECGDSA / ECRDSA / SM2
+};
+struct EcamdSigSignArgs {
+	EcamdEcdsaSignArgs a;
+	int alg;
+};
+hipError_t ecamd_launch_sig_prep(int nw, const EcamdSigPrepArgs &a, hipStream_t s);
+hipError_t ecamd_launch_sig_sign(int nw, const EcamdSigSignArgs &a, hipStream_t s);
+
 // ---- ECDSA public-key recovery (sig/ecdsa_common.c:867-1049 of the reference), ecamd_recover_kernels.h ----
 struct EcamdRecoverPrepArgs {
 	const uint8_t *sigs;     // n x 2*qlen, r || s big-endian

@@ -2856,3 +2856,4 @@ hipError_t ecamd_launch_prj_export(const EcamdPrjOutArgs &a, hipStream_t s)
 
 // ECDSA public-key recovery: k_recover_prep / _point / _fin / _redo and their launchers
 #include "ecamd_recover_kernels.h"
+#include "ecamd_sigfam_kernels.h"

@@ -6,7 +6,7 @@ torch.distributed.run, weak scaling, contiguous shards, one RCCL all-gather of t
 bytes per step); not the driver's headline bench.  --workload ecdsa_recover is the exception: one GPU, recovery beside the
 verification of the same signatures in alternating windows (recover_row).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -119,9 +119,95 @@ def recover_row(a, ctx, dev, stream, rng, B):
     ctx.close()
 
 
+def sig_family_row(a, ctx, dev, stream, rng, B):
+    """ECGDSA / ECRDSA / SM2 (ec_sig_verify_batch_dev or ec_sig_sign_batch_dev, --alg), inputs resident in HBM, beside the ECDSA
+    call of the same kind on the same curve in the same run, in alternating windows of a.steps calls as recover_row does.  Gates:
+    every signature the device made is accepted, and with the digests of the next item none is.  One GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload sig_verify / sig_sign measures one GPU: run it with --gpus 1, outside torch.distributed.run")
+    import oracles as O
+    alg = {"ecgdsa": 6, "ecrdsa": 7, "sm2": 8}[a.alg]
+    curve = a.curve
+    cv = ctx.curve(curve)
+    q = O.CURVES[curve]["q"]
+    ql, cl = O.qlen(curve), O.clen(curve)
+    hl = 32
+    raw = rng.integers(0, 256, size=(2, B, ql + 8), dtype=np.uint8)
+
+    def scal(rows, below):
+        return [(int.from_bytes(rows[i].tobytes(), "big") % below) + 1 for i in range(B)]
+
+    def t(b):
+        return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+    xs, ks = scal(raw[0], q - 2), scal(raw[1], q - 1)
+    privs, nonces = (b"".join(v.to_bytes(ql, "big") for v in vs) for vs in (xs, ks))
+    dg = rng.integers(0, 256, size=hl * B, dtype=np.uint8).tobytes()   # H(m); for SM2 they stand for H(Z || m)
+    pubs_e, st = cv.scalar_mult(privs)
+    assert set(st) == {0}
+    pubs = cv.scalar_mult(b"".join(pow(x, -1, q).to_bytes(ql, "big") for x in xs))[0] if alg == 6 else pubs_e
+    sigs_e, st = cv.ecdsa_sign(privs, nonces, dg, hl)
+    assert set(st) == {0}
+    sigs, st = cv.sig_sign(alg, privs, nonces, dg, hl)
+    assert set(st) == {0}
+    d_pub_e, d_sig_e, d_pub, d_sig, d_dg, d_x, d_k = (t(b) for b in (pubs_e, sigs_e, pubs, sigs, dg, privs, nonces))
+    d_res = torch.empty(B, dtype=torch.uint8, device=dev)
+    d_out, d_st = torch.empty(2 * ql * B, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    sign = a.workload == "sig_sign"
+
+    def ecdsa():
+        if sign:
+            cv.ecdsa_sign_dev(B, d_x.data_ptr(), d_k.data_ptr(), d_dg.data_ptr(), hl, d_out.data_ptr(), d_st.data_ptr(), stream.cuda_stream)
+        else:
+            cv.ecdsa_verify_dev(B, d_pub_e.data_ptr(), d_sig_e.data_ptr(), d_dg.data_ptr(), hl, d_res.data_ptr(), stream.cuda_stream)
+
+    def family():
+        if sign:
+            cv.sig_sign_dev(alg, B, d_x.data_ptr(), d_k.data_ptr(), d_dg.data_ptr(), hl, d_out.data_ptr(), d_st.data_ptr(), stream.cuda_stream)
+        else:
+            cv.sig_verify_dev(alg, B, d_pub.data_ptr(), d_sig.data_ptr(), d_dg.data_ptr(), hl, d_res.data_ptr(), stream.cuda_stream)
+    # ---- gates ----
+    cv.sig_verify_dev(alg, B, d_pub.data_ptr(), d_sig.data_ptr(), d_dg.data_ptr(), hl, d_res.data_ptr(), stream.cuda_stream)
+    torch.cuda.synchronize()
+    if bytes(d_res.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: a signature the device made was rejected")
+    d_rot = torch.roll(d_dg, hl)
+    cv.sig_verify_dev(alg, B, d_pub.data_ptr(), d_sig.data_ptr(), d_rot.data_ptr(), hl, d_res.data_ptr(), stream.cuda_stream)
+    torch.cuda.synchronize()
+    if bytes(d_res.cpu().numpy()) != b"\1" * B:
+        raise SystemExit("PARITY FAILURE: a signature was accepted for another item's digest")
+    family()
+    torch.cuda.synchronize()
+    if sign and (bytes(d_out.cpu().numpy()) != sigs or bytes(d_st.cpu().numpy()) != bytes(B)):
+        raise SystemExit("PARITY FAILURE: the device-pointer form signs differently")
+    gate = "all 2^%d device-made signatures accepted, none for its neighbour's digest" % a.batch_log2
+    # ---- timing: alternating windows ----
+    for _ in range(a.warmup):
+        ecdsa()
+        family()
+    torch.cuda.synchronize()
+    te, tf = [], []
+    for _ in range(3):
+        for fn, acc in ((ecdsa, te), (family, tf)):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            acc.append((time.perf_counter() - t0) / a.steps)
+    me, mf = float(np.median(te)), float(np.median(tf))
+    kind = "signatures" if sign else "verifications"
+    print(json.dumps({"metric": "%s %s/sec (%s, batch=2^%d, device-resident)" % (a.alg.upper(), kind, curve.lower(), a.batch_log2),
+                      "value": B / mf, "unit": kind + "/s", "family_ms": [1e3 * x for x in tf],
+                      "ecdsa_same_run": {"value": B / me, "unit": kind + "/s", "ecdsa_ms": [1e3 * x for x in te]},
+                      "family_over_ecdsa": me / mf, "gate": gate,
+                      "config": {"workload": a.workload, "alg": a.alg, "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+    cv.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2"], help="sig_verify / sig_sign: the scheme")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -168,6 +254,8 @@ def main():
     ref_subset = work = gate_ref = None
     if a.workload == "ecdsa_recover":
         return recover_row(a, ctx, dev, stream, rng, B)
+    if a.workload in ("sig_verify", "sig_sign"):
+        return sig_family_row(a, ctx, dev, stream, rng, B)
     if a.workload == "ecdsa_verify":
         curve = a.curve
         cv = ctx.curve(curve)
