@@ -295,6 +295,44 @@ int ec_sig_verify_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint3
 			const uint8_t *sigs, const uint8_t *digests, uint32_t digest_len, uint8_t *result);
 int ec_sig_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const uint8_t *privs,
 		      const uint8_t *nonces, const uint8_t *digests, uint32_t digest_len, uint8_t *sigs, uint8_t *status);
+/*
+ * ECSDSA, ECOSDSA and ECKCDSA: the schemes of libecc's table that hash AFTER the multiplication.  The verifier computes
+ * W' = [u]G + [v]Y, hashes its affine coordinates on the device and compares the digest with the signature's r byte for byte; the
+ * signer hashes W = [k]G and derives e = digest mod q.  alg: libecc's ec_alg_type numbers; hash_type: libecc's hash_alg_type
+ * numbers 1 .. 4 (SHA-224, SHA-256, SHA-384, SHA-512; hsize = 28, 32, 48, 64).  Any other alg or hash_type is a call-level
+ * error (-1, ecamd_last_error()).
+ *   sigs     n x (r_len + qlen), r then s big-endian.  r_len = hsize for ECSDSA and ECOSDSA (sig/ecsdsa.h:28),
+ *            min(hsize, qlen) for ECKCDSA (sig/eckcdsa.h:28).
+ *   inputs   ECSDSA, ECOSDSA: message slots in the format of ec_ecdsa_verify_msg_batch_fmt -- a little-endian u32 length, then
+ *            the hash input <blank> || m; stride a multiple of 4, at most 4096, 4 + length <= stride.  The caller leaves the
+ *            blank empty and counts it in the length: 2*clen octets for ECSDSA (W'x || W'y), clen for ECOSDSA (W'x)
+ *            (sig/ecsdsa_common.c:509-518).  The device writes the coordinates into a staged copy; the caller's array is not
+ *            modified.  A slot whose length is shorter than the blank or does not fit the stride is result / status 1.
+ *            ECKCDSA: n x hsize digests h = H(z || m), stride = hsize; z is the first block-size octets of Yx || Yy, zero
+ *            padded (sig/eckcdsa.c:225-252), and is hashed by the caller, as SM2's Z is.  The device hashes FE2OS(W'x).
+ * Per item, verification is ec_pub_key_import_from_aff_buf + ec_verify with result[i] = 0 / 1 for 0 / -1, for every input:
+ *   ECSDSA / ECOSDSA (sig/ecsdsa_common.c:474-607): s in [1, q - 1]; e = -(OS2I(r) mod q) mod q over all hsize bytes of r, e != 0;
+ *            W' = [s]G + [e]Y not at infinity; accept iff H(W'x [|| W'y] || m) = r.
+ *   ECKCDSA (sig/eckcdsa.c:589-800): s in [1, q - 1]; h' = the last r_len bytes of h; e = OS2I(r XOR h') mod q (0 allowed);
+ *            W' = [s]Y + [e]G not at infinity; accept iff the last r_len bytes of H(FE2OS(W'x)) = r.
+ * Signing is _ec_sign with the nonce k supplied by the caller (k in [1, q - 1]), W = [k]G:
+ *   ECSDSA / ECOSDSA (sig/ecsdsa_common.c:180-371): r = H(Wx [|| Wy] || m), e = OS2I(r) mod q, s = (k + e x) mod q; e = 0 or s = 0 fails.
+ *   ECKCDSA (sig/eckcdsa.c:340-471): r = the last r_len bytes of H(FE2OS(Wx)), e = OS2I(r XOR h') mod q, s = x (k - e) mod q;
+ *            s = 0 restarts, which a fixed nonce cannot get past.
+ * status[i] = 1 with zero signature bytes where ec_key_pair_import_from_priv_key_buf or _ec_sign returns -1 or would restart.
+ * ECKCDSA: x = 0 or x >= q (its public key is [1/x]G).  ECSDSA and ECOSDSA check no range in the reference, which signs with x = 0
+ * and with any x >= q of qlen bytes, s = (k + e x) mod q; so do these calls.
+ * Private keys are x itself.  Chunking by ecamd_ctx_set_max_chunk, n = 0 and NULL arguments as ec_sig_verify_batch /
+ * ec_sig_sign_batch.  Verification multiplies by public values only; signing's [k]G honours ecamd_ctx_set_secret_scalars, and
+ * ecamd_ctx_wipe_scratch covers the staged W and slots.
+ */
+#define ECAMD_SIG_ECKCDSA 2
+#define ECAMD_SIG_ECSDSA 3
+#define ECAMD_SIG_ECOSDSA 4
+int ec_sig_hashed_verify_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n,
+			       const uint8_t *pubkeys_aff, const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, uint8_t *result);
+int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+			     const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, uint8_t *sigs, uint8_t *status);
 /* nn_get_random_mod (nn/nn_rand.c:92-150) given its random bytes.  The reference draws 2 * qlen bytes with get_random straight into the
  * limb array of an nn (they read as a little-endian integer on the little-endian hosts libecc and this library run on), reduces modulo
  * q - 1 and adds one.  raw: n x 2*qlen bytes from the caller's own randomness source; out: n x qlen big-endian, each in [1, q - 1].  The
@@ -552,6 +590,17 @@ int ec_sig_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, u
 int ec_sig_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const void *d_privs,
 			  const void *d_nonces, const void *d_digests, uint32_t digest_len, void *d_sigs, void *d_status,
 			  void *hip_stream);
+/* ec_sig_hashed_verify_batch / ec_sig_hashed_sign_batch with device pointers: enqueue only.  Scratch: besides what a verification
+ * or signing call of the curve takes, ECSDSA / ECOSDSA stage a device-to-device copy of the slots of one chunk -- min(n, max_chunk)
+ * x stride bytes (4 GiB at a chunk of 2^20 items and the largest stride of 4096; 92 MiB at the 92-byte stride of a 24-byte
+ * message on a 256-bit curve) -- although only 4 + length bytes of a slot are hashed: choose the stride to fit the longest
+ * message, or lower ecamd_ctx_set_max_chunk.  ECKCDSA stages 4 + clen bytes per item. */
+int ec_sig_hashed_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n,
+				   const void *d_pubkeys_aff, const void *d_sigs, const void *d_inputs, uint32_t stride, void *d_result,
+				   void *hip_stream);
+int ec_sig_hashed_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_privs,
+				 const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs, void *d_status,
+				 void *hip_stream);
 
 /*
  * ---- several GPUs from C ----

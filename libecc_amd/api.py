@@ -30,10 +30,14 @@ EXPORTED_SYMBOLS = [
     "ec_schnorr_verify_all_batch", "ec_schnorr_verify_all_batch_dev", "ec_schnorr_verify_msg_all_batch", "ec_eddsa_verify_msg_prj_all_batch", "ecamd_multi_eddsa_verify_msg_prj_all_batch", "ecamd_multi_schnorr_verify_msg_all_batch", "ec_schnorr_verify_all_available", "ecamd_multi_schnorr_verify_all_batch", "ecamd_debug_schnorr_msm", "ecamd_debug_schnorr_msm_words",
     "ec_ecdsa_recover_batch", "ec_ecdsa_recover_batch_dev",
     "ec_sig_verify_batch", "ec_sig_verify_batch_dev", "ec_sig_sign_batch", "ec_sig_sign_batch_dev",
+    "ec_sig_hashed_verify_batch", "ec_sig_hashed_verify_batch_dev", "ec_sig_hashed_sign_batch", "ec_sig_hashed_sign_batch_dev",
 ]
 
 # libecc's ec_alg_type numbers of the schemes ec_sig_verify_batch / ec_sig_sign_batch serve (ECAMD_SIG_* in include/libecc_amd.h)
 SIG_ECGDSA, SIG_ECRDSA, SIG_SM2 = 6, 7, 8
+# ... and of the schemes that hash the commitment, served by ec_sig_hashed_verify_batch / ec_sig_hashed_sign_batch
+SIG_ECKCDSA, SIG_ECSDSA, SIG_ECOSDSA = 2, 3, 4
+HASH_SIZES = {1: 28, 2: 32, 3: 48, 4: 64}          # libecc's hash_alg_type numbers of SHA-224 / 256 / 384 / 512
 
 
 class EcamdError(RuntimeError):
@@ -113,6 +117,10 @@ def load_library():
         L.ec_sig_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u8p]
         L.ec_sig_verify_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, u32, vp, vp]
         L.ec_sig_sign_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, u32, vp, vp, vp]
+        L.ec_sig_hashed_verify_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p]
+        L.ec_sig_hashed_sign_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u8p]
+        L.ec_sig_hashed_verify_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, vp, vp]
+        L.ec_sig_hashed_sign_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, vp, vp, vp]
         L.ec_ecdsa_recover_batch.argtypes = [vp, vp, u32, u8p, u8p, u32, u8p, u8p, u8p, u8p]
         L.ec_ecdsa_recover_batch_dev.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp]
         L.ec_eddsa_verify_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp]
@@ -385,6 +393,30 @@ class Curve:
         _chk(self.L, self.L.ec_sig_sign_batch(self.ctx.h, self.h, alg, n, privs, nonces, digests, hlen, sigs, st), "ec_sig_sign_batch")
         return sigs.raw[:2 * self.qlen * n], st.raw[:n]
 
+    def sig_hashed_rlen(self, alg, hash_type):
+        """bytes of r in a signature of ECSDSA / ECOSDSA (the digest size) or ECKCDSA (min(digest size, qlen))"""
+        hs = HASH_SIZES.get(hash_type, 0)
+        return min(hs, self.qlen) if alg == SIG_ECKCDSA else hs
+
+    def sig_hashed_verify(self, alg, hash_type, pubs, sigs, inputs, stride):
+        """ECSDSA / ECOSDSA / ECKCDSA verification: 0 accept / 1 reject per item.  inputs: message slots of `stride` bytes with the blank
+        for the commitment in front of the message (ECSDSA, ECOSDSA), or the digests H(z || m) with stride = digest size (ECKCDSA)"""
+        n = len(pubs) // (2 * self.clen)
+        res = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_sig_hashed_verify_batch(self.ctx.h, self.h, alg, hash_type, n, pubs, sigs, inputs, stride, res),
+             "ec_sig_hashed_verify_batch")
+        return res.raw[:n]
+
+    def sig_hashed_sign(self, alg, hash_type, privs, nonces, inputs, stride):
+        """ECSDSA / ECOSDSA / ECKCDSA signatures (r || s) with caller-supplied nonces, and a status byte per item"""
+        n = len(privs) // self.qlen
+        sl = self.sig_hashed_rlen(alg, hash_type) + self.qlen
+        sigs = C.create_string_buffer(max(1, sl * n))
+        st = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_sig_hashed_sign_batch(self.ctx.h, self.h, alg, hash_type, n, privs, nonces, inputs, stride, sigs, st),
+             "ec_sig_hashed_sign_batch")
+        return sigs.raw[:sl * n], st.raw[:n]
+
     def random_mod(self, raw):
         """nn_get_random_mod given its 2 * qlen random bytes per item: LE(raw) mod (q - 1) + 1, big-endian"""
         n = len(raw) // (2 * self.qlen)
@@ -546,6 +578,14 @@ class Curve:
     def sig_sign_dev(self, alg, n, d_privs, d_nonces, d_digests, hlen, d_sigs, d_status, stream=None):
         _chk(self.L, self.L.ec_sig_sign_batch_dev(self.ctx.h, self.h, alg, n, d_privs, d_nonces, d_digests, hlen, d_sigs, d_status,
                                                    stream), "ec_sig_sign_batch_dev")
+
+    def sig_hashed_verify_dev(self, alg, hash_type, n, d_pubs, d_sigs, d_inputs, stride, d_result, stream=None):
+        _chk(self.L, self.L.ec_sig_hashed_verify_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_pubs, d_sigs, d_inputs, stride, d_result,
+                                                            stream), "ec_sig_hashed_verify_batch_dev")
+
+    def sig_hashed_sign_dev(self, alg, hash_type, n, d_privs, d_nonces, d_inputs, stride, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_sig_hashed_sign_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_privs, d_nonces, d_inputs, stride, d_sigs,
+                                                          d_status, stream), "ec_sig_hashed_sign_batch_dev")
 
     def ecdsa_recover_dev(self, n, d_sigs, d_digests, hlen, d_pub1, d_pub2, d_st1, d_st2, stream=None):
         _chk(self.L, self.L.ec_ecdsa_recover_batch_dev(self.ctx.h, self.h, n, d_sigs, d_digests, hlen, d_pub1, d_pub2, d_st1,

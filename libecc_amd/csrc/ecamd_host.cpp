@@ -21,6 +21,7 @@
 
 #include "../../include/libecc_amd.h"
 #include "ecamd_internal.h"
+#include "ecamd_sighash.h"
 
 // ------------------------------------------------------------------------------------------
 // error reporting
@@ -6315,6 +6316,272 @@ extern "C" int ec_ecdsa_recover_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uin
 	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
 						       hipStream_t s, const std::function<int()> &) {
 		return ecdsa_recover_dev_locked(ctx, cv, m, ip[0], ip[1], hlen, op[2], op[3], op[4], op[5], s);
+	});
+}
+
+// ------------------------------------------------------------------------------------------
+// batched ECSDSA / ECOSDSA / ECKCDSA (include/libecc_amd.h: ec_sig_hashed_*): the schemes that hash the commitment.  Per chunk of
+// at most max_chunk items, verification is
+//   k_hsig_prep       s in [1, q - 1], e from r, the multipliers u (of G) and v (of Y), the flag byte
+//   A = [u]G, B = [v]Y one fixed-base and one variable-base pass; on a cofactor curve [q]Y too, as ECDSA verification does
+//   k_recover_fin     W' = A + B as affine bytes, one shared inversion per eight items (its second sum A - B is not used)
+//   k_recover_redo    the items with A or B at infinity or x_A = x_B, on the complete formulas
+//   k_hsig_fill       W' into the blank of a copy of the caller's slots, or ECKCDSA's slot of FE2OS(W'x)
+//   k_sha2_slots      the digest
+//   k_hsig_cmp        the digest against r
+// and signing is [k]G (secret-scalar mode as the context says), k_hsig_fill, k_sha2_slots, k_hsig_sign.
+// stage: 3 u / [k]G, 4 v / status of [k]G, 5 A, 6 B, 7 stA, 8 stB, 9 flags, 10 subgroup status, 11 [q]Y, 12 W', 13 A - B (a sink: k_recover_fin's second sum, not used here),
+// 14 status of W', 15 status of A - B, 16 staged slots, 17 digests.  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static uint32_t hsig_staged_stride(const ecamd_curve *cv, int alg, uint32_t stride)
+{
+	return alg == ECAMD_SIG_ECKCDSA ? (uint32_t)((4 + cv->clen + 3) & ~3) : stride;
+}
+
+// a stride that cannot hold the length word and the blank: no slot is usable, every item is rejected
+static bool hsig_no_room(const ecamd_curve *cv, int alg, uint32_t stride)
+{
+	return alg != ECAMD_SIG_ECKCDSA && stride < 4u + (uint32_t)echsig::blank_len(alg, cv->clen);
+}
+
+static int hsig_stage_hash(ecamd_ctx *ctx, int hash_type, uint32_t m, EcamdHsigArgs &H, const uint8_t *d_in, uint32_t stride,
+			   hipStream_t s)
+{
+	uint8_t **S = ctx->stage;
+	if (H.alg != ECAMD_SIG_ECKCDSA) {
+		// the caller's array is not modified: the coordinates go into a copy
+		HIPCHK(hipMemcpyAsync(S[16], d_in, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
+	}
+	H.slots = S[16];
+	H.dg = S[17];
+	HIPCHK(ecamd_launch_hsig_fill(H, s));
+	HIPCHK(ecamd_launch_sha2_slots(hash_type, S[16], H.sstride, m, S[17], H.hsize, s));
+	return 0;
+}
+
+static int hsig_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_pub,
+				  const uint8_t *d_sig, const uint8_t *d_in, uint32_t stride, uint8_t *d_res, hipStream_t s)
+{
+	PublicScalars pub_scope(ctx);   // u, v and the group order are public
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
+	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	if (hsig_no_room(cv, alg, stride)) {
+		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
+		return 0;
+	}
+	const size_t siglen = (size_t)echsig::r_len(alg, (int)hsize, (int)ql) + ql;
+	const uint32_t sstride = hsig_staged_stride(cv, alg, stride);
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	const size_t need[18] = {0, 0, 0, chunk * ql, chunk * ql, chunk * plen, chunk * plen, chunk, chunk, chunk, chunk, chunk * plen + 256,
+				 chunk * plen, chunk * plen, chunk, chunk, (size_t)chunk * sstride, (size_t)chunk * hsize};
+	for (int i = 3; i < 18; i++) {
+		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
+			return -1;
+		}
+	}
+	uint8_t **S = ctx->stage;
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		const uint8_t *pub = d_pub + (size_t)off * plen, *in = d_in + (size_t)off * stride;
+		EcamdHsigArgs H;
+		memset(&H, 0, sizeof(H));
+		H.sigs = d_sig + (size_t)off * siglen;
+		H.inputs = in;
+		H.u = S[3];
+		H.v = S[4];
+		H.flags = S[9];
+		H.W = S[12];
+		H.stW = S[14];
+		H.out = d_res + off;
+		H.n = m;
+		H.qlen = (uint32_t)ql;
+		H.clen = (uint32_t)cl;
+		H.hsize = hsize;
+		H.sstride = sstride;
+		H.qslot = cv->qslot;
+		H.alg = alg;
+		HIPCHK(ecamd_launch_hsig_prep(cv->qnw, H, s));
+		if (smul_dev_locked(ctx, cv, m, S[3], (uint32_t)ql, nullptr, S[5], S[7], s) ||
+		    smul_dev_locked(ctx, cv, m, S[4], (uint32_t)ql, pub, S[6], S[8], s)) {
+			return -1;
+		}
+		if (big_cmp(cv->order, cv->q) != 0) {
+			// cofactor != 1: ec_pub_key_import_from_aff_buf also requires [q]Y == infinity (sig/ec_key.c:199-205), as in ecdsa_two_smul_dev
+			if (smul_dev_locked(ctx, cv, m, cv->d_gen + plen, (uint32_t)ql, pub, S[11], S[10], s, 0)) {
+				return -1;
+			}
+			HIPCHK(ecamd_launch_status_require(S[8], S[10], 2, m, s));
+		}
+		EcamdRecoverFinArgs F;
+		F.A = S[5];
+		F.stA = S[7];
+		F.B = S[6];
+		F.stB = S[8];
+		F.flags = S[9];
+		F.yst = S[9];
+		F.out1 = S[12];
+		F.out2 = S[13];   // sinks: the recovery kernels also write A - B and its status, which this path never reads
+		F.st1 = S[14];
+		F.st2 = S[15];
+		F.n = m;
+		F.clen = (uint32_t)cl;
+		F.slot = cv->slot;
+		HIPCHK(ecamd_launch_recover_fin(cv->nw, F, s));
+		HIPCHK(ecamd_launch_recover_redo(cv->nw, F, s));
+		if (hsig_stage_hash(ctx, hash_type, m, H, in, stride, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_hsig_cmp(H, s));
+	}
+	return 0;
+}
+
+static int hsig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_privs,
+				const uint8_t *d_nonces, const uint8_t *d_in, uint32_t stride, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
+{
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
+	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	const size_t siglen = (size_t)echsig::r_len(alg, (int)hsize, (int)ql) + ql;
+	const uint32_t sstride = hsig_staged_stride(cv, alg, stride);
+	if (hsig_no_room(cv, alg, stride)) {
+		HIPCHK(hipMemsetAsync(d_sigs, 0, n * siglen, s));
+		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
+		return 0;
+	}
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], chunk * plen) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], chunk) ||
+	    ensure(&ctx->stage[9], &ctx->stage_bytes[9], chunk) || ensure(&ctx->stage[16], &ctx->stage_bytes[16], (size_t)chunk * sstride) ||
+	    ensure(&ctx->stage[17], &ctx->stage_bytes[17], (size_t)chunk * hsize)) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		const uint8_t *in = d_in + (size_t)off * stride;
+		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[3], S[4], s)) {   // W = [k]G
+			return -1;
+		}
+		EcamdHsigArgs H;
+		memset(&H, 0, sizeof(H));
+		H.inputs = in;
+		H.privs = d_privs + off * ql;
+		H.nonces = d_nonces + off * ql;
+		H.flags = S[9];
+		H.W = S[3];
+		H.stW = S[4];
+		H.out = d_sigs + (size_t)off * siglen;
+		H.status = d_status + off;
+		H.n = m;
+		H.qlen = (uint32_t)ql;
+		H.clen = (uint32_t)cl;
+		H.hsize = hsize;
+		H.sstride = sstride;
+		H.qslot = cv->qslot;
+		H.alg = alg;
+		H.sign = 1;
+		if (hsig_stage_hash(ctx, hash_type, m, H, in, stride, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_hsig_sign(cv->qnw, H, s));
+	}
+	return 0;
+}
+
+static int hsig_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a, const void *b,
+			const void *c, const void *d, const void *e, uint32_t stride)
+{
+	if (!echsig::alg_known(alg)) {
+		return fail(std::string(fn) + ": alg must be ECAMD_SIG_ECKCDSA, ECAMD_SIG_ECSDSA or ECAMD_SIG_ECOSDSA");
+	}
+	if (echsig::hash_size(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224, SHA-256, SHA-384, SHA-512)");
+	}
+	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	if (alg == ECAMD_SIG_ECKCDSA) {
+		if (stride != (uint32_t)echsig::hash_size(hash_type)) {
+			return fail(std::string(fn) + ": ECKCDSA takes digests h = H(z || m): stride must be the hash's digest size");
+		}
+	} else if ((stride & 3u) || stride > 4096 || stride < 4) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	return 0;
+}
+
+extern "C" int ec_sig_hashed_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
+					      const void *d_sigs, const void *d_inputs, uint32_t stride, void *d_result, void *hip_stream)
+{
+	if (hsig_args_ok("ec_sig_hashed_verify_batch_dev", ctx, cv, alg, hash_type, n, d_pubkeys, d_sigs, d_inputs, d_result, d_result, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return hsig_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_inputs, stride,
+				      (uint8_t *)d_result, s);
+}
+
+extern "C" int ec_sig_hashed_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
+					  const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, uint8_t *result)
+{
+	if (hsig_args_ok("ec_sig_hashed_verify_batch", ctx, cv, alg, hash_type, n, pubkeys, sigs, inputs, result, result, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t siglen = (size_t)echsig::r_len(alg, echsig::hash_size(hash_type), cv->qlen) + cv->qlen;
+	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, siglen}, {inputs, nullptr, stride}, {nullptr, result, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+					       hipStream_t s, const std::function<int()> &) {
+		return hsig_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], s);
+	});
+}
+
+extern "C" int ec_sig_hashed_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+					    const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs, void *d_status, void *hip_stream)
+{
+	if (hsig_args_ok("ec_sig_hashed_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_inputs, d_sigs, d_status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return hsig_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_inputs, stride,
+				    (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+}
+
+extern "C" int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+					const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, uint8_t *sigs, uint8_t *status)
+{
+	if (hsig_args_ok("ec_sig_hashed_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, inputs, sigs, status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t ql = (size_t)cv->qlen;
+	const size_t siglen = (size_t)echsig::r_len(alg, echsig::hash_size(hash_type), cv->qlen) + ql;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {inputs, nullptr, stride}, {nullptr, sigs, siglen}, {nullptr, status, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+					       hipStream_t s, const std::function<int()> &) {
+		return hsig_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], op[4], s);
 	});
 }
 

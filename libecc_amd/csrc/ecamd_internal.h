@@ -148,6 +148,27 @@ hipError_t ecamd_launch_recover_point(const EcamdRecoverPointArgs &a, hipStream_
 hipError_t ecamd_launch_recover_fin(int nw, const EcamdRecoverFinArgs &a, hipStream_t s);
 hipError_t ecamd_launch_recover_redo(int nw, const EcamdRecoverFinArgs &a, hipStream_t s);
 
+// ---- ECSDSA / ECOSDSA / ECKCDSA (sig/ecsdsa_common.c, sig/eckcdsa.c of the reference), ecamd_sighash_kernels.h ----
+// One argument block for the four kernels; each reads the fields its step needs.
+struct EcamdHsigArgs {
+	const uint8_t *sigs;     // verification: n x (r_len + qlen), r || s
+	const uint8_t *inputs;   // ECKCDSA: n x hsize, the caller's h = H(z || m); unused by the kernels otherwise
+	const uint8_t *privs, *nonces;   // signing: n x qlen each
+	uint8_t *u, *v;          // k_hsig_prep: n x qlen big-endian, the multipliers of G and Y (zeros where flagged)
+	uint8_t *flags;          // n: 0 ok, 1 rejected before the hash (range checks, e = 0, an unusable slot)
+	const uint8_t *W, *stW;  // the commitment, n x 2*clen affine, and its status (ECAMD_OK / ECAMD_ERR / ECAMD_INF)
+	uint8_t *slots;          // n x sstride: the staged hash input (a copy of the caller's slots, or ECKCDSA's slot of FE2OS(W.x))
+	const uint8_t *dg;       // n x hsize: the digest of the staged slots
+	uint8_t *out;            // k_hsig_cmp: n result bytes; k_hsig_sign: n x (r_len + qlen) signatures
+	uint8_t *status;         // k_hsig_sign: n
+	uint32_t n, qlen, clen, hsize, sstride;
+	int qslot, alg, sign;    // sign != 0: k_hsig_fill runs in a signing call (no front end wrote flags)
+};
+hipError_t ecamd_launch_hsig_prep(int qnw, const EcamdHsigArgs &a, hipStream_t s);
+hipError_t ecamd_launch_hsig_fill(const EcamdHsigArgs &a, hipStream_t s);
+hipError_t ecamd_launch_hsig_cmp(const EcamdHsigArgs &a, hipStream_t s);
+hipError_t ecamd_launch_hsig_sign(int qnw, const EcamdHsigArgs &a, hipStream_t s);
+
 // nw: 32-bit words per field element; must be one of ecamd_supported_nw()
 int ecamd_nw_supported(int nw);
 hipError_t ecamd_upload_curve(int nw, int slot, const void *curvek, size_t bytes);

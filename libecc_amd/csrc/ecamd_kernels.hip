@@ -2857,3 +2857,5 @@ hipError_t ecamd_launch_prj_export(const EcamdPrjOutArgs &a, hipStream_t s)
 // ECDSA public-key recovery: k_recover_prep / _point / _fin / _redo and their launchers
 #include "ecamd_recover_kernels.h"
 #include "ecamd_sigfam_kernels.h"
+// ECSDSA / ECOSDSA / ECKCDSA: k_hsig_prep / _fill / _cmp / _sign and their launchers
+#include "ecamd_sighash_kernels.h"

@@ -204,10 +204,116 @@ def sig_family_row(a, ctx, dev, stream, rng, B):
     ctx.close()
 
 
+def sig_hashed_row(a, ctx, dev, stream, rng, B):
+    """ECSDSA / ECOSDSA / ECKCDSA (ec_sig_hashed_verify_batch_dev or ec_sig_hashed_sign_batch_dev, --alg, SHA-256, 24-byte messages),
+    inputs resident in HBM, beside ec_ecdsa_verify_batch_dev and ec_ecdsa_recover_batch_dev (the same structure: comb, window loop,
+    shared-inversion finish) on the same curve in the same run, in alternating windows of a.steps calls.  Gates: every signature
+    the device made is accepted, and with the inputs of the next item none is.  One GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload sig_hashed_verify / sig_hashed_sign measures one GPU: run it with --gpus 1, outside torch.distributed.run")
+    import hashlib
+    import oracles as O
+    alg = {"eckcdsa": 2, "ecsdsa": 3, "ecosdsa": 4}[a.alg]
+    curve = a.curve
+    cv = ctx.curve(curve)
+    q = O.CURVES[curve]["q"]
+    ql, cl = O.qlen(curve), O.clen(curve)
+    ht, hl, mlen = 2, 32, 24
+    raw = rng.integers(0, 256, size=(2, B, ql + 8), dtype=np.uint8)
+
+    def scal(rows):
+        return [(int.from_bytes(rows[i].tobytes(), "big") % (q - 1)) + 1 for i in range(B)]
+
+    def t(b):
+        return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+    xs, ks = scal(raw[0]), scal(raw[1])
+    privs, nonces = (b"".join(v.to_bytes(ql, "big") for v in vs) for vs in (xs, ks))
+    pubs_e, st = cv.scalar_mult(privs)
+    assert set(st) == {0}
+    pubs = cv.scalar_mult(b"".join(pow(x, -1, q).to_bytes(ql, "big") for x in xs))[0] if alg == 2 else pubs_e
+    msgs = rng.integers(0, 256, size=(B, mlen), dtype=np.uint8)
+    if alg == 2:
+        # h = H(z || m), z the first 64 octets of Yx || Yy (zero padded): hashed by the caller
+        stride = hl
+        inp = b"".join(hashlib.sha256((pubs[2 * cl * i:2 * cl * (i + 1)] + bytes(64))[:64] + msgs[i].tobytes()).digest() for i in range(B))
+    else:
+        bl = 2 * cl if alg == 3 else cl
+        stride = (4 + bl + mlen + 3) & ~3
+        slots = np.zeros((B, stride), dtype=np.uint8)
+        slots[:, 0] = bl + mlen
+        slots[:, 4 + bl:4 + bl + mlen] = msgs
+        inp = slots.tobytes()
+    dg = rng.integers(0, 256, size=hl * B, dtype=np.uint8).tobytes()
+    sigs_e, st = cv.ecdsa_sign(privs, nonces, dg, hl)
+    assert set(st) == {0}
+    sigs, st = cv.sig_hashed_sign(alg, ht, privs, nonces, inp, stride)
+    assert set(st) == {0}
+    d_pub_e, d_sig_e, d_pub, d_sig, d_dg, d_in, d_x, d_k = (t(b) for b in (pubs_e, sigs_e, pubs, sigs, dg, inp, privs, nonces))
+    d_res = torch.empty(B, dtype=torch.uint8, device=dev)
+    d_out, d_st = torch.empty(len(sigs), dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    d_k1, d_k2 = (torch.empty(2 * cl * B, dtype=torch.uint8, device=dev) for _ in range(2))
+    d_s1, d_s2 = (torch.empty(B, dtype=torch.uint8, device=dev) for _ in range(2))
+    sign = a.workload == "sig_hashed_sign"
+
+    def ecdsa():
+        cv.ecdsa_verify_dev(B, d_pub_e.data_ptr(), d_sig_e.data_ptr(), d_dg.data_ptr(), hl, d_res.data_ptr(), stream.cuda_stream)
+
+    def recover():
+        cv.ecdsa_recover_dev(B, d_sig_e.data_ptr(), d_dg.data_ptr(), hl, d_k1.data_ptr(), d_k2.data_ptr(), d_s1.data_ptr(), d_s2.data_ptr(),
+                             stream.cuda_stream)
+
+    def hashed():
+        if sign:
+            cv.sig_hashed_sign_dev(alg, ht, B, d_x.data_ptr(), d_k.data_ptr(), d_in.data_ptr(), stride, d_out.data_ptr(), d_st.data_ptr(),
+                                   stream.cuda_stream)
+        else:
+            cv.sig_hashed_verify_dev(alg, ht, B, d_pub.data_ptr(), d_sig.data_ptr(), d_in.data_ptr(), stride, d_res.data_ptr(), stream.cuda_stream)
+    # ---- gates ----
+    cv.sig_hashed_verify_dev(alg, ht, B, d_pub.data_ptr(), d_sig.data_ptr(), d_in.data_ptr(), stride, d_res.data_ptr(), stream.cuda_stream)
+    torch.cuda.synchronize()
+    if bytes(d_res.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: a signature the device made was rejected")
+    d_rot = torch.roll(d_in, stride)
+    cv.sig_hashed_verify_dev(alg, ht, B, d_pub.data_ptr(), d_sig.data_ptr(), d_rot.data_ptr(), stride, d_res.data_ptr(), stream.cuda_stream)
+    torch.cuda.synchronize()
+    if bytes(d_res.cpu().numpy()) != b"\1" * B:
+        raise SystemExit("PARITY FAILURE: a signature was accepted for another item's input")
+    hashed()
+    torch.cuda.synchronize()
+    if sign and (bytes(d_out.cpu().numpy()) != sigs or bytes(d_st.cpu().numpy()) != bytes(B)):
+        raise SystemExit("PARITY FAILURE: the device-pointer form signs differently")
+    gate = "all 2^%d device-made signatures accepted, none for its neighbour's input" % a.batch_log2
+    # ---- timing: alternating windows ----
+    for _ in range(a.warmup):
+        ecdsa()
+        recover()
+        hashed()
+    torch.cuda.synchronize()
+    te, tr, tf = [], [], []
+    for _ in range(3):
+        for fn, acc in ((ecdsa, te), (recover, tr), (hashed, tf)):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            acc.append((time.perf_counter() - t0) / a.steps)
+    me, mr, mf = float(np.median(te)), float(np.median(tr)), float(np.median(tf))
+    kind = "signatures" if sign else "verifications"
+    print(json.dumps({"metric": "%s %s/sec (%s, SHA-256, batch=2^%d, device-resident)" % (a.alg.upper(), kind, curve.lower(), a.batch_log2),
+                      "value": B / mf, "unit": kind + "/s", "hashed_ms": [1e3 * x for x in tf],
+                      "ecdsa_verify_same_run": {"value": B / me, "unit": "verifications/s", "ms": [1e3 * x for x in te]},
+                      "ecdsa_recover_same_run": {"value": B / mr, "unit": "recoveries/s", "ms": [1e3 * x for x in tr]},
+                      "hashed_over_recover": mr / mf, "gate": gate,
+                      "config": {"workload": a.workload, "alg": a.alg, "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+    cv.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
-    ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2"], help="sig_verify / sig_sign: the scheme")
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa"],
+                    help="sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -256,6 +362,8 @@ def main():
         return recover_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("sig_verify", "sig_sign"):
         return sig_family_row(a, ctx, dev, stream, rng, B)
+    if a.workload in ("sig_hashed_verify", "sig_hashed_sign"):
+        return sig_hashed_row(a, ctx, dev, stream, rng, B)
     if a.workload == "ecdsa_verify":
         curve = a.curve
         cv = ctx.curve(curve)
