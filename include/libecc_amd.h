@@ -333,6 +333,53 @@ int ec_sig_hashed_verify_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg
 			       const uint8_t *pubkeys_aff, const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, uint8_t *result);
 int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *privs,
 			     const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, uint8_t *sigs, uint8_t *status);
+/* BIP0340 and ECFSDSA ITEM BY ITEM: the two Schnorr-type schemes whose signature carries the commitment as a point, with a verdict
+ * per item -- what ec_schnorr_verify_all_batch / ec_schnorr_verify_msg_all_batch cannot give ("valid" or "not decided" for the whole
+ * batch) -- and their signing.  alg: libecc's ec_alg_type numbers (lib_ecc_types.h); hash_type 1 .. 4 (SHA-224 / 256 / 384 / 512);
+ * any other alg or hash_type is a call-level -1 with ecamd_last_error().
+ *
+ * Verification is, per item, ec_pub_key_import_from_aff_buf (key_fmt ECAMD_PT_AFFINE: keys n x 2*clen X || Y) or
+ * ec_pub_key_import_from_buf (ECAMD_PT_PROJECTIVE: n x 3*clen X || Y || Z) followed by ec_verify; result[i] = 0 / 1 for its 0 / -1, for
+ * EVERY input.  Keys, signatures (r_len + qlen bytes, r_len = clen for BIP0340 and 2*clen for ECFSDSA) and hash slots have the formats of
+ * ec_schnorr_verify_msg_all_batch, so a caller whose whole-batch call came back "not decided" hands the same arrays to this call.
+ * A slot is a little-endian u32 length, then the scheme's hash input, `stride` bytes in all (a multiple of 4 in 4 .. 4096):
+ *   BIP0340  H(tag) || H(tag) || r || <blank clen> || m     tag = "BIP0340/challenge" (sig/bip0340.c:437-441)
+ *   ECFSDSA  W.x || W.y || m                               (sig/ecfsdsa.c:472-482)
+ * The caller's array is never modified: in a staged copy the device writes the key's x into the blank and OVERWRITES the commitment
+ * field with the signature's own r (W) bytes, so the verdict depends on key, signature and message only.  A slot whose length does not
+ * hold the fixed fields or does not fit the stride rejects its item; a stride too small for the fixed fields rejects every item.
+ *   BIP0340 (sig/bip0340.c:383-560): the key's unique representative (a key at infinity fails), then the one with an even y; r < p,
+ *     s < q (s = 0 is NOT refused by the range check); e = H(slot) mod q over the whole digest; R = [s]G + [q - e]Y must be finite, have
+ *     an even y and R.x = r.
+ *   ECFSDSA (sig/ecfsdsa.c:404-607): W.x, W.y < p and W on the curve, s in [1, q - 1]; e = H(W.x || W.y || m) mod q; W' = [s]G + [q - e]Y
+ *     must be finite and both affine coordinates equal the signature's bytes.  A key at infinity (0 : y : 0) is used as it is (W' = [s]G);
+ *     (0 : 0 : 0) imports but cannot be multiplied: rejected.
+ * On cofactor curves the key import's subgroup check ([q]Y = infinity) applies.  There is no prime-order restriction and no radix-2^29
+ * requirement: every handle ec_prj_pt_mul_batch serves is served, ecamd_curve_from_params handles included.  Every multiplier is public
+ * (whatever ecamd_ctx_set_secret_scalars says).
+ *
+ * Signing is _ec_sign with the nonce supplied by the caller, as for every other signing call here.
+ *   nonces  n x qlen: the value k the scheme multiplies G by, k in [1, q - 1], otherwise status 1.  For BIP0340 that is the reference's
+ *           H_nonce(...) mod q (sig/bip0340.c:237-294): the "BIP0340/aux" and "BIP0340/nonce" tagged hashes STAY WITH THE CALLER, as RFC 6979
+ *           does for ECDSA.
+ *   privs   n x qlen: x itself.  BIP0340: 0 < x < q, ECFSDSA: x < q (the reference signs with x = 0: s = k), otherwise status 1.
+ *   pubkeys_aff  BIP0340: the key pair's public half, n x 2*clen -- its x is hashed and the parity of its y decides d <-> q - d.  NULL:
+ *           the device derives Y = [x]G (fixed-base, honours secret-scalar mode).  Non-NULL: imported (coordinates < p, on the curve,
+ *           otherwise status 1) and used as the reference uses key_pair->pub_key (not compared with [x]G).  ECFSDSA ignores it.
+ *   slots   BIP0340: H(tag) || H(tag) || <blank clen: r> || <blank clen: Y.x> || m;  ECFSDSA: <blank 2*clen: W> || m; the blanks are
+ *           counted in the length.  Unusable slots and a stride too small: as in verification, status 1.
+ *   BIP0340: R = [k]G, affine; R.y odd: k <- q - k; Y.y odd: d = q - x, else d = x; r = R.x, e = H(slot) mod q, s = (k + e d) mod q.
+ *   ECFSDSA: W = [k]G, r = W.x || W.y, e = H(r || m) mod q, s = (k + e x) mod q; s = 0 is status 1.
+ * A status 1 item has all-zero signature bytes.  [k]G (and [x]G) honour ecamd_ctx_set_secret_scalars.
+ * Chunking by ecamd_ctx_set_max_chunk, n = 0, NULL arguments and a handle of another context behave as for ec_sig_hashed_*;
+ * ecamd_ctx_wipe_scratch covers the staged slots, keys and commitments. */
+#define ECAMD_SIG_ECFSDSA 5
+#define ECAMD_SIG_BIP0340 20
+int ec_schnorr_verify_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *keys, int key_fmt,
+			    const uint8_t *sigs, const uint8_t *hash_slots, uint32_t stride, uint8_t *result);
+int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+			  const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+			  uint8_t *status);
 /* nn_get_random_mod (nn/nn_rand.c:92-150) given its random bytes.  The reference draws 2 * qlen bytes with get_random straight into the
  * limb array of an nn (they read as a little-endian integer on the little-endian hosts libecc and this library run on), reduces modulo
  * q - 1 and adds one.  raw: n x 2*qlen bytes from the caller's own randomness source; out: n x qlen big-endian, each in [1, q - 1].  The
@@ -601,6 +648,14 @@ int ec_sig_hashed_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int
 int ec_sig_hashed_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_privs,
 				 const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs, void *d_status,
 				 void *hip_stream);
+/* ec_schnorr_verify_batch / ec_schnorr_sign_batch with device pointers: enqueue only.  Scratch: besides what a verification or signing
+ * call of the curve takes, a device-to-device copy of the slots of one chunk (min(n, max_chunk) x stride bytes: choose the stride to fit
+ * the longest message, or lower ecamd_ctx_set_max_chunk).  d_pubkeys_aff may be NULL, as pubkeys_aff. */
+int ec_schnorr_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_keys, int key_fmt,
+				const void *d_sigs, const void *d_hash_slots, uint32_t stride, void *d_result, void *hip_stream);
+int ec_schnorr_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_privs,
+			      const void *d_pubkeys_aff, const void *d_nonces, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+			      void *d_status, void *hip_stream);
 
 /*
  * ---- several GPUs from C ----

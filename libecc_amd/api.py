@@ -31,12 +31,15 @@ EXPORTED_SYMBOLS = [
     "ec_ecdsa_recover_batch", "ec_ecdsa_recover_batch_dev",
     "ec_sig_verify_batch", "ec_sig_verify_batch_dev", "ec_sig_sign_batch", "ec_sig_sign_batch_dev",
     "ec_sig_hashed_verify_batch", "ec_sig_hashed_verify_batch_dev", "ec_sig_hashed_sign_batch", "ec_sig_hashed_sign_batch_dev",
+    "ec_schnorr_verify_batch", "ec_schnorr_verify_batch_dev", "ec_schnorr_sign_batch", "ec_schnorr_sign_batch_dev",
 ]
 
 # libecc's ec_alg_type numbers of the schemes ec_sig_verify_batch / ec_sig_sign_batch serve (ECAMD_SIG_* in include/libecc_amd.h)
 SIG_ECGDSA, SIG_ECRDSA, SIG_SM2 = 6, 7, 8
 # ... and of the schemes that hash the commitment, served by ec_sig_hashed_verify_batch / ec_sig_hashed_sign_batch
 SIG_ECKCDSA, SIG_ECSDSA, SIG_ECOSDSA = 2, 3, 4
+# ... and of the two Schnorr-type schemes with a point commitment, served item by item by ec_schnorr_verify_batch / ec_schnorr_sign_batch
+SIG_ECFSDSA, SIG_BIP0340 = 5, 20
 HASH_SIZES = {1: 28, 2: 32, 3: 48, 4: 64}          # libecc's hash_alg_type numbers of SHA-224 / 256 / 384 / 512
 
 
@@ -121,6 +124,10 @@ def load_library():
         L.ec_sig_hashed_sign_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u8p]
         L.ec_sig_hashed_verify_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, vp, vp]
         L.ec_sig_hashed_sign_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, vp, vp, vp]
+        L.ec_schnorr_verify_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, C.c_int, u8p, u8p, u32, u8p]
+        L.ec_schnorr_sign_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u8p, u32, u8p, u8p]
+        L.ec_schnorr_verify_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, C.c_int, vp, vp, u32, vp, vp]
+        L.ec_schnorr_sign_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, vp, u32, vp, vp, vp]
         L.ec_ecdsa_recover_batch.argtypes = [vp, vp, u32, u8p, u8p, u32, u8p, u8p, u8p, u8p]
         L.ec_ecdsa_recover_batch_dev.argtypes = [vp, vp, u32, vp, vp, u32, vp, vp, vp, vp, vp]
         L.ec_eddsa_verify_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp]
@@ -417,6 +424,30 @@ class Curve:
              "ec_sig_hashed_sign_batch")
         return sigs.raw[:sl * n], st.raw[:n]
 
+    def schnorr_rlen(self, alg):
+        """bytes of the commitment in a BIP0340 (R.x) / ECFSDSA (W.x || W.y) signature"""
+        return self.clen if alg == SIG_BIP0340 else 2 * self.clen
+
+    def schnorr_verify(self, alg, hash_type, keys, key_fmt, sigs, slots, stride):
+        """BIP0340 / ECFSDSA verification item by item (alg: SIG_BIP0340, SIG_ECFSDSA; hash_type 1 .. 4): 0 accept / 1 reject per item.
+        keys: X || Y (key_fmt 0) or X || Y || Z (1); slots: the hash inputs of ec_schnorr_verify_msg_all_batch"""
+        n = len(sigs) // (self.schnorr_rlen(alg) + self.qlen)
+        res = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_schnorr_verify_batch(self.ctx.h, self.h, alg, hash_type, n, keys, key_fmt, sigs, slots, stride, res),
+             "ec_schnorr_verify_batch")
+        return res.raw[:n]
+
+    def schnorr_sign(self, alg, hash_type, privs, pubs, nonces, slots, stride):
+        """BIP0340 / ECFSDSA signatures (r || s) with caller-supplied nonces, and a status byte per item; pubs: X || Y per item, or None
+        (BIP0340 derives Y = [x]G on the device; ECFSDSA ignores it)"""
+        n = len(privs) // self.qlen
+        sl = self.schnorr_rlen(alg) + self.qlen
+        sigs = C.create_string_buffer(max(1, sl * n))
+        st = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_schnorr_sign_batch(self.ctx.h, self.h, alg, hash_type, n, privs, pubs, nonces, slots, stride, sigs, st),
+             "ec_schnorr_sign_batch")
+        return sigs.raw[:sl * n], st.raw[:n]
+
     def random_mod(self, raw):
         """nn_get_random_mod given its 2 * qlen random bytes per item: LE(raw) mod (q - 1) + 1, big-endian"""
         n = len(raw) // (2 * self.qlen)
@@ -586,6 +617,14 @@ class Curve:
     def sig_hashed_sign_dev(self, alg, hash_type, n, d_privs, d_nonces, d_inputs, stride, d_sigs, d_status, stream=None):
         _chk(self.L, self.L.ec_sig_hashed_sign_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_privs, d_nonces, d_inputs, stride, d_sigs,
                                                           d_status, stream), "ec_sig_hashed_sign_batch_dev")
+
+    def schnorr_verify_dev(self, alg, hash_type, n, d_keys, key_fmt, d_sigs, d_slots, stride, d_result, stream=None):
+        _chk(self.L, self.L.ec_schnorr_verify_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_keys, key_fmt, d_sigs, d_slots, stride, d_result,
+                                                         stream), "ec_schnorr_verify_batch_dev")
+
+    def schnorr_sign_dev(self, alg, hash_type, n, d_privs, d_pubs, d_nonces, d_slots, stride, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_schnorr_sign_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_privs, d_pubs, d_nonces, d_slots, stride, d_sigs,
+                                                       d_status, stream), "ec_schnorr_sign_batch_dev")
 
     def ecdsa_recover_dev(self, n, d_sigs, d_digests, hlen, d_pub1, d_pub2, d_st1, d_st2, stream=None):
         _chk(self.L, self.L.ec_ecdsa_recover_batch_dev(self.ctx.h, self.h, n, d_sigs, d_digests, hlen, d_pub1, d_pub2, d_st1,

@@ -16,6 +16,8 @@ DEPS = ["ecamd_madchain.h", "ecamd_field.h", "ecamd_point.h", "ecamd_u29.h", "ec
         "ecamd_internal.h", "ecamd_lattice.h", "ecamd_randmod.h", "ecamd_recover.h", "ecamd_recover_kernels.h",
         "ecamd_sigfam.h", "ecamd_sigfam_kernels.h", "ecamd_sighash.h", "ecamd_sighash_kernels.h",
         "ecamd_curve_table.inc"]
+# headers that only some translation units include
+SOURCE_DEPS = {"ecamd_kernels.hip": ["ecamd_schnorr.h", "ecamd_schnorr_kernels.h"], "ecamd_host.cpp": ["ecamd_schnorr.h"]}
 # the public header only matters to the host-side translation units (the kernels see ecamd_internal.h)
 HOST_DEPS = [os.path.join("..", "..", "include", "libecc_amd.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -72,7 +74,8 @@ def build(force=False, verbose=False):
             same_cmd = open(opath + ".cmd").read() == " ".join(cmd)
         except OSError:
             same_cmd = False
-        if force or not same_cmd or _stale(opath, [spath] + deps + (hdeps if src.endswith(".cpp") else [])):
+        if force or not same_cmd or _stale(opath, [spath] + deps + (hdeps if src.endswith(".cpp") else []) +
+                                              [os.path.join(CSRC, d) for d in SOURCE_DEPS.get(src, [])]):
             todo.append(cmd)
 
     def run(cmd):

@@ -22,6 +22,7 @@
 #include "../../include/libecc_amd.h"
 #include "ecamd_internal.h"
 #include "ecamd_sighash.h"
+#include "ecamd_schnorr.h"
 
 // ------------------------------------------------------------------------------------------
 // error reporting
@@ -6582,6 +6583,338 @@ extern "C" int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, i
 	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
 					       hipStream_t s, const std::function<int()> &) {
 		return hsig_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], op[4], s);
+	});
+}
+
+// ------------------------------------------------------------------------------------------
+// BIP0340 / ECFSDSA item by item (include/libecc_amd.h: ec_schnorr_verify_batch, ec_schnorr_sign_batch): the two schemes whose
+// signature carries the commitment as a point.  Per chunk of at most max_chunk items, verification is
+//   k_prj_import           projective keys only: prj_pt_import_from_buf + prj_pt_unique (affine keys are validated by the multiplication)
+//   k_schnorr_item_prep    key status and ranges, r < p (W.x, W.y < p), s in range, the slot's length; the flag byte, the key as
+//                          the equation uses it, s; the copy of the caller's slots patched with the signature's r (W) and the key's x
+//   k_ptf (op 2)           ECFSDSA: W on the curve
+//   k_sha2_slots, k_schnorr_ne   e = H(slot) mod q, then q - e
+//   A = [s]G, B = [q - e]Y one fixed-base and one variable-base pass; on a cofactor curve [q]Y too, as ECDSA verification does
+//   k_recover_fin / _redo  W' = A + B as affine bytes, one shared inversion per eight items; the exceptional pairs on the complete formulas
+//   k_schnorr_item_cmp     BIP0340: finite, y even, x = r; ECFSDSA: finite, x || y = r
+// and signing is [k]G (secret-scalar mode as the context says), BIP0340: Y = [x]G (the same) or the caller's key through k_ptf (op 2),
+// k_schnorr_item_fill, k_sha2_slots, k_schnorr_item_sign.
+// stage: 3 s / [k]G, 4 q - e / status of [k]G, 5 A / Y, 6 B, 7 stA / status of Y, 8 stB, 9 flags, 10 subgroup status, 11 [q]Y, 12 W',
+// 13 A - B (a sink), 14 status of W', 15 status of A - B, 16 staged slots, 17 digests, 18 the key as the equation uses it,
+// 20 / 21 the projective import's keys and status, 22 / 23 ECFSDSA's W and its on-curve status.  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static bool schnorr_item_no_room(const ecamd_curve *cv, int alg, uint32_t hsize, uint32_t stride)
+{
+	return stride < 4u + (uint32_t)ecschnorr::fixed_len(alg, (int)hsize, cv->clen);
+}
+
+static void schnorr_item_args(EcamdSchnorrItemArgs &H, const ecamd_curve *cv, int alg, uint32_t hsize, uint32_t stride, uint32_t m)
+{
+	memset(&H, 0, sizeof(H));
+	H.n = m;
+	H.qlen = (uint32_t)cv->qlen;
+	H.clen = (uint32_t)cv->clen;
+	H.hsize = hsize;
+	H.sstride = stride;
+	H.qslot = cv->qslot;
+	H.alg = alg;
+	big_to_be(H.p_be, cv->clen, cv->p);
+}
+
+static int schnorr_item_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_keys,
+					  int key_fmt, const uint8_t *d_sig, const uint8_t *d_in, uint32_t stride, uint8_t *d_res, hipStream_t s)
+{
+	PublicScalars pub_scope(ctx);   // s, q - e and the group order are public
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
+	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	if (schnorr_item_no_room(cv, alg, hsize, stride)) {
+		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
+		return 0;
+	}
+	const bool fs = alg == ECAMD_SIG_ECFSDSA, prj = key_fmt == ECAMD_PT_PROJECTIVE;
+	const size_t siglen = (size_t)ecschnorr::r_len(alg, (int)cl) + ql, kw = (prj ? 3 : 2) * cl;
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	const size_t need[24] = {0, 0, 0, chunk * ql, chunk * ql, chunk * plen, chunk * plen, chunk, chunk, chunk, chunk, chunk * plen + 256,
+				 chunk * plen, chunk * plen, chunk, chunk, (size_t)chunk * stride, (size_t)chunk * hsize, chunk * plen, 0,
+				 prj ? chunk * plen : 0, prj ? chunk : 0, fs ? chunk * plen : 0, fs ? chunk : 0};
+	for (int i = 3; i < 24; i++) {
+		if (need[i] && ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
+			return -1;
+		}
+	}
+	uint8_t **S = ctx->stage;
+	EcamdSchnorrNeArgs N;
+	memset(&N, 0, sizeof(N));
+	for (int w = 0; w < 18; w++) {
+		N.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
+	}
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		const uint8_t *keys = d_keys + (size_t)off * kw, *kst = nullptr;
+		if (prj) {
+			EcamdPrjInArgs I;
+			I.in = keys;
+			I.aff = S[20];
+			I.pre = S[21];
+			I.n = m;
+			I.clen = (uint32_t)cl;
+			I.for_mul = fs ? 1 : 0;   // (0 : 0 : 0): ECFSDSA multiplies the key as it is, BIP0340 takes its unique representative
+			I.slot = cv->slot;
+			HIPCHK(launch_prj_import(cv, I, s));
+			keys = S[20];
+			kst = S[21];
+		}
+		// the caller's array is not modified: the patches go into a copy
+		HIPCHK(hipMemcpyAsync(S[16], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
+		EcamdSchnorrItemArgs H;
+		schnorr_item_args(H, cv, alg, hsize, stride, m);
+		H.keys = keys;
+		H.kst = kst;
+		H.gen = cv->d_gen;
+		H.sigs = d_sig + (size_t)off * siglen;
+		H.slots = S[16];
+		H.key_out = S[18];
+		H.s_out = S[3];
+		H.w_out = fs ? S[22] : nullptr;
+		H.flags = S[9];
+		H.wst = fs ? S[23] : nullptr;
+		H.A = S[5];
+		H.stA = S[7];
+		H.W = S[12];
+		H.stW = S[14];
+		H.out = d_res + off;
+		HIPCHK(ecamd_launch_schnorr_item_prep(cv->qnw, H, s));
+		if (fs) {
+			// "Reject the signature if r is not a valid point on the curve" (ecfsdsa.c:449-460): the on-curve test the point calls use
+			EcamdPtfArgs T;
+			memset(&T, 0, sizeof(T));
+			T.p1 = S[22];
+			T.p2 = S[22];
+			T.out = S[22];   // untouched by op 2
+			T.status = S[23];
+			T.n = m;
+			T.clen = (uint32_t)cl;
+			T.op = 2;
+			T.slot = cv->slot;
+			HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
+		}
+		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[16], stride, m, S[17], hsize, s));
+		N.dig = S[17];
+		N.ne = S[4];
+		N.n = m;
+		N.hlen = hsize;
+		N.qlen = (uint32_t)ql;
+		HIPCHK(ecamd_launch_schnorr_ne(cv->qnw, N, s));
+		if (smul_dev_locked(ctx, cv, m, S[3], (uint32_t)ql, nullptr, S[5], S[7], s) ||
+		    smul_dev_locked(ctx, cv, m, S[4], (uint32_t)ql, S[18], S[6], S[8], s)) {
+			return -1;
+		}
+		if (big_cmp(cv->order, cv->q) != 0) {
+			// cofactor != 1: the key import also requires [q]Y == infinity (sig/ec_key.c:199-205), as in hsig_verify_dev_locked
+			if (smul_dev_locked(ctx, cv, m, cv->d_gen + plen, (uint32_t)ql, S[18], S[11], S[10], s, 0)) {
+				return -1;
+			}
+			HIPCHK(ecamd_launch_status_require(S[8], S[10], 2, m, s));
+		}
+		EcamdRecoverFinArgs F;
+		F.A = S[5];
+		F.stA = S[7];
+		F.B = S[6];
+		F.stB = S[8];
+		// k_recover_fin takes ANY non-zero flag as "no sum for this item": that holds for flag 2 too (ECFSDSA, the key at infinity),
+		// whose verdict k_schnorr_item_cmp reads from A = [s]G and stA, not from W'
+		F.flags = S[9];
+		F.yst = S[9];
+		F.out1 = S[12];
+		F.out2 = S[13];   // sinks, as in hsig_verify_dev_locked
+		F.st1 = S[14];
+		F.st2 = S[15];
+		F.n = m;
+		F.clen = (uint32_t)cl;
+		F.slot = cv->slot;
+		HIPCHK(ecamd_launch_recover_fin(cv->nw, F, s));
+		HIPCHK(ecamd_launch_recover_redo(cv->nw, F, s));
+		HIPCHK(ecamd_launch_schnorr_item_cmp(H, s));
+	}
+	return 0;
+}
+
+static int schnorr_item_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_privs,
+					const uint8_t *d_pubs, const uint8_t *d_nonces, const uint8_t *d_in, uint32_t stride, uint8_t *d_sigs,
+					uint8_t *d_status, hipStream_t s)
+{
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
+	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	const size_t siglen = (size_t)ecschnorr::r_len(alg, (int)cl) + ql;
+	if (schnorr_item_no_room(cv, alg, hsize, stride)) {
+		HIPCHK(hipMemsetAsync(d_sigs, 0, n * siglen, s));
+		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
+		return 0;
+	}
+	const bool bip = alg == ECAMD_SIG_BIP0340;
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], chunk * plen) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], chunk) ||
+	    ensure(&ctx->stage[9], &ctx->stage_bytes[9], chunk) || ensure(&ctx->stage[16], &ctx->stage_bytes[16], (size_t)chunk * stride) ||
+	    ensure(&ctx->stage[17], &ctx->stage_bytes[17], (size_t)chunk * hsize) ||
+	    (bip && (ensure(&ctx->stage[5], &ctx->stage_bytes[5], chunk * plen) || ensure(&ctx->stage[7], &ctx->stage_bytes[7], chunk)))) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[3], S[4], s)) {   // R = [k]G
+			return -1;
+		}
+		EcamdSchnorrItemArgs H;
+		schnorr_item_args(H, cv, alg, hsize, stride, m);
+		if (bip && d_pubs) {
+			// the key pair's public half as the caller holds it: coordinates < p and on the curve
+			EcamdPtfArgs T;
+			memset(&T, 0, sizeof(T));
+			T.p1 = d_pubs + off * plen;
+			T.p2 = T.p1;
+			T.out = S[5];   // untouched by op 2
+			T.status = S[7];
+			T.n = m;
+			T.clen = (uint32_t)cl;
+			T.op = 2;
+			T.slot = cv->slot;
+			HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
+			H.keys = d_pubs + off * plen;
+		} else if (bip) {
+			if (smul_dev_locked(ctx, cv, m, d_privs + off * ql, (uint32_t)ql, nullptr, S[5], S[7], s)) {   // Y = [x]G
+				return -1;
+			}
+			H.keys = S[5];
+		}
+		H.kst = bip ? S[7] : nullptr;
+		H.privs = d_privs + off * ql;
+		H.nonces = d_nonces + off * ql;
+		H.slots = S[16];
+		H.flags = S[9];
+		H.W = S[3];
+		H.stW = S[4];
+		H.dg = S[17];
+		H.out = d_sigs + (size_t)off * siglen;
+		H.status = d_status + off;
+		HIPCHK(hipMemcpyAsync(S[16], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
+		HIPCHK(ecamd_launch_schnorr_item_fill(H, s));
+		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[16], stride, m, S[17], hsize, s));
+		HIPCHK(ecamd_launch_schnorr_item_sign(cv->qnw, H, s));
+	}
+	return 0;
+}
+
+static int schnorr_item_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a,
+				const void *b, const void *c, const void *d, const void *e, uint32_t stride)
+{
+	if (!ecschnorr::alg_known(alg)) {
+		return fail(std::string(fn) + ": alg must be ECAMD_SIG_BIP0340 or ECAMD_SIG_ECFSDSA");
+	}
+	if (echsig::hash_size(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224, SHA-256, SHA-384, SHA-512)");
+	}
+	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	if ((stride & 3u) || stride > 4096 || stride < 4) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	return 0;
+}
+
+static int schnorr_item_fmt_ok(const char *fn, int key_fmt)
+{
+	if (key_fmt != ECAMD_PT_AFFINE && key_fmt != ECAMD_PT_PROJECTIVE) {
+		return fail(std::string(fn) + ": key_fmt must be ECAMD_PT_AFFINE or ECAMD_PT_PROJECTIVE");
+	}
+	return 0;
+}
+
+extern "C" int ec_schnorr_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_keys,
+					   int key_fmt, const void *d_sigs, const void *d_hash_slots, uint32_t stride, void *d_result,
+					   void *hip_stream)
+{
+	if (schnorr_item_args_ok("ec_schnorr_verify_batch_dev", ctx, cv, alg, hash_type, n, d_keys, d_sigs, d_hash_slots, d_result, d_result, stride) ||
+	    schnorr_item_fmt_ok("ec_schnorr_verify_batch_dev", key_fmt)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return schnorr_item_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_keys, key_fmt, (const uint8_t *)d_sigs,
+					      (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_result, s);
+}
+
+extern "C" int ec_schnorr_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *keys, int key_fmt,
+				       const uint8_t *sigs, const uint8_t *hash_slots, uint32_t stride, uint8_t *result)
+{
+	if (schnorr_item_args_ok("ec_schnorr_verify_batch", ctx, cv, alg, hash_type, n, keys, sigs, hash_slots, result, result, stride) ||
+	    schnorr_item_fmt_ok("ec_schnorr_verify_batch", key_fmt)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t cl = (size_t)cv->clen, siglen = (size_t)ecschnorr::r_len(alg, cv->clen) + cv->qlen;
+	const std::vector<HostArr> arrs = {{keys, nullptr, (key_fmt == ECAMD_PT_PROJECTIVE ? 3 : 2) * cl}, {sigs, nullptr, siglen},
+					   {hash_slots, nullptr, stride}, {nullptr, result, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+						       hipStream_t s, const std::function<int()> &) {
+		return schnorr_item_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], key_fmt, ip[1], ip[2], stride, op[3], s);
+	});
+}
+
+extern "C" int ec_schnorr_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+					 const void *d_pubkeys_aff, const void *d_nonces, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+					 void *d_status, void *hip_stream)
+{
+	if (schnorr_item_args_ok("ec_schnorr_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_hash_slots, d_sigs, d_status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return schnorr_item_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff,
+					    (const uint8_t *)d_nonces, (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+}
+
+extern "C" int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+				     const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+				     uint8_t *status)
+{
+	if (schnorr_item_args_ok("ec_schnorr_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, hash_slots, sigs, status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t ql = (size_t)cv->qlen, plen = (size_t)2 * cv->clen;
+	const size_t siglen = (size_t)ecschnorr::r_len(alg, cv->clen) + ql;
+	const bool with_pub = alg == ECAMD_SIG_BIP0340 && pubkeys_aff != nullptr;   // ECFSDSA ignores it
+	std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {hash_slots, nullptr, stride}, {nullptr, sigs, siglen},
+				     {nullptr, status, 1}};
+	if (with_pub) {
+		arrs.push_back({pubkeys_aff, nullptr, plen});
+	}
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+						       hipStream_t s, const std::function<int()> &) {
+		return schnorr_item_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], with_pub ? ip[5] : nullptr, ip[1], ip[2], stride, op[3], op[4], s);
 	});
 }
 

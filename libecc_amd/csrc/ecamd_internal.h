@@ -169,6 +169,34 @@ hipError_t ecamd_launch_hsig_fill(const EcamdHsigArgs &a, hipStream_t s);
 hipError_t ecamd_launch_hsig_cmp(const EcamdHsigArgs &a, hipStream_t s);
 hipError_t ecamd_launch_hsig_sign(int qnw, const EcamdHsigArgs &a, hipStream_t s);
 
+// ---- BIP0340 / ECFSDSA item by item (sig/bip0340.c, sig/ecfsdsa.c of the reference), ecamd_schnorr_kernels.h ----
+// One argument block for the four kernels; each reads the fields its step needs.
+struct EcamdSchnorrItemArgs {
+	const uint8_t *keys;     // n x 2*clen affine: verification: the keys (the caller's, or the projective import's); signing, BIP0340: Y
+	const uint8_t *kst;      // n: their status (ECAMD_OK / ECAMD_ERR / ECAMD_INF); NULL: affine keys nothing has looked at yet
+	const uint8_t *gen;      // k_schnorr_item_prep: the generator, 2*clen affine bytes (stands in for ECFSDSA's key at infinity)
+	const uint8_t *sigs;     // verification: n x (r_len + qlen)
+	const uint8_t *privs, *nonces;   // signing: n x qlen each
+	uint8_t *slots;          // n x sstride: the staged copy of the caller's slots
+	uint8_t *key_out;        // k_schnorr_item_prep: n x 2*clen, the key as the equation uses it (BIP0340: the even-y representative)
+	uint8_t *s_out;          // k_schnorr_item_prep: n x qlen, s (zeros where flagged)
+	uint8_t *w_out;          // k_schnorr_item_prep, ECFSDSA: n x 2*clen, the signature's W for the on-curve test
+	uint8_t *flags;          // n: 0 ok, 1 rejected before the multiplications; 2 (ECFSDSA): ok, and the key is the point at infinity
+	const uint8_t *wst;      // k_schnorr_item_cmp, ECFSDSA: n, the on-curve test of W (0 on the curve)
+	const uint8_t *A, *stA;  // k_schnorr_item_cmp: [s]G and its status (the sum where the key is the point at infinity)
+	const uint8_t *W, *stW;  // the sum W' (verification) / the commitment [k]G (signing), n x 2*clen affine, and its status
+	const uint8_t *dg;       // k_schnorr_item_sign: n x hsize, the digest of the staged slots
+	uint8_t *out;            // k_schnorr_item_cmp: n result bytes; k_schnorr_item_sign: n x (r_len + qlen) signatures
+	uint8_t *status;         // k_schnorr_item_sign: n
+	uint32_t n, qlen, clen, hsize, sstride;
+	int qslot, alg;
+	uint8_t p_be[72];        // the field prime, clen bytes big-endian
+};
+hipError_t ecamd_launch_schnorr_item_prep(int qnw, const EcamdSchnorrItemArgs &a, hipStream_t s);
+hipError_t ecamd_launch_schnorr_item_fill(const EcamdSchnorrItemArgs &a, hipStream_t s);
+hipError_t ecamd_launch_schnorr_item_cmp(const EcamdSchnorrItemArgs &a, hipStream_t s);
+hipError_t ecamd_launch_schnorr_item_sign(int qnw, const EcamdSchnorrItemArgs &a, hipStream_t s);
+
 // nw: 32-bit words per field element; must be one of ecamd_supported_nw()
 int ecamd_nw_supported(int nw);
 hipError_t ecamd_upload_curve(int nw, int slot, const void *curvek, size_t bytes);

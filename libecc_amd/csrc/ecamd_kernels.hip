@@ -2859,3 +2859,5 @@ hipError_t ecamd_launch_prj_export(const EcamdPrjOutArgs &a, hipStream_t s)
 #include "ecamd_sigfam_kernels.h"
 // ECSDSA / ECOSDSA / ECKCDSA: k_hsig_prep / _fill / _cmp / _sign and their launchers
 #include "ecamd_sighash_kernels.h"
+// BIP0340 / ECFSDSA item by item: k_schnorr_item_prep / _cmp / _fill / _sign and their launchers
+#include "ecamd_schnorr_kernels.h"

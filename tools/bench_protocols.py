@@ -309,11 +309,155 @@ def sig_hashed_row(a, ctx, dev, stream, rng, B):
     ctx.close()
 
 
+def schnorr_row(a, ctx, dev, stream, rng, B):
+    """BIP0340 / ECFSDSA item by item (ec_schnorr_verify_batch_dev or ec_schnorr_sign_batch_dev, --alg, SHA-256, 24-byte messages),
+    inputs resident in HBM, beside ec_ecdsa_verify_batch_dev and ECSDSA (ec_sig_hashed_verify_batch_dev / _sign_batch_dev: the same two
+    multiplications, the same shared-inversion finish, the same hash) on the same curve in the same run, in alternating windows of
+    a.steps calls.  Signing is timed with the key derived on the device (BIP0340: a second fixed-base multiplication) and with the key
+    supplied.  Gates: every signature the device made is accepted, with the slots of the next item none is, and --ref-items random items
+    (and as many damaged ones) get the unmodified reference's verdict.  One GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload schnorr_verify / schnorr_sign measures one GPU: run it with --gpus 1, outside torch.distributed.run")
+    import oracles as O
+    import schnorr_ref as S
+    alg = {"bip0340": S.BIP0340, "ecfsdsa": S.ECFSDSA}[a.alg]
+    curve = a.curve
+    cv = ctx.curve(curve)
+    q = O.CURVES[curve]["q"]
+    ql, cl = O.qlen(curve), O.clen(curve)
+    ht, hl, mlen, hname = 2, 32, 24, "SHA256"
+    rl = S.r_len(alg, cl)
+    sl = rl + ql
+    raw = rng.integers(0, 256, size=(2, B, ql + 8), dtype=np.uint8)
+
+    def scal(rows):
+        return [(int.from_bytes(rows[i].tobytes(), "big") % (q - 1)) + 1 for i in range(B)]
+
+    def t(b):
+        return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+    privs, nonces = (b"".join(v.to_bytes(ql, "big") for v in vs) for vs in (scal(raw[0]), scal(raw[1])))
+    pubs, st = cv.scalar_mult(privs)
+    assert set(st) == {0}
+    msgs = rng.integers(0, 256, size=(B, mlen), dtype=np.uint8)
+    fl = S.fixed_len(alg, hname, cl)
+    stride = (4 + fl + mlen + 3) & ~3
+    slots = np.zeros((B, stride), dtype=np.uint8)
+    slots[:, 0:4] = np.frombuffer((fl + mlen).to_bytes(4, "little"), dtype=np.uint8)
+    if alg == S.BIP0340:
+        slots[:, 4:4 + 2 * hl] = np.frombuffer(S.tagged(hname, S.TAG_CHALLENGE), dtype=np.uint8)
+    slots[:, 4 + fl:4 + fl + mlen] = msgs
+    sigs, st = cv.schnorr_sign(alg, ht, privs, None, nonces, slots.tobytes(), stride)
+    assert set(st) == {0}
+    # verification takes the arrays of ec_schnorr_verify_msg_all_batch: the commitment field holds the signature's r
+    r_off = 4 + S.fixed_len(alg, hname, cl) - 2 * cl
+    vsl = slots.copy()
+    vsl[:, r_off:r_off + rl] = np.frombuffer(sigs, dtype=np.uint8).reshape(B, sl)[:, :rl]
+    # the yardsticks: ECDSA on random digests, ECSDSA on the same messages
+    dg = rng.integers(0, 256, size=hl * B, dtype=np.uint8).tobytes()
+    sigs_e, st = cv.ecdsa_sign(privs, nonces, dg, hl)
+    assert set(st) == {0}
+    hstride = (4 + 2 * cl + mlen + 3) & ~3
+    hsl = np.zeros((B, hstride), dtype=np.uint8)
+    hsl[:, 0] = 2 * cl + mlen
+    hsl[:, 4 + 2 * cl:4 + 2 * cl + mlen] = msgs
+    sigs_h, st = cv.sig_hashed_sign(3, ht, privs, nonces, hsl.tobytes(), hstride)
+    assert set(st) == {0}
+    d_pub, d_sig, d_in, d_vin, d_x, d_k, d_sig_e, d_dg, d_sig_h, d_hin = (t(b) for b in (pubs, sigs, slots.tobytes(), vsl.tobytes(), privs, nonces,
+                                                                                           sigs_e, dg, sigs_h, hsl.tobytes()))
+    d_res = torch.empty(B, dtype=torch.uint8, device=dev)
+    d_out, d_st = torch.empty(max(len(sigs), len(sigs_h)), dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    sign = a.workload == "schnorr_sign"
+
+    def ecdsa():
+        cv.ecdsa_verify_dev(B, d_pub.data_ptr(), d_sig_e.data_ptr(), d_dg.data_ptr(), hl, d_res.data_ptr(), stream.cuda_stream)
+
+    def ecsdsa():
+        if sign:
+            cv.sig_hashed_sign_dev(3, ht, B, d_x.data_ptr(), d_k.data_ptr(), d_hin.data_ptr(), hstride, d_out.data_ptr(), d_st.data_ptr(),
+                                   stream.cuda_stream)
+        else:
+            cv.sig_hashed_verify_dev(3, ht, B, d_pub.data_ptr(), d_sig_h.data_ptr(), d_hin.data_ptr(), hstride, d_res.data_ptr(), stream.cuda_stream)
+
+    def schnorr(with_key=False):
+        if sign:
+            cv.schnorr_sign_dev(alg, ht, B, d_x.data_ptr(), d_pub.data_ptr() if with_key else None, d_k.data_ptr(), d_in.data_ptr(), stride,
+                                d_out.data_ptr(), d_st.data_ptr(), stream.cuda_stream)
+        else:
+            cv.schnorr_verify_dev(alg, ht, B, d_pub.data_ptr(), 0, d_sig.data_ptr(), d_vin.data_ptr(), stride, d_res.data_ptr(), stream.cuda_stream)
+
+    def schnorr_key():
+        schnorr(True)
+    # ---- gates ----
+    cv.schnorr_verify_dev(alg, ht, B, d_pub.data_ptr(), 0, d_sig.data_ptr(), d_vin.data_ptr(), stride, d_res.data_ptr(), stream.cuda_stream)
+    torch.cuda.synchronize()
+    if bytes(d_res.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: a signature the device made was rejected")
+    d_rot = torch.roll(d_in, stride)   # the next item's message; the commitment field is the device's to fill
+    cv.schnorr_verify_dev(alg, ht, B, d_pub.data_ptr(), 0, d_sig.data_ptr(), d_rot.data_ptr(), stride, d_res.data_ptr(), stream.cuda_stream)
+    torch.cuda.synchronize()
+    if bytes(d_res.cpu().numpy()) != b"\1" * B:
+        raise SystemExit("PARITY FAILURE: a signature was accepted for another item's message")
+    for wk in (False, True):
+        schnorr(wk)
+        torch.cuda.synchronize()
+        if sign and (bytes(d_out.cpu().numpy())[:len(sigs)] != sigs or bytes(d_st.cpu().numpy()) != bytes(B)):
+            raise SystemExit("PARITY FAILURE: the device-pointer form signs differently")
+    gate = "all 2^%d device-made signatures accepted, none for its neighbour's message" % a.batch_log2
+    if O.have_ref() and a.ref_items > 0:
+        from concurrent.futures import ThreadPoolExecutor
+        idx = [int(i) for i in np.sort(np.random.default_rng(2).choice(B, size=min(B, a.ref_items), replace=False))]
+
+        def one(i):
+            key, sig, msg = pubs[2 * cl * i:2 * cl * (i + 1)], sigs[sl * i:sl * (i + 1)], msgs[i].tobytes()
+            bad = sig[:-1] + bytes([sig[-1] ^ 1])
+            return S.ref_verify(curve, alg, hname, key, S.AFF, sig, msg), S.ref_verify(curve, alg, hname, key, S.AFF, bad, msg)
+        with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
+            got = list(ex.map(one, idx))
+        if got != [(0, -1)] * len(idx):
+            raise SystemExit("PARITY FAILURE: the reference disagrees on %d of %d sampled items" % (sum(g != (0, -1) for g in got), len(idx)))
+        bs = np.frombuffer(sigs, dtype=np.uint8).reshape(B, sl).copy()
+        bs[idx, sl - 1] ^= 1
+        cv.schnorr_verify_dev(alg, ht, B, d_pub.data_ptr(), 0, t(bs.tobytes()).data_ptr(), d_vin.data_ptr(), stride, d_res.data_ptr(), stream.cuda_stream)
+        torch.cuda.synchronize()
+        exp = np.zeros(B, dtype=np.uint8)
+        exp[idx] = 1
+        if bytes(d_res.cpu().numpy()) != exp.tobytes():
+            raise SystemExit("PARITY FAILURE: damaged items are not the ones rejected")
+        gate += "; %d items and their damaged twins as the reference decides" % len(idx)
+    # ---- timing: alternating windows ----
+    fns = [ecdsa, ecsdsa, schnorr] + ([schnorr_key] if sign else [])
+    for _ in range(a.warmup):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    times = [[] for _ in fns]
+    for _ in range(3):
+        for fn, acc in zip(fns, times):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            acc.append((time.perf_counter() - t0) / a.steps)
+    med = [float(np.median(x)) for x in times]
+    kind = "signatures" if sign else "verifications"
+    row = {"metric": "%s %s/sec (%s, SHA-256, batch=2^%d, device-resident)" % (a.alg.upper(), kind, curve.lower(), a.batch_log2),
+           "value": B / med[2], "unit": kind + "/s", "schnorr_ms": [1e3 * x for x in times[2]],
+           "ecdsa_verify_same_run": {"value": B / med[0], "unit": "verifications/s", "ms": [1e3 * x for x in times[0]]},
+           "ecsdsa_same_run": {"value": B / med[1], "unit": kind + "/s", "ms": [1e3 * x for x in times[1]]},
+           "schnorr_over_ecsdsa": med[1] / med[2], "gate": gate,
+           "config": {"workload": a.workload, "alg": a.alg, "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}
+    if sign:
+        row["key_supplied"] = {"value": B / med[3], "unit": "signatures/s", "ms": [1e3 * x for x in times[3]]}
+    print(json.dumps(row))
+    cv.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
-    ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa"],
-                    help="sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa")
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa"],
+                    help="sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -364,6 +508,8 @@ def main():
         return sig_family_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("sig_hashed_verify", "sig_hashed_sign"):
         return sig_hashed_row(a, ctx, dev, stream, rng, B)
+    if a.workload in ("schnorr_verify", "schnorr_sign"):
+        return schnorr_row(a, ctx, dev, stream, rng, B)
     if a.workload == "ecdsa_verify":
         curve = a.curve
         cv = ctx.curve(curve)
