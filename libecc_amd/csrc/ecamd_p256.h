@@ -300,6 +300,40 @@ template <int NW, int WB> U29_FN bool odd_digit(u32 *e, u32 &idx)
 	return neg;
 }
 
+// ---- the same recoding in 64 digits of 4 bits, for scalars below 2^256 (at most 32 bytes) ----
+// k + q costs a 257th bit, hence a 65th digit.  Instead the odd k' stays below 2^256 and carries a sign:
+//   k odd: k' = k, +;   k even, k < q: k' = q - k, -;   k even, k > q: k' = k - q, +      (k = q is odd)
+// so that [k]P = +-[k']P.  Branch-free (the masked mode runs the same code): d = k - q with borrow b, d negated when b is set.
+// E = (k' - 1) / 2 + 2^255 fills the eight words of e exactly, so it is left-aligned as it stands: odd_digit<8, 4> reads its 64
+// windows, top first, and the top one is >= 8 (a positive digit).  Returns the sign (true: negative); the caller flips the
+// `neg` of every digit with it, which negates the whole sum.
+U29_FN bool recode_odd64(u32 *e, const u32 *kw)
+{
+	const u32 even = (kw[0] & 1u) - 1u;  // all ones when k is even
+	u32 d[8];
+	u32 borrow = 0;
+#pragma unroll
+	for (int w = 0; w < 8; w++) {
+		const u64 x = (u64)kw[w] - QOrder::W[w] - borrow;
+		d[w] = (u32)x;
+		borrow = (u32)(x >> 63);
+	}
+	const u32 below = 0u - borrow;  // all ones when k < q
+	u64 c = borrow;
+#pragma unroll
+	for (int w = 0; w < 8; w++) {
+		c += (u64)(d[w] ^ below);  // -d = ~d + 1
+		d[w] = ((u32)c & even) | (kw[w] & ~even);
+		c >>= 32;
+	}
+#pragma unroll
+	for (int w = 0; w < 7; w++) {
+		e[w] = (d[w] >> 1) | (d[w + 1] << 31);
+	}
+	e[7] = (d[7] >> 1) | 0x80000000u;
+	return (even & below) != 0u;
+}
+
 U29_FN TabEnt to_tab(const Jac &P)
 {
 	TabEnt T;

@@ -562,15 +562,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P256_WAVES, 
 
 // ------------------------------------------------------------------------------------------
 // A2/B2/C2. the per-item-table path: regular odd-digit windows of ODD_WB = 4 bits over a co-Z table
-//   scalar  k' = k or k + q (odd), t windows, every digit odd in [-15, 15] (recode_odd, ecamd_p256.h); k + q is 256 bits, so
-//           a scalar of fewer than 32 bytes still takes t = 65 windows (the signed window took 2 slen);
+//   scalar  up to 32 bytes (KW = 8): k' = k, q - k or k - q (odd, below 2^256) with a sign, 64 digits, every digit odd in
+//           [-15, 15] (recode_odd64, ecamd_p256.h); the sign flips every digit and the start entry's y, no field operation.  A
+//           shorter scalar takes 64 digits too (q - k is 256 bits; the signed window took 2 slen).  Blinded scalars (KW = 17):
+//           k' = k or k + q, t = ceil((8 slen + 1) / 4) digits (recode_odd);
 //   table   [1, 3, ..., 15]P: dblu, then one co-Z addition (zaddu) per entry -- no exceptional pair possible;
 //   affine  Montgomery's trick over the LAST Z of AFF_K items per lane, then entry by entry down the chain's Z ratios;
 //   loop    top digit (positive) -> accumulator, then t - 1 windows of 4 doublings + 1 mixed addition.  No digit is zero, so
-//           there is no infinity flag and nothing to select: every addition checks its exceptional pair (hz).  For k' < 2q
-//           (scalars of up to 32 bytes) the partial sums before the last window lie in [1, q / 8), so only the last addition can
-//           meet one: when k' = 0 or 2 d0 mod q for the last digit d0 -- k = q - 2 (k' = q - 2, d0 = -1) is such a scalar below
-//           q, besides k = 0 and scalars of q or more; longer (blinded) scalars can meet one at any window.  Such an item goes to
+//           there is no infinity flag and nothing to select: every addition checks its exceptional pair (hz).  For k' < 2^256
+//           (scalars of up to 32 bytes) the partial sum before window j is below 2^252 / 16^j < q, so only the last addition can
+//           meet one: when k' = 0 or 2 d0 mod q for the last digit d0 -- k = 0 and k = q (k' = q), k = 2 and k = q - 2
+//           (k' = q - 2, d0 = -1), nothing else; longer (blinded) scalars can meet one at any window.  Such an item goes to
 //           the complete kernel (ECAMD_STATUS_REDO), in the masked mode too, as on the signed-window path.
 //   staging per block of 64 items, quad-major / lane-minor: entry e = 1..NE-1 at quads 7 (e - 1) .. 7 e - 1 (X 0-8, Y 9-17,
 //           r 18-26, 27), the last Z at ODD_ZQ .. + 2 and its prefix product at ODD_ZQ + 3 .. + 5
@@ -579,7 +581,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P256_WAVES, 
 #ifndef P256_ODD_WINDOWS
 #define P256_ODD_WINDOWS 1
 #endif
+// P256_REC64=0 keeps recode_odd's 65 digits for scalars of at most 32 bytes too (A/B comparisons).
+#ifndef P256_REC64
+#define P256_REC64 1
+#endif
 #define ODD_WB 4                                    /* window bits */
+static_assert(!P256_REC64 || ODD_WB == 4, "recode_odd64 makes 4-bit windows");
 #define ODD_NE (1 << (ODD_WB - 1))                  /* table entries */
 #define ODD_TAB_ITEM_WORDS (ODD_NE * TAB_ENT_WORDS)
 #define ODD_ENT_QUADS 7
@@ -723,8 +730,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P256_WAVES, 
 	}
 	const u32 *tabi = A.tbl + (size_t)i * ODD_TAB_ITEM_WORDS;  // this item's affine table
 	const int slen = (int)A.slen;
-	u32 e[KW + 1];
+	constexpr bool REC64 = KW == 8 && P256_REC64;  // 64 signed-sum digits in eight words (recode_odd64)
+	constexpr int EW = REC64 ? 8 : KW + 1;
+	u32 e[EW];
 	int nwin;
+	bool sign = false;
 	{
 		u32 kw[KW];
 		const u8 *sc = A.scalars + (size_t)i * A.sstride;
@@ -744,12 +754,17 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P256_WAVES, 
 				kw[w] = x;
 			}
 		}
-		nwin = recode_odd<KW, ODD_WB>(e, kw, slen);
+		if constexpr (REC64) {
+			sign = recode_odd64(e, kw);
+			nwin = 64;
+		} else {
+			nwin = recode_odd<KW, ODD_WB>(e, kw, slen);
+		}
 	}
 	Jac acc;
 	{
 		u32 idx;
-		(void)odd_digit<KW + 1, ODD_WB>(e, idx);  // the top digit is positive
+		(void)odd_digit<EW, ODD_WB>(e, idx);  // the top digit is positive
 		Fcanon px, py;
 		if (MASKED) {
 			tab_load_masked<ODD_NE>(tabi, idx, px, py);
@@ -757,7 +772,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P256_WAVES, 
 			tab_load(tabi, idx, px, py);
 		}
 		acc.X = weaken<FX>(px);
-		acc.Y = weaken<FY>(py);
+		if constexpr (REC64) {
+			acc.Y = weaken<FY>(carry(sel(sign, neg_aff(py), weaken<FYaff>(py))));
+		} else {
+			acc.Y = weaken<FY>(py);
+		}
 		acc.Z = weaken<FZ>(constant<Fcanon>(K::ONE));
 	}
 	bool bad = false, hz;
@@ -768,7 +787,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(P256_WAVES, 
 			acc = dbl(acc);
 		}
 		u32 idx;
-		const bool neg = odd_digit<KW + 1, ODD_WB>(e, idx);
+		const bool neg = odd_digit<EW, ODD_WB>(e, idx) != sign;
 		Fcanon tx, tyc;
 		if (MASKED) {
 			tab_load_masked<ODD_NE>(tabi, idx, tx, tyc);
