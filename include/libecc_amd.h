@@ -380,6 +380,38 @@ int ec_schnorr_verify_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, i
 int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *privs,
 			  const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
 			  uint8_t *status);
+/* BIGN and DBIGN (STB 34.101.45; sig/bign_common.c): the scheme that hashes its commitment with belt-hash (STB 34.101.31),
+ * whatever hash the message had.  alg: libecc's ec_alg_type numbers 18 / 19 -- the two verify and sign identically here; they differ
+ * in where the nonce comes from, and DBIGN's generator (__bign_determinitic_nonce) STAYS WITH THE CALLER, as RFC 6979 does for ECDSA.
+ * Any other alg is a call-level error (-1, ecamd_last_error()).
+ *   lengths  qlen = ceil(|q| / 8), l = qlen / 2 (integer division).  sigs: n x (l + qlen), s0 (l bytes) then s1 (qlen bytes),
+ *            both LITTLE-ENDIAN, as the reference writes them (the digest read as a number and W's coordinates in the hash input
+ *            are little-endian too).  privs and nonces are n x qlen BIG-ENDIAN, like every other signing call here.
+ *   inputs   hash_type 0: n x stride digests H(m), stride = the digest length in 1 .. 128, as for ec_sig_verify_batch (the caller
+ *            hashed).  hash_type 1 .. 4 (SHA-224 / 256 / 384 / 512) or ECAMD_HASH_BELT (16): message slots in the format of
+ *            ec_ecdsa_verify_msg_batch_fmt -- a little-endian u32 length, then the message; stride a multiple of 4 in 4 .. 4096 --
+ *            and the device computes H(m) first.  bign256v1 with belt-hash is the standard's own configuration.  A slot whose
+ *            length does not fit the stride is result / status 1.  Any other hash_type is a call-level error.
+ *   oid      the OID octets of the message's hash (NOT libecc's adata framing oid_len || t_len || oid || t), the same for all items,
+ *            a HOST pointer in the _dev forms too; oid_len in 0 .. 64, otherwise (or oid NULL with oid_len > 0) a call-level error.
+ * Per item, verification is ec_pub_key_import_from_aff_buf + ec_verify with result[i] = 0 / 1 for 0 / -1, for every input
+ * (sig/bign_common.c:742-962): s1 < q (s0 has no range check); hbar = the whole digest, little-endian, mod q; u = s1 + hbar (0 is
+ * legal), v = s0 + 2^(8l); W = [u]G + [v]Y not at infinity; t = the first min(l, 32) bytes of
+ * belt-hash(oid || first 2l bytes of LE(W.x) || LE(W.y) || digest), zero-padded to l bytes; accept iff t = s0 over all l bytes (on a
+ * 521-bit order l = 33: byte 32 of an acceptable s0 is 0).  On cofactor curves the key import's subgroup check applies.
+ * Signing is _ec_sign with the nonce k supplied by the caller (sig/bign_common.c:468-690): x < q (x = 0 signs), k in [1, q - 1],
+ * W = [k]G, s0 = t as above, s1 = (k - hbar - (s0 + 2^(8l)) x) mod q.  No restart, no test of s1.  status[i] = 1 with zero signature
+ * bytes otherwise.  Verification multiplies by public values only; signing's [k]G honours ecamd_ctx_set_secret_scalars (belt-hash's
+ * inputs are public: W is recomputed by every verifier), and ecamd_ctx_wipe_scratch covers the staged W, slots and digests.
+ * Chunking by ecamd_ctx_set_max_chunk, n = 0, NULL arguments and a handle of another context behave as for ec_sig_hashed_*. */
+#define ECAMD_SIG_BIGN 18
+#define ECAMD_SIG_DBIGN 19
+#define ECAMD_HASH_BELT 16
+int ec_bign_verify_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys_aff,
+			 const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *result);
+int ec_bign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+		       const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *sigs,
+		       uint8_t *status);
 /* nn_get_random_mod (nn/nn_rand.c:92-150) given its random bytes.  The reference draws 2 * qlen bytes with get_random straight into the
  * limb array of an nn (they read as a little-endian integer on the little-endian hosts libecc and this library run on), reduces modulo
  * q - 1 and adds one.  raw: n x 2*qlen bytes from the caller's own randomness source; out: n x qlen big-endian, each in [1, q - 1].  The
@@ -648,6 +680,15 @@ int ec_sig_hashed_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int
 int ec_sig_hashed_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_privs,
 				 const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs, void *d_status,
 				 void *hip_stream);
+/* ec_bign_verify_batch / ec_bign_sign_batch with device pointers (oid stays a host pointer): enqueue only.  Scratch: besides what a
+ * verification or signing call of the curve takes, per item of a chunk belt-hash's slot (at most 4 + 64 + 66 + 128 bytes), its
+ * 32-byte digest and, for hash_type != 0, the digest of the message.  Message slots are read where they lie: no copy. */
+int ec_bign_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_pubkeys_aff,
+			     const void *d_sigs, const void *d_inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, void *d_result,
+			     void *hip_stream);
+int ec_bign_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_privs,
+			   const void *d_nonces, const void *d_inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, void *d_sigs,
+			   void *d_status, void *hip_stream);
 /* ec_schnorr_verify_batch / ec_schnorr_sign_batch with device pointers: enqueue only.  Scratch: besides what a verification or signing
  * call of the curve takes, a device-to-device copy of the slots of one chunk (min(n, max_chunk) x stride bytes: choose the stride to fit
  * the longest message, or lower ecamd_ctx_set_max_chunk).  d_pubkeys_aff may be NULL, as pubkeys_aff. */

@@ -151,7 +151,9 @@ int ecccdh_derive_secret_batch(const ec_priv_key *const *our_priv_keys, const u8
  * sig/ecdsa_common.c:318-586) and the five EdDSA variants (_eddsa_sign, sig/eddsa.c:1554).  ON THE CPU: every other algorithm of
  * sig/sig_algs_internal.h's table -- ECKCDSA, ECSDSA, ECOSDSA, ECFSDSA, ECGDSA, ECRDSA, SM2, BIGN, DBIGN, BIP0340 -- is signed item by
  * item by libecc's own _ec_sign on the pool threads (cpu_sign_items): the call parallelises them over the host cores and nothing
- * more; they are not part of the accelerated path (the hot path is ECDSA / EdDSA / ECDH).  The host side of
+ * more; they are not part of the accelerated path (the hot path is ECDSA / EdDSA / ECDH).  (The C ABI of
+ * include/libecc_amd.h serves them on the GPU -- BIGN and DBIGN by ec_bign_sign_batch / ec_bign_verify_batch -- but this typed
+ * layer is not rerouted to those calls.)  The host side of
  * the GPU algorithms also uses the application's libecc for what is per call or rare: nn_mod of an over-long private scalar,
  * nn_modinv_fermat for ECKCDSA-type key rules, the HMAC of RFC 6979, the blinding product m + b #E of prj_pt_mul_blind_batch.
  *   rand: as for _ec_sign -- NULL = libecc's nn_get_random_mod (its steps restated around a serialised get_random, see

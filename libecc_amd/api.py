@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "ec_sig_verify_batch", "ec_sig_verify_batch_dev", "ec_sig_sign_batch", "ec_sig_sign_batch_dev",
     "ec_sig_hashed_verify_batch", "ec_sig_hashed_verify_batch_dev", "ec_sig_hashed_sign_batch", "ec_sig_hashed_sign_batch_dev",
     "ec_schnorr_verify_batch", "ec_schnorr_verify_batch_dev", "ec_schnorr_sign_batch", "ec_schnorr_sign_batch_dev",
+    "ec_bign_verify_batch", "ec_bign_verify_batch_dev", "ec_bign_sign_batch", "ec_bign_sign_batch_dev",
 ]
 
 # libecc's ec_alg_type numbers of the schemes ec_sig_verify_batch / ec_sig_sign_batch serve (ECAMD_SIG_* in include/libecc_amd.h)
@@ -40,6 +41,10 @@ SIG_ECGDSA, SIG_ECRDSA, SIG_SM2 = 6, 7, 8
 SIG_ECKCDSA, SIG_ECSDSA, SIG_ECOSDSA = 2, 3, 4
 # ... and of the two Schnorr-type schemes with a point commitment, served item by item by ec_schnorr_verify_batch / ec_schnorr_sign_batch
 SIG_ECFSDSA, SIG_BIP0340 = 5, 20
+# ... and of BIGN / DBIGN (STB 34.101.45), served by ec_bign_verify_batch / ec_bign_sign_batch; HASH_BELT: libecc's hash_alg_type
+# number of belt-hash, which those calls (and only those) compute on the device beside SHA-2
+SIG_BIGN, SIG_DBIGN = 18, 19
+HASH_BELT = 16
 HASH_SIZES = {1: 28, 2: 32, 3: 48, 4: 64}          # libecc's hash_alg_type numbers of SHA-224 / 256 / 384 / 512
 
 
@@ -124,6 +129,10 @@ def load_library():
         L.ec_sig_hashed_sign_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u8p]
         L.ec_sig_hashed_verify_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, vp, vp]
         L.ec_sig_hashed_sign_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, vp, vp, vp]
+        L.ec_bign_verify_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u32, u8p]
+        L.ec_bign_sign_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u32, u8p, u8p]
+        L.ec_bign_verify_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, u8p, u32, vp, vp]
+        L.ec_bign_sign_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, u8p, u32, vp, vp, vp]
         L.ec_schnorr_verify_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, C.c_int, u8p, u8p, u32, u8p]
         L.ec_schnorr_sign_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u8p, u32, u8p, u8p]
         L.ec_schnorr_verify_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, C.c_int, vp, vp, u32, vp, vp]
@@ -424,6 +433,31 @@ class Curve:
              "ec_sig_hashed_sign_batch")
         return sigs.raw[:sl * n], st.raw[:n]
 
+    def bign_siglen(self):
+        """bytes of a BIGN signature: s0 (qlen // 2) then s1 (qlen), both little-endian"""
+        return self.qlen // 2 + self.qlen
+
+    def bign_verify(self, alg, hash_type, pubs, sigs, inputs, stride, oid):
+        """BIGN / DBIGN verification (alg: SIG_BIGN, SIG_DBIGN): 0 accept / 1 reject per item.  hash_type 0: inputs are the digests
+        H(m), stride their length; hash_type 1 .. 4 or HASH_BELT: inputs are message slots of `stride` bytes, hashed on the device.
+        oid: the OID octets of the message's hash (at most 64)"""
+        n = len(pubs) // (2 * self.clen)
+        res = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_bign_verify_batch(self.ctx.h, self.h, alg, hash_type, n, pubs, sigs, inputs, stride, oid, len(oid), res),
+             "ec_bign_verify_batch")
+        return res.raw[:n]
+
+    def bign_sign(self, alg, hash_type, privs, nonces, inputs, stride, oid):
+        """BIGN / DBIGN signatures (s0 || s1, little-endian) with caller-supplied nonces (big-endian, like privs), and a status byte
+        per item"""
+        n = len(privs) // self.qlen
+        sl = self.bign_siglen()
+        sigs = C.create_string_buffer(max(1, sl * n))
+        st = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_bign_sign_batch(self.ctx.h, self.h, alg, hash_type, n, privs, nonces, inputs, stride, oid, len(oid), sigs, st),
+             "ec_bign_sign_batch")
+        return sigs.raw[:sl * n], st.raw[:n]
+
     def schnorr_rlen(self, alg):
         """bytes of the commitment in a BIP0340 (R.x) / ECFSDSA (W.x || W.y) signature"""
         return self.clen if alg == SIG_BIP0340 else 2 * self.clen
@@ -613,6 +647,14 @@ class Curve:
     def sig_hashed_verify_dev(self, alg, hash_type, n, d_pubs, d_sigs, d_inputs, stride, d_result, stream=None):
         _chk(self.L, self.L.ec_sig_hashed_verify_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_pubs, d_sigs, d_inputs, stride, d_result,
                                                             stream), "ec_sig_hashed_verify_batch_dev")
+
+    def bign_verify_dev(self, alg, hash_type, n, d_pubs, d_sigs, d_inputs, stride, oid, d_result, stream=None):
+        _chk(self.L, self.L.ec_bign_verify_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_pubs, d_sigs, d_inputs, stride, oid, len(oid),
+                                                      d_result, stream), "ec_bign_verify_batch_dev")
+
+    def bign_sign_dev(self, alg, hash_type, n, d_privs, d_nonces, d_inputs, stride, oid, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_bign_sign_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_privs, d_nonces, d_inputs, stride, oid, len(oid),
+                                                    d_sigs, d_status, stream), "ec_bign_sign_batch_dev")
 
     def sig_hashed_sign_dev(self, alg, hash_type, n, d_privs, d_nonces, d_inputs, stride, d_sigs, d_status, stream=None):
         _chk(self.L, self.L.ec_sig_hashed_sign_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_privs, d_nonces, d_inputs, stride, d_sigs,

@@ -17,7 +17,8 @@ DEPS = ["ecamd_madchain.h", "ecamd_field.h", "ecamd_point.h", "ecamd_u29.h", "ec
         "ecamd_sigfam.h", "ecamd_sigfam_kernels.h", "ecamd_sighash.h", "ecamd_sighash_kernels.h",
         "ecamd_curve_table.inc"]
 # headers that only some translation units include
-SOURCE_DEPS = {"ecamd_kernels.hip": ["ecamd_schnorr.h", "ecamd_schnorr_kernels.h"], "ecamd_host.cpp": ["ecamd_schnorr.h"]}
+SOURCE_DEPS = {"ecamd_kernels.hip": ["ecamd_schnorr.h", "ecamd_schnorr_kernels.h", "ecamd_bign.h", "ecamd_bign_kernels.h"],
+               "ecamd_host.cpp": ["ecamd_schnorr.h", "ecamd_bign.h"], "ecamd_hash.hip": ["ecamd_belt.h"]}
 # the public header only matters to the host-side translation units (the kernels see ecamd_internal.h)
 HOST_DEPS = [os.path.join("..", "..", "include", "libecc_amd.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "ecamd_internal.h"
+#include "ecamd_belt.h"
 
 typedef uint32_t u32;
 typedef uint64_t u64;
@@ -206,6 +207,55 @@ hipError_t ecamd_launch_sha2_slots(int hash_type, const uint8_t *slots, uint32_t
 	case 4: hipLaunchKernelGGL(k_sha2_slots<512>, grid, block, 0, s, slots, stride, n, out, out_stride); break;
 	default: return hipErrorInvalidValue;
 	}
+	return hipGetLastError();
+}
+
+// ---- belt-hash (STB 34.101.31) of the same slots, for BIGN (ecamd_belt.h): one message per lane.  The substitution table is the one
+//      per-lane gather of this kernel; each block stages its 256 octets into LDS once (why octets: ecamd_belt.h).  Everything hashed
+//      here is public, so the look-ups are the same in secret-scalar mode. ----
+__constant__ __attribute__((aligned(16))) u8 c_belt_h[256] = {ECAMD_BELT_H};   // read as dwords by the staging
+
+__global__ __launch_bounds__(64) void k_belt_slots(const u8 *slots, u32 stride, u32 n, u8 *out, u32 out_stride)
+{
+#if defined(__HIPCC__)
+	__shared__ __attribute__((aligned(16))) u8 sH[256];
+	((u32 *)sH)[threadIdx.x] = ((const u32 *)c_belt_h)[threadIdx.x];   // 64 threads x 4 octets
+	__syncthreads();
+	const u8 *H = sH;
+#else
+	// a host build: the tests compile this whole file against a stand-in for the runtime that has neither __shared__ nor a barrier
+	// (tests/hash_host_shim.cpp for the SHA-2 kernels, tests/belt_kernel_host_shim.cpp for this one), so there the table is read
+	// where it lies.  The staging above runs on the device alone; tests/test_gpu_bign.py covers it.
+	const u8 *H = c_belt_h;
+#endif
+	const u32 i = blockIdx.x * 64 + threadIdx.x;
+	if (i >= n) {
+		return;
+	}
+	const u32 *slot = (const u32 *)(slots + (size_t)i * stride);
+	u32 len = slot[0];
+	len = len > stride - 4 ? stride - 4 : len;      // stay inside the slot
+	u32 dg[8];
+	ecbelt::hash_words(H, slot + 1, len, dg);
+	u8 *dst = out + (size_t)i * out_stride;
+#pragma unroll
+	for (int k = 0; k < 8; k++) {
+		dst[4 * k] = (u8)dg[k];
+		dst[4 * k + 1] = (u8)(dg[k] >> 8);
+		dst[4 * k + 2] = (u8)(dg[k] >> 16);
+		dst[4 * k + 3] = (u8)(dg[k] >> 24);
+	}
+}
+
+hipError_t ecamd_launch_belt_slots(const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s)
+{
+	if (n == 0) {
+		return hipSuccess;
+	}
+	if (stride < 4 || (stride & 3u) || out_stride < 32) {
+		return hipErrorInvalidValue;
+	}
+	hipLaunchKernelGGL(k_belt_slots, dim3((n + 63) / 64), dim3(64), 0, s, slots, stride, n, out, out_stride);
 	return hipGetLastError();
 }
 

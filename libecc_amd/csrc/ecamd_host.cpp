@@ -23,6 +23,7 @@
 #include "ecamd_internal.h"
 #include "ecamd_sighash.h"
 #include "ecamd_schnorr.h"
+#include "ecamd_bign.h"
 
 // ------------------------------------------------------------------------------------------
 // error reporting
@@ -6583,6 +6584,271 @@ extern "C" int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, i
 	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
 					       hipStream_t s, const std::function<int()> &) {
 		return hsig_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], op[4], s);
+	});
+}
+
+// ------------------------------------------------------------------------------------------
+// batched BIGN / DBIGN (include/libecc_amd.h: ec_bign_*): the scheme that hashes its commitment with belt-hash.  Per chunk of at
+// most max_chunk items, verification is
+//   k_sha2_slots / k_belt_slots   hash_type != 0 only: the digests of the caller's message slots
+//   k_bign_prep       s1 < q, hbar, the multipliers u (of G) and v (of Y), the flag byte
+//   A = [u]G, B = [v]Y one fixed-base and one variable-base pass (public scalars); on a cofactor curve [q]Y too, as ECDSA verification does
+//   k_recover_fin     W' = A + B as affine bytes, one shared inversion per eight items (its second sum A - B is not used)
+//   k_recover_redo    the items with A or B at infinity (u = 0) or x_A = x_B, on the complete formulas
+//   k_bign_fill       belt-hash's slot OID || <LE(W'x) || LE(W'y)>_2l || digest
+//   k_belt_slots      t
+//   k_bign_cmp        t against s0
+// and signing is [k]G (secret-scalar mode as the context says), k_bign_fill, k_belt_slots, k_bign_sign.
+// stage: as hsig_verify_dev_locked up to 15; 16 belt-hash's slots, 17 the digests of the messages, 18 the BelT digests.  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static int bign_message_digests(ecamd_ctx *ctx, int hash_type, uint32_t m, const uint8_t *d_in, uint32_t stride, EcamdBignArgs &B, hipStream_t s)
+{
+	if (hash_type == 0) {
+		B.dg = d_in;          // the caller hashed: stride is the digest length
+		B.mslots = nullptr;
+		return 0;
+	}
+	uint8_t **S = ctx->stage;
+	if (hash_type == ecbign::HASH_BELT) {
+		HIPCHK(ecamd_launch_belt_slots(d_in, stride, m, S[17], B.hsize, s));
+	} else {
+		HIPCHK(ecamd_launch_sha2_slots(hash_type, d_in, stride, m, S[17], B.hsize, s));
+	}
+	B.dg = S[17];
+	B.mslots = d_in;
+	B.mstride = stride;
+	return 0;
+}
+
+static void bign_args(EcamdBignArgs &B, const ecamd_curve *cv, int hash_type, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint32_t m)
+{
+	memset(&B, 0, sizeof(B));
+	B.n = m;
+	B.qlen = (uint32_t)cv->qlen;
+	B.clen = (uint32_t)cv->clen;
+	B.hsize = hash_type == 0 ? stride : (uint32_t)ecbign::hash_size(hash_type);
+	B.oid_len = oid_len;
+	B.bstride = ecbign::belt_stride(oid_len, cv->qlen, B.hsize);
+	B.qslot = cv->qslot;
+	if (oid_len) {
+		memcpy(B.oid, oid, oid_len);
+	}
+}
+
+static int bign_stage_belt(ecamd_ctx *ctx, EcamdBignArgs &B, hipStream_t s)
+{
+	uint8_t **S = ctx->stage;
+	B.slots = S[16];
+	B.bt = S[18];
+	HIPCHK(ecamd_launch_bign_fill(B, s));
+	HIPCHK(ecamd_launch_belt_slots(S[16], B.bstride, B.n, S[18], ecbign::DIGEST_BT, s));
+	return 0;
+}
+
+static int bign_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_pub, const uint8_t *d_sig,
+				  const uint8_t *d_in, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *d_res, hipStream_t s)
+{
+	PublicScalars pub_scope(ctx);   // u, v and the group order are public
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen, siglen = (size_t)ecbign::sig_len(cv->qlen);
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	EcamdBignArgs B;
+	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
+	const size_t need[19] = {0, 0, 0, chunk * ql, chunk * ql, chunk * plen, chunk * plen, chunk, chunk, chunk, chunk, chunk * plen + 256,
+				 chunk * plen, chunk * plen, chunk, chunk, (size_t)chunk * B.bstride, hash_type ? (size_t)chunk * B.hsize : 0,
+				 (size_t)chunk * ecbign::DIGEST_BT};
+	for (int i = 3; i < 19; i++) {
+		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
+			return -1;
+		}
+	}
+	uint8_t **S = ctx->stage;
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		const uint8_t *pub = d_pub + (size_t)off * plen;
+		B.n = m;
+		B.sigs = d_sig + (size_t)off * siglen;
+		B.u = S[3];
+		B.v = S[4];
+		B.flags = S[9];
+		B.W = S[12];
+		B.stW = S[14];
+		B.out = d_res + off;
+		if (bign_message_digests(ctx, hash_type, m, d_in + (size_t)off * stride, stride, B, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_bign_prep(cv->qnw, B, s));
+		if (smul_dev_locked(ctx, cv, m, S[3], (uint32_t)ql, nullptr, S[5], S[7], s) ||
+		    smul_dev_locked(ctx, cv, m, S[4], (uint32_t)ql, pub, S[6], S[8], s)) {
+			return -1;
+		}
+		if (big_cmp(cv->order, cv->q) != 0) {
+			// cofactor != 1: ec_pub_key_import_from_aff_buf also requires [q]Y == infinity (sig/ec_key.c:199-205), as in hsig_verify_dev_locked
+			if (smul_dev_locked(ctx, cv, m, cv->d_gen + plen, (uint32_t)ql, pub, S[11], S[10], s, 0)) {
+				return -1;
+			}
+			HIPCHK(ecamd_launch_status_require(S[8], S[10], 2, m, s));
+		}
+		EcamdRecoverFinArgs F;
+		F.A = S[5];
+		F.stA = S[7];
+		F.B = S[6];
+		F.stB = S[8];
+		F.flags = S[9];
+		F.yst = S[9];
+		F.out1 = S[12];
+		F.out2 = S[13];   // sinks, as in hsig_verify_dev_locked
+		F.st1 = S[14];
+		F.st2 = S[15];
+		F.n = m;
+		F.clen = (uint32_t)cl;
+		F.slot = cv->slot;
+		HIPCHK(ecamd_launch_recover_fin(cv->nw, F, s));
+		HIPCHK(ecamd_launch_recover_redo(cv->nw, F, s));
+		if (bign_stage_belt(ctx, B, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_bign_cmp(B, s));
+	}
+	return 0;
+}
+
+static int bign_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
+				const uint8_t *d_in, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *d_sigs, uint8_t *d_status,
+				hipStream_t s)
+{
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen, siglen = (size_t)ecbign::sig_len(cv->qlen);
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	EcamdBignArgs B;
+	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
+	if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], chunk * plen) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], chunk) ||
+	    ensure(&ctx->stage[16], &ctx->stage_bytes[16], (size_t)chunk * B.bstride) ||
+	    ensure(&ctx->stage[17], &ctx->stage_bytes[17], hash_type ? (size_t)chunk * B.hsize : 0) ||
+	    ensure(&ctx->stage[18], &ctx->stage_bytes[18], (size_t)chunk * ecbign::DIGEST_BT)) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[3], S[4], s)) {   // W = [k]G
+			return -1;
+		}
+		B.n = m;
+		B.privs = d_privs + off * ql;
+		B.nonces = d_nonces + off * ql;
+		B.W = S[3];
+		B.stW = S[4];
+		B.out = d_sigs + (size_t)off * siglen;
+		B.status = d_status + off;
+		B.sign = 1;
+		if (bign_message_digests(ctx, hash_type, m, d_in + (size_t)off * stride, stride, B, s) || bign_stage_belt(ctx, B, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_bign_sign(cv->qnw, B, s));
+	}
+	return 0;
+}
+
+static int bign_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a, const void *b,
+			const void *c, const void *d, const void *e, uint32_t stride, const uint8_t *oid, uint32_t oid_len)
+{
+	if (!ecbign::alg_known(alg)) {
+		return fail(std::string(fn) + ": alg must be ECAMD_SIG_BIGN or ECAMD_SIG_DBIGN");
+	}
+	if (hash_type != 0 && ecbign::hash_size(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 0 (inputs are digests), 1 .. 4 (SHA-224 / 256 / 384 / 512) or ECAMD_HASH_BELT");
+	}
+	if (oid_len > (uint32_t)ecbign::MAX_OID || (oid_len && !oid)) {
+		return fail(std::string(fn) + ": oid_len must be 0 .. 64, and oid non-NULL when it is not 0");
+	}
+	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	if (hash_type == 0) {
+		if (stride < 1 || stride > (uint32_t)ecbign::MAX_DIGEST) {
+			return fail(std::string(fn) + ": hash_type 0 takes digests: stride must be the digest length, 1 .. 128");
+		}
+	} else if ((stride & 3u) || stride > 4096 || stride < 4) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	return 0;
+}
+
+extern "C" int ec_bign_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
+					const void *d_sigs, const void *d_inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, void *d_result,
+					void *hip_stream)
+{
+	if (bign_args_ok("ec_bign_verify_batch_dev", ctx, cv, alg, hash_type, n, d_pubkeys, d_sigs, d_inputs, d_result, d_result, stride, oid, oid_len)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return bign_verify_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_inputs, stride, oid,
+				      oid_len, (uint8_t *)d_result, s);
+}
+
+extern "C" int ec_bign_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
+				    const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *result)
+{
+	if (bign_args_ok("ec_bign_verify_batch", ctx, cv, alg, hash_type, n, pubkeys, sigs, inputs, result, result, stride, oid, oid_len)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, (size_t)ecbign::sig_len(cv->qlen)},
+					   {inputs, nullptr, stride}, {nullptr, result, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+						       hipStream_t s, const std::function<int()> &) {
+		return bign_verify_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], ip[2], stride, oid, oid_len, op[3], s);
+	});
+}
+
+extern "C" int ec_bign_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+				      const void *d_nonces, const void *d_inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, void *d_sigs,
+				      void *d_status, void *hip_stream)
+{
+	if (bign_args_ok("ec_bign_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_inputs, d_sigs, d_status, stride, oid, oid_len)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return bign_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_inputs, stride, oid,
+				    oid_len, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+}
+
+extern "C" int ec_bign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+				  const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *sigs,
+				  uint8_t *status)
+{
+	if (bign_args_ok("ec_bign_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, inputs, sigs, status, stride, oid, oid_len)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {inputs, nullptr, stride},
+					   {nullptr, sigs, (size_t)ecbign::sig_len(cv->qlen)}, {nullptr, status, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+						       hipStream_t s, const std::function<int()> &) {
+		return bign_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], ip[2], stride, oid, oid_len, op[3], op[4], s);
 	});
 }
 

@@ -197,6 +197,29 @@ hipError_t ecamd_launch_schnorr_item_fill(const EcamdSchnorrItemArgs &a, hipStre
 hipError_t ecamd_launch_schnorr_item_cmp(const EcamdSchnorrItemArgs &a, hipStream_t s);
 hipError_t ecamd_launch_schnorr_item_sign(int qnw, const EcamdSchnorrItemArgs &a, hipStream_t s);
 
+// ---- BIGN / DBIGN (sig/bign_common.c of the reference), ecamd_bign_kernels.h ----
+// One argument block for the four kernels; each reads the fields its step needs.
+struct EcamdBignArgs {
+	const uint8_t *sigs;     // verification: n x (l + qlen), s0 || s1, little-endian
+	const uint8_t *dg;       // n x hsize: the digests of the messages (the caller's, or what the device hashed from mslots)
+	const uint8_t *mslots;   // the caller's message slots when the device hashed them (their length words are checked), else NULL
+	const uint8_t *privs, *nonces;   // signing: n x qlen each, big-endian
+	uint8_t *u, *v;          // k_bign_prep: n x qlen big-endian, the multipliers of G and Y (zeros where flagged)
+	uint8_t *flags;          // n: 0 ok, 1 rejected before the multiplications (s1 >= q, an unusable message slot)
+	const uint8_t *W, *stW;  // the commitment, n x 2*clen affine, and its status (ECAMD_OK / ECAMD_ERR / ECAMD_INF)
+	uint8_t *slots;          // n x bstride: belt-hash's input slots, built by k_bign_fill
+	const uint8_t *bt;       // n x 32: the BelT digests of the slots
+	uint8_t *out;            // k_bign_cmp: n result bytes; k_bign_sign: n x (l + qlen) signatures
+	uint8_t *status;         // k_bign_sign: n
+	uint32_t n, qlen, clen, hsize, mstride, bstride, oid_len;
+	int qslot, sign;         // sign != 0: k_bign_fill runs in a signing call (no front end wrote flags)
+	uint8_t oid[64];
+};
+hipError_t ecamd_launch_bign_prep(int qnw, const EcamdBignArgs &a, hipStream_t s);
+hipError_t ecamd_launch_bign_fill(const EcamdBignArgs &a, hipStream_t s);
+hipError_t ecamd_launch_bign_cmp(const EcamdBignArgs &a, hipStream_t s);
+hipError_t ecamd_launch_bign_sign(int qnw, const EcamdBignArgs &a, hipStream_t s);
+
 // nw: 32-bit words per field element; must be one of ecamd_supported_nw()
 int ecamd_nw_supported(int nw);
 hipError_t ecamd_upload_curve(int nw, int slot, const void *curvek, size_t bytes);
@@ -716,6 +739,8 @@ hipError_t ecamd_launch_reject_where(uint8_t *result, const uint8_t *status, uin
 // SHAKE256 of the same slots: the first outlen (<= 136) octets of the output per message
 hipError_t ecamd_launch_shake256_slots(const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, uint32_t outlen, hipStream_t s);
 hipError_t ecamd_launch_sha2_slots(int hash_type, const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s);
+// belt-hash (STB 34.101.31) of the same slots: 32 digest bytes per item (ecamd_belt.h)
+hipError_t ecamd_launch_belt_slots(const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s);
 struct EcamdPrjInArgs;
 // prj_pt_import_from_buf + prj_pt_unique on a radix-2^29 unit, one inversion per eight triples (k_prj_import_g)
 hipError_t ecamd_g29_prj_import(int pbits, int gslot, const EcamdPrjInArgs &a, hipStream_t s, int flavour);

@@ -2861,3 +2861,5 @@ hipError_t ecamd_launch_prj_export(const EcamdPrjOutArgs &a, hipStream_t s)
 #include "ecamd_sighash_kernels.h"
 // BIP0340 / ECFSDSA item by item: k_schnorr_item_prep / _cmp / _fill / _sign and their launchers
 #include "ecamd_schnorr_kernels.h"
+// BIGN / DBIGN: k_bign_prep / _fill / _cmp / _sign and their launchers
+#include "ecamd_bign_kernels.h"

@@ -6,7 +6,7 @@ torch.distributed.run, weak scaling, contiguous shards, one RCCL all-gather of t
 bytes per step); not the driver's headline bench.  --workload ecdsa_recover is the exception: one GPU, recovery beside the
 verification of the same signatures in alternating windows (recover_row).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|bign_verify|bign_sign [--hash 0|16]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -453,11 +453,140 @@ def schnorr_row(a, ctx, dev, stream, rng, B):
     ctx.close()
 
 
+def bign_row(a, ctx, dev, stream, rng, B):
+    """BIGN (ec_bign_verify_batch_dev or ec_bign_sign_batch_dev, 24-byte messages), inputs resident in HBM, beside ECKCDSA
+    (ec_sig_hashed_verify_batch_dev / _sign_batch_dev, SHA-256: the same two multiplications, the same shared-inversion finish, one
+    short hash of the commitment) under the same private keys on the same curve in the same run, in alternating windows of a.steps
+    calls.  --hash 0: the caller hashed (SHA-256 on the host, the digests resident); --hash 16: message slots, belt-hash on the
+    device.  Gates: every signature the device made is accepted, with the inputs of the next item none is, the device-pointer form
+    signs what the host-pointer form signed, and --ref-items random items (and as many damaged ones) get the unmodified reference's
+    verdict where it is built.  One GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload bign_verify / bign_sign measures one GPU: run it with --gpus 1, outside torch.distributed.run")
+    import oracles as O
+    import bign_ref as BR
+    from libecc_amd import api as A
+    curve = a.curve
+    cv = ctx.curve(curve)
+    q = O.CURVES[curve]["q"]
+    ql, cl = O.qlen(curve), O.clen(curve)
+    hl, mlen = 32, 24
+    sl = cv.bign_siglen()
+    raw = rng.integers(0, 256, size=(2, B, ql + 8), dtype=np.uint8)
+
+    def scal(rows):
+        return [(int.from_bytes(rows[i].tobytes(), "big") % (q - 1)) + 1 for i in range(B)]
+
+    def t(b):
+        return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+    xs, ks = scal(raw[0]), scal(raw[1])
+    privs, nonces = (b"".join(v.to_bytes(ql, "big") for v in vs) for vs in (xs, ks))
+    pubs, st = cv.scalar_mult(privs)
+    assert set(st) == {0}
+    pubs_k = cv.scalar_mult(b"".join(pow(x, -1, q).to_bytes(ql, "big") for x in xs))[0]     # ECKCDSA's key is [1 / x]G
+    msgs = rng.integers(0, 256, size=(B, mlen), dtype=np.uint8)
+    if a.hash == 0:
+        hname, oid, stride = "SHA256", bytes.fromhex("0609608648016503040201"), hl
+        inp = b"".join(hashlib.sha256(msgs[i].tobytes()).digest() for i in range(B))
+    else:
+        hname, oid, stride = "BELT", BR.OID_BELT, BR.stride_for(mlen)
+        slots = np.zeros((B, stride), dtype=np.uint8)
+        slots[:, 0] = mlen
+        slots[:, 4:4 + mlen] = msgs
+        inp = slots.tobytes()
+    # the yardstick's input: h = H(z || m), z the first 64 octets of Yx || Yy (zero padded), hashed by the caller
+    inp_k = b"".join(hashlib.sha256((pubs_k[2 * cl * i:2 * cl * (i + 1)] + bytes(64))[:64] + msgs[i].tobytes()).digest() for i in range(B))
+    sigs, st = cv.bign_sign(A.SIG_BIGN, a.hash, privs, nonces, inp, stride, oid)
+    assert set(st) == {0}
+    sigs_k, st = cv.sig_hashed_sign(2, 2, privs, nonces, inp_k, hl)
+    assert set(st) == {0}
+    d_pub, d_sig, d_in, d_pub_k, d_sig_k, d_in_k, d_x, d_k = (t(b) for b in (pubs, sigs, inp, pubs_k, sigs_k, inp_k, privs, nonces))
+    d_res = torch.empty(B, dtype=torch.uint8, device=dev)
+    d_out, d_st = torch.empty(max(len(sigs), len(sigs_k)), dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    sign = a.workload == "bign_sign"
+
+    def bverify(d_s, d_i):
+        cv.bign_verify_dev(A.SIG_BIGN, a.hash, B, d_pub.data_ptr(), d_s.data_ptr(), d_i.data_ptr(), stride, oid, d_res.data_ptr(), stream.cuda_stream)
+        torch.cuda.synchronize()
+        return bytes(d_res.cpu().numpy())
+
+    def eckcdsa():
+        if sign:
+            cv.sig_hashed_sign_dev(2, 2, B, d_x.data_ptr(), d_k.data_ptr(), d_in_k.data_ptr(), hl, d_out.data_ptr(), d_st.data_ptr(), stream.cuda_stream)
+        else:
+            cv.sig_hashed_verify_dev(2, 2, B, d_pub_k.data_ptr(), d_sig_k.data_ptr(), d_in_k.data_ptr(), hl, d_res.data_ptr(), stream.cuda_stream)
+
+    def bign():
+        if sign:
+            cv.bign_sign_dev(A.SIG_BIGN, a.hash, B, d_x.data_ptr(), d_k.data_ptr(), d_in.data_ptr(), stride, oid, d_out.data_ptr(), d_st.data_ptr(),
+                             stream.cuda_stream)
+        else:
+            cv.bign_verify_dev(A.SIG_BIGN, a.hash, B, d_pub.data_ptr(), d_sig.data_ptr(), d_in.data_ptr(), stride, oid, d_res.data_ptr(), stream.cuda_stream)
+    # ---- gates ----
+    if bverify(d_sig, d_in) != bytes(B):
+        raise SystemExit("PARITY FAILURE: a signature the device made was rejected")
+    if bverify(d_sig, torch.roll(d_in, stride)) != b"\1" * B:
+        raise SystemExit("PARITY FAILURE: a signature was accepted for another item's input")
+    cv.sig_hashed_verify_dev(2, 2, B, d_pub_k.data_ptr(), d_sig_k.data_ptr(), d_in_k.data_ptr(), hl, d_res.data_ptr(), stream.cuda_stream)
+    torch.cuda.synchronize()
+    if bytes(d_res.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: the yardstick's own signature was rejected")
+    bign()
+    torch.cuda.synchronize()
+    if sign and (bytes(d_out.cpu().numpy())[:len(sigs)] != sigs or bytes(d_st.cpu().numpy()) != bytes(B)):
+        raise SystemExit("PARITY FAILURE: the device-pointer form signs differently")
+    gate = "all 2^%d device-made signatures accepted, none for its neighbour's input" % a.batch_log2
+    if O.have_ref() and a.ref_items > 0:
+        from concurrent.futures import ThreadPoolExecutor
+        idx = [int(i) for i in np.sort(np.random.default_rng(2).choice(B, size=min(B, a.ref_items), replace=False))]
+
+        def one(i):
+            key, sig, msg = pubs[2 * cl * i:2 * cl * (i + 1)], sigs[sl * i:sl * (i + 1)], msgs[i].tobytes()
+            bad = sig[:-1] + bytes([sig[-1] ^ 1])
+            return BR.ref_verify(curve, hname, oid, key, sig, msg), BR.ref_verify(curve, hname, oid, key, bad, msg)
+        with ThreadPoolExecutor(max_workers=min(16, os.cpu_count() or 1)) as ex:
+            got = list(ex.map(one, idx))
+        if got != [(0, -1)] * len(idx):
+            raise SystemExit("PARITY FAILURE: the reference disagrees on %d of %d sampled items" % (sum(g != (0, -1) for g in got), len(idx)))
+        bs = np.frombuffer(sigs, dtype=np.uint8).reshape(B, sl).copy()
+        bs[idx, sl - 1] ^= 1
+        exp = np.zeros(B, dtype=np.uint8)
+        exp[idx] = 1
+        if bverify(t(bs.tobytes()), d_in) != exp.tobytes():
+            raise SystemExit("PARITY FAILURE: damaged items are not the ones rejected")
+        gate += "; %d items and their damaged twins as the reference decides" % len(idx)
+    # ---- timing: alternating windows ----
+    for _ in range(a.warmup):
+        eckcdsa()
+        bign()
+    torch.cuda.synchronize()
+    te, tb = [], []
+    for _ in range(3):
+        for fn, acc in ((eckcdsa, te), (bign, tb)):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            acc.append((time.perf_counter() - t0) / a.steps)
+    me, mb = float(np.median(te)), float(np.median(tb))
+    kind = "signatures" if sign else "verifications"
+    how = "SHA-256 digests supplied" if a.hash == 0 else "belt-hash of the message on the device"
+    print(json.dumps({"metric": "BIGN %s/sec (%s, %s, batch=2^%d, device-resident)" % (kind, curve.lower(), how, a.batch_log2),
+                      "value": B / mb, "unit": kind + "/s", "bign_ms": [1e3 * x for x in tb],
+                      "eckcdsa_same_run": {"value": B / me, "unit": kind + "/s", "ms": [1e3 * x for x in te]},
+                      "bign_over_eckcdsa": me / mb, "gate": gate,
+                      "config": {"workload": a.workload, "hash": a.hash, "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+    cv.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
     ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa"],
                     help="sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
+    ap.add_argument("--hash", type=int, default=16, choices=[0, 16],
+                    help="bign_verify / bign_sign: 0 the caller hashed (SHA-256 digests supplied), 16 belt-hash of message slots on the device")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -510,6 +639,8 @@ def main():
         return sig_hashed_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("schnorr_verify", "schnorr_sign"):
         return schnorr_row(a, ctx, dev, stream, rng, B)
+    if a.workload in ("bign_verify", "bign_sign"):
+        return bign_row(a, ctx, dev, stream, rng, B)
     if a.workload == "ecdsa_verify":
         curve = a.curve
         cv = ctx.curve(curve)
