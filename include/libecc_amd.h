@@ -256,8 +256,8 @@ int ec_eddsa_verify_ph_prj_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint3
 				 uint8_t *result);
 /* ECDSA signing with caller-supplied nonces: per item the tail of ec_sign / __ecdsa_sign_finalize
  * (sig/ecdsa_common.c:318-586) -- kG = prj_pt_mul(k, G), r = kG.x mod q, s = k^-1 (x r + e) mod q --
- * with h = H(m) and the nonce k supplied by the caller (random, or RFC 6979 computed on the host;
- * the reference's KAT harness injects k through the same ctx->rand hook).  privs, nonces: n x qlen;
+ * with h = H(m) and the nonce k supplied by the caller (random; for RFC 6979 see ec_decdsa_sign_batch, which derives
+ * k on the device; the reference's KAT harness injects k through the same ctx->rand hook).  privs, nonces: n x qlen;
  * sigs: n x 2*qlen.  status[i] = 1 where the reference would fail or restart (private key >= q, k not in [1, q-1],
  * r = 0, e == x r, s = 0). */
 int ec_ecdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const uint8_t *privs,
@@ -360,8 +360,8 @@ int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, 
  *
  * Signing is _ec_sign with the nonce supplied by the caller, as for every other signing call here.
  *   nonces  n x qlen: the value k the scheme multiplies G by, k in [1, q - 1], otherwise status 1.  For BIP0340 that is the reference's
- *           H_nonce(...) mod q (sig/bip0340.c:237-294): the "BIP0340/aux" and "BIP0340/nonce" tagged hashes STAY WITH THE CALLER, as RFC 6979
- *           does for ECDSA.
+ *           H_nonce(...) mod q (sig/bip0340.c:237-294): the "BIP0340/aux" and "BIP0340/nonce" tagged hashes STAY WITH THE CALLER (unlike RFC 6979
+ *           for ECDSA: ec_decdsa_sign_batch).
  *   privs   n x qlen: x itself.  BIP0340: 0 < x < q, ECFSDSA: x < q (the reference signs with x = 0: s = k), otherwise status 1.
  *   pubkeys_aff  BIP0340: the key pair's public half, n x 2*clen -- its x is hashed and the parity of its y decides d <-> q - d.  NULL:
  *           the device derives Y = [x]G (fixed-base, honours secret-scalar mode).  Non-NULL: imported (coordinates < p, on the curve,
@@ -382,7 +382,7 @@ int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int
 			  uint8_t *status);
 /* BIGN and DBIGN (STB 34.101.45; sig/bign_common.c): the scheme that hashes its commitment with belt-hash (STB 34.101.31),
  * whatever hash the message had.  alg: libecc's ec_alg_type numbers 18 / 19 -- the two verify and sign identically here; they differ
- * in where the nonce comes from, and DBIGN's generator (__bign_determinitic_nonce) STAYS WITH THE CALLER, as RFC 6979 does for ECDSA.
+ * in where the nonce comes from, and DBIGN's generator (__bign_determinitic_nonce) STAYS WITH THE CALLER (unlike RFC 6979 for ECDSA: ec_decdsa_sign_batch).
  * Any other alg is a call-level error (-1, ecamd_last_error()).
  *   lengths  qlen = ceil(|q| / 8), l = qlen / 2 (integer division).  sigs: n x (l + qlen), s0 (l bytes) then s1 (qlen bytes),
  *            both LITTLE-ENDIAN, as the reference writes them (the digest read as a number and W's coordinates in the hash input
@@ -423,6 +423,33 @@ int ec_nn_random_mod_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n,
  * msg_stride bytes each.  Signature bytes equal those of ec_ecdsa_sign_batch fed with the reduced nonces and the digests. */
 int ec_ecdsa_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const uint8_t *privs, const uint8_t *nonce_raw,
 			    int hash_type, const uint8_t *msg_slots, uint32_t msg_stride, uint8_t *sigs, uint8_t *status);
+/* Deterministic ECDSA (DECDSA, libecc's ec_alg_type 14): the nonce of RFC 6979 section 3.2 derived ON THE DEVICE, as the reference's
+ * __ecdsa_rfc6979_nonce runs it (sig/ecdsa_common.c:48-169, called from __ecdsa_sign_finalize at :450), HMAC through the hash of the
+ * message (hmac/hmac.c).  hash_type 1 .. 4 (SHA-224 / 256 / 384 / 512, libecc's hash_alg_type numbers) names BOTH the message hash and
+ * the HMAC, as in libecc; any other value is a call-level error (-1, ecamd_last_error()).
+ *   ec_rfc6979_nonce_batch   privs n x qlen big-endian (int2octets(x) is these octets as given: nn_export_to_buf of the imported key,
+ *            :77), digests n x hsize (h1 = H(m), hsize = 28 / 32 / 48 / 64); nonces n x qlen big-endian.  V = 01.., K = 00..;
+ *            bits2octets(h1) = the digest as a big-endian integer, >> (8 hsize - qbits) when longer, mod q (:89-94); steps d - g (:78-116);
+ *            step h: V = HMAC_K(V) appended to T until 8 |T| >= qbits, k = the first qlen octets of T >> (8 qlen - qbits), accepted iff
+ *            k < q, otherwise K = HMAC_K(V || 00), V = HMAC_K(V) and again (:136-165).  As in the reference k = 0 is NOT rejected here (the
+ *            signing step refuses it).  status[i] = 0; 1 with a zero nonce only after 1000 rejected candidates, which no libecc curve
+ *            reaches (none rejects more than half).  The nonces are SECRET: this call hands them to the caller, who owns their wiping.
+ *   ec_decdsa_sign_batch     ec_key_pair_import_from_priv_key_buf + _ec_sign(DECDSA) per item (sig/sig_algs.c, sig/decdsa.c:46-90).
+ *            in_is_digest = 0: `in` holds message slots as for ec_ecdsa_sign_msg_batch (u32 length + bytes, in_stride a multiple of 4 in
+ *            4 .. 4096), hashed on the device; a slot whose length does not fit the stride is status 1.  in_is_digest = 1: `in` is
+ *            n x hsize digests and in_stride must equal hsize.  Anything else is a call-level error.  Then the nonce as above, into a
+ *            scratch buffer that never leaves the device (wiped when it is freed and by ecamd_ctx_wipe_scratch, like the nonces of
+ *            ec_ecdsa_sign_msg_batch), then ec_ecdsa_sign_batch's core: signature bytes and status are those of ec_ecdsa_sign_batch fed with
+ *            the derived k.  Key rules are ec_ecdsa_sign_batch's, which are the reference's (recorded in tests/golden/decdsa.json): x = 0
+ *            imports and signs, x >= q does not import -- status 1, zero bytes.  The reference RESTARTS on r = 0, e = x r or s = 0
+ *            (:492, :516, :548) and would derive the same k for ever; here that is status 1 with zero bytes.
+ * [k]G honours ecamd_ctx_set_secret_scalars; the nonce kernel looks nothing up by a secret and branches on one only in the RFC's own
+ * retry.  Chunking by ecamd_ctx_set_max_chunk, n = 0 (returns 0, touches nothing), NULL arguments and a handle of another context
+ * (-1) as for ec_ecdsa_sign_batch.  Orders of at most 528 bits (qlen <= 66). */
+int ec_rfc6979_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs,
+			   const uint8_t *digests, uint8_t *nonces, uint8_t *status);
+int ec_decdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *in,
+			 uint32_t in_stride, int in_is_digest, uint8_t *sigs, uint8_t *status);
 /* ec_key_pair_gen's generic rule (sig/ec_key.c:594-610): x = nn_get_random_mod(q) from the item's 2*qlen random bytes, Y = [x]G.
  * priv_out: n x qlen big-endian; pub_out: n x 2*clen affine X || Y; status as ec_prj_pt_mul_batch.  (Secret scalars: see
  * ecamd_ctx_set_secret_scalars; the private keys cross the bus on their way back, as supplied ones do on their way in.) */
@@ -689,6 +716,15 @@ int ec_bign_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, 
 int ec_bign_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_privs,
 			   const void *d_nonces, const void *d_inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, void *d_sigs,
 			   void *d_status, void *hip_stream);
+/* ec_rfc6979_nonce_batch / ec_decdsa_sign_batch with device pointers: enqueue only (sig/ecdsa_common.c:48-169 on the device, then the
+ * core of ec_ecdsa_sign_batch_dev).  Scratch of the signing call: per item of a chunk the nonce (qlen bytes, secret), the digest when
+ * in_is_digest = 0, and what ec_ecdsa_sign_batch_dev takes.  Message slots and digests are read where they lie: with in_is_digest = 0
+ * d_in must be 4-byte aligned (the length word of a slot is read as one aligned word; in_stride is a multiple of 4), digests and keys
+ * are read by octets and need no alignment.  d_nonces of the nonce call is the caller's buffer: secret, and the caller's to wipe. */
+int ec_rfc6979_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs,
+			       const void *d_digests, void *d_nonces, void *d_status, void *hip_stream);
+int ec_decdsa_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs, const void *d_in,
+			     uint32_t in_stride, int in_is_digest, void *d_sigs, void *d_status, void *hip_stream);
 /* ec_schnorr_verify_batch / ec_schnorr_sign_batch with device pointers: enqueue only.  Scratch: besides what a verification or signing
  * call of the curve takes, a device-to-device copy of the slots of one chunk (min(n, max_chunk) x stride bytes: choose the stride to fit
  * the longest message, or lower ecamd_ctx_set_max_chunk).  d_pubkeys_aff may be NULL, as pubkeys_aff. */

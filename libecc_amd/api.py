@@ -33,6 +33,7 @@ EXPORTED_SYMBOLS = [
     "ec_sig_hashed_verify_batch", "ec_sig_hashed_verify_batch_dev", "ec_sig_hashed_sign_batch", "ec_sig_hashed_sign_batch_dev",
     "ec_schnorr_verify_batch", "ec_schnorr_verify_batch_dev", "ec_schnorr_sign_batch", "ec_schnorr_sign_batch_dev",
     "ec_bign_verify_batch", "ec_bign_verify_batch_dev", "ec_bign_sign_batch", "ec_bign_sign_batch_dev",
+    "ec_rfc6979_nonce_batch", "ec_rfc6979_nonce_batch_dev", "ec_decdsa_sign_batch", "ec_decdsa_sign_batch_dev",
 ]
 
 # libecc's ec_alg_type numbers of the schemes ec_sig_verify_batch / ec_sig_sign_batch serve (ECAMD_SIG_* in include/libecc_amd.h)
@@ -143,6 +144,10 @@ def load_library():
         L.ec_eddsa_sign_R_batch.argtypes = [vp, vp, u32, u8p, u8p, u8p]
         L.ec_eddsa_sign_S_batch.argtypes = [vp, vp, u32, u8p, u8p, u8p, u8p]
         L.ec_ecdsa_sign_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, u32, vp, vp, vp]
+        L.ec_rfc6979_nonce_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u8p]
+        L.ec_rfc6979_nonce_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, vp, vp]
+        L.ec_decdsa_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u32, C.c_int, u8p, u8p]
+        L.ec_decdsa_sign_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u32, C.c_int, vp, vp, vp]
         L.ec_ecccdh_derive_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
         L.ec_xdh_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
         L.ec_ecccdh_derive_batch.argtypes = [vp, vp, u32, u8p, u8p, u8p, u8p]
@@ -502,6 +507,23 @@ class Curve:
              "ec_ecdsa_sign_msg_batch")
         return sigs.raw[:2 * self.qlen * n], st.raw[:n]
 
+    def rfc6979_nonce(self, hash_type, privs, digests):
+        """the nonces of deterministic ECDSA (RFC 6979 section 3.2, HMAC over SHA-2 hash_type 1 .. 4) derived on the device:
+        (n x qlen big-endian, status)"""
+        n = len(privs) // self.qlen
+        out, st = C.create_string_buffer(max(1, self.qlen * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_rfc6979_nonce_batch(self.ctx.h, self.h, hash_type, n, privs, digests, out, st), "ec_rfc6979_nonce_batch")
+        return out.raw[:self.qlen * n], st.raw[:n]
+
+    def decdsa_sign(self, hash_type, privs, inputs, stride, is_digest):
+        """deterministic ECDSA signatures (r || s) and a status byte per item; inputs: message slots of `stride` bytes (is_digest
+        False, hashed on the device) or the digests themselves (is_digest True, stride = the digest length)"""
+        n = len(privs) // self.qlen
+        sigs, st = C.create_string_buffer(max(1, 2 * self.qlen * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_decdsa_sign_batch(self.ctx.h, self.h, hash_type, n, privs, inputs, stride, 1 if is_digest else 0, sigs, st),
+             "ec_decdsa_sign_batch")
+        return sigs.raw[:2 * self.qlen * n], st.raw[:n]
+
     def key_pair_gen_raw(self, raw):
         """x = nn_get_random_mod value of the item's 2 * qlen random bytes, Y = [x]G: (privs, pubs affine, status)"""
         n = len(raw) // (2 * self.qlen)
@@ -679,6 +701,14 @@ class Curve:
     def ecdsa_sign_dev(self, n, d_privs, d_nonces, d_digests, hlen, d_sigs, d_status, stream=None):
         _chk(self.L, self.L.ec_ecdsa_sign_batch_dev(self.ctx.h, self.h, n, d_privs, d_nonces, d_digests, hlen, d_sigs,
                                                      d_status, stream), "ec_ecdsa_sign_batch_dev")
+
+    def rfc6979_nonce_dev(self, hash_type, n, d_privs, d_digests, d_nonces, d_status, stream=None):
+        _chk(self.L, self.L.ec_rfc6979_nonce_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_digests, d_nonces, d_status, stream),
+             "ec_rfc6979_nonce_batch_dev")
+
+    def decdsa_sign_dev(self, hash_type, n, d_privs, d_in, stride, is_digest, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_decdsa_sign_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_in, stride, 1 if is_digest else 0, d_sigs,
+                                                      d_status, stream), "ec_decdsa_sign_batch_dev")
 
     def ecccdh_dev(self, n, d_privs, d_peers, d_secrets, d_status, stream=None):
         _chk(self.L, self.L.ec_ecccdh_derive_batch_dev(self.ctx.h, self.h, n, d_privs, d_peers, d_secrets, d_status,

@@ -24,6 +24,7 @@
 #include "ecamd_sighash.h"
 #include "ecamd_schnorr.h"
 #include "ecamd_bign.h"
+#include "ecamd_rfc6979.h"
 
 // ------------------------------------------------------------------------------------------
 // error reporting
@@ -3035,6 +3036,177 @@ extern "C" int ec_ecdsa_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, ui
 			d_dig = ctx->stage[17];
 		}
 		return ecdsa_sign_dev_locked(ctx, cv, m, ip[0], ctx->stage[20], d_dig, hlen, op[3], op[4], s);
+	});
+}
+
+// ------------------------------------------------------------------------------------------
+// deterministic ECDSA (include/libecc_amd.h: ec_rfc6979_nonce_batch, ec_decdsa_sign_batch): the nonce of RFC 6979 section 3.2
+// derived on the device (k_rfc6979_nonce, ecamd_rfc6979.hip), then the ECDSA signing core.  Per chunk of at most max_chunk items:
+//   k_sha2_slots       in_is_digest = 0: h1 = H(m) into stage 17
+//   k_rfc6979_nonce    k into stage 20 (secret: ensure() wipes what it frees, ecamd_ctx_wipe_scratch the rest); a slot whose length
+//                      does not fit gets k = 0
+//   ecdsa_sign_dev_locked   [k]G as the context's secret-scalar mode says, r, s; k = 0 is status 1 with zero bytes
+// Only enqueues.
+// ------------------------------------------------------------------------------------------
+static int rfc6979_nonce_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_digests,
+				    const uint8_t *d_slots, uint32_t stride, uint8_t *d_nonces, uint8_t *d_status, hipStream_t s)
+{
+	(void)ctx;
+	EcamdRfc6979Args R;
+	memset(&R, 0, sizeof(R));
+	R.privs = d_privs;
+	R.digests = d_digests;
+	R.slots = d_slots;
+	R.stride = stride;
+	R.nonces = d_nonces;
+	R.status = d_status;
+	R.n = n;
+	R.qlen = (uint32_t)cv->qlen;
+	R.qbits = (uint32_t)cv->qbits;
+	for (int w = 0; w < 17; w++) {
+		R.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
+	}
+	HIPCHK(ecamd_launch_rfc6979_nonce(hash_type, R, s));
+	return 0;
+}
+
+static int rfc6979_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type)
+{
+	if (ecrfc::hash_size(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224 / 256 / 384 / 512)");
+	}
+	if (!ctx || !cv || cv->ctx != ctx) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0 || big_bitlen(cv->q) < 2 || cv->q.size() > 17 || cv->qlen > ecrfc::MAX_QLEN ||
+	    (uint32_t)cv->qlen != ((uint32_t)cv->qbits + 7) / 8) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	return 0;
+}
+
+extern "C" int ec_rfc6979_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
+					  const void *d_digests, void *d_nonces, void *d_status, void *hip_stream)
+{
+	if (rfc6979_args_ok("ec_rfc6979_nonce_batch_dev", ctx, cv, hash_type)) {
+		return -1;
+	}
+	if (n && (!d_privs || !d_digests || !d_nonces || !d_status)) {
+		return fail("ec_rfc6979_nonce_batch_dev: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return rfc6979_nonce_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_digests, nullptr, 0, (uint8_t *)d_nonces,
+					(uint8_t *)d_status, s);
+}
+
+extern "C" int ec_rfc6979_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+				      const uint8_t *digests, uint8_t *nonces, uint8_t *status)
+{
+	if (rfc6979_args_ok("ec_rfc6979_nonce_batch", ctx, cv, hash_type)) {
+		return -1;
+	}
+	if (n && (!privs || !digests || !nonces || !status)) {
+		return fail("ec_rfc6979_nonce_batch: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {digests, nullptr, (size_t)ecrfc::hash_size(hash_type)}, {nullptr, nonces, ql},
+					   {nullptr, status, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+						       hipStream_t s, const std::function<int()> &) {
+		return rfc6979_nonce_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], nullptr, 0, op[2], op[3], s);
+	});
+}
+
+static int decdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_in,
+				  uint32_t stride, int in_is_digest, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
+{
+	const size_t ql = (size_t)cv->qlen;
+	const uint32_t hlen = (uint32_t)ecrfc::hash_size(hash_type);
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	if (ensure(&ctx->stage[20], &ctx->stage_bytes[20], (size_t)chunk * ql)) {
+		return -1;
+	}
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		const uint8_t *in = d_in + (size_t)off * stride, *d_dig = in;
+		if (!in_is_digest) {
+			if (ecdsa_hash_stage(ctx, hash_type, m, in, stride, hlen, s)) {
+				return -1;
+			}
+			d_dig = ctx->stage[17];
+		}
+		// (the nonce kernel's status lands in the caller's status bytes and is replaced by the signing core's: a zero nonce is status 1 there)
+		if (rfc6979_nonce_dev_locked(ctx, cv, hash_type, m, d_privs + off * ql, d_dig, in_is_digest ? nullptr : in, stride, ctx->stage[20],
+					     d_status + off, s) ||
+		    ecdsa_sign_dev_locked(ctx, cv, m, d_privs + off * ql, ctx->stage[20], d_dig, hlen, d_sigs + off * 2 * ql, d_status + off, s)) {
+			return -1;
+		}
+	}
+	return 0;
+}
+
+static int decdsa_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *a, const void *b,
+			  uint32_t stride, int in_is_digest, const void *c, const void *d)
+{
+	if (rfc6979_args_ok(fn, ctx, cv, hash_type)) {
+		return -1;
+	}
+	if (in_is_digest != 0 && in_is_digest != 1) {
+		return fail(std::string(fn) + ": in_is_digest must be 0 or 1");
+	}
+	if (in_is_digest ? stride != (uint32_t)ecrfc::hash_size(hash_type) : (stride < 4 || (stride & 3u) || stride > 4096)) {
+		return fail(std::string(fn) + ": in_stride must be the digest length (in_is_digest = 1) or a multiple of 4 in 4 .. 4096 (message slots)");
+	}
+	if (n && (!a || !b || !c || !d)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	return 0;
+}
+
+extern "C" int ec_decdsa_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs, const void *d_in,
+					uint32_t in_stride, int in_is_digest, void *d_sigs, void *d_status, void *hip_stream)
+{
+	if (decdsa_args_ok("ec_decdsa_sign_batch_dev", ctx, cv, hash_type, n, d_privs, d_in, in_stride, in_is_digest, d_sigs, d_status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return decdsa_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_in, in_stride, in_is_digest, (uint8_t *)d_sigs,
+				      (uint8_t *)d_status, s);
+}
+
+extern "C" int ec_decdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *in,
+				    uint32_t in_stride, int in_is_digest, uint8_t *sigs, uint8_t *status)
+{
+	if (decdsa_args_ok("ec_decdsa_sign_batch", ctx, cv, hash_type, n, privs, in, in_stride, in_is_digest, sigs, status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {in, nullptr, in_stride}, {nullptr, sigs, 2 * ql}, {nullptr, status, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+						       hipStream_t s, const std::function<int()> &) {
+		return decdsa_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], in_stride, in_is_digest, op[2], op[3], s);
 	});
 }
 

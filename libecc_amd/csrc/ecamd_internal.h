@@ -683,6 +683,18 @@ struct EcamdRandModArgs {
 	uint32_t q[18];          // the generator's order, little-endian words
 };
 hipError_t ecamd_launch_rand_mod(int qnw, const EcamdRandModArgs &a, hipStream_t s);
+// the nonce of deterministic ECDSA (RFC 6979 section 3.2, ecamd_rfc6979.h / ecamd_rfc6979.hip); hash_type 1 .. 4 is the HMAC's hash
+struct EcamdRfc6979Args {
+	const uint8_t *privs;    // n x qlen big-endian
+	const uint8_t *digests;  // n x hsize
+	const uint8_t *slots;    // NULL, or the n message slots the digests were hashed from: a length word that does not fit `stride`
+	uint32_t stride;         //   gives its item status 1 and a zero nonce
+	uint8_t *nonces;         // n x qlen big-endian (secret)
+	uint8_t *status;         // n: 0, or 1 with a zero nonce
+	uint32_t n, qlen, qbits;
+	uint32_t q[17];          // the generator's order, little-endian words
+};
+hipError_t ecamd_launch_rfc6979_nonce(int hash_type, const EcamdRfc6979Args &a, hipStream_t s);
 // Front end of ec_schnorr_verify_msg_all_batch (BIP0340 / ECFSDSA from keys, signatures and hash inputs; round 6), per chunk of m items:
 //   k_schnorr_prep  the imported key's x into the blank of the item's hash input (BIP0340), the key as the equation uses it (BIP0340: the
 //                   representative with an even y), s and the commitment (r, or W) into the batch-wide arrays; a key that did not import

@@ -6,7 +6,7 @@ torch.distributed.run, weak scaling, contiguous shards, one RCCL all-gather of t
 bytes per step); not the driver's headline bench.  --workload ecdsa_recover is the exception: one GPU, recovery beside the
 verification of the same signatures in alternating windows (recover_row).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|bign_verify|bign_sign [--hash 0|16]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..4 --curve C]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -580,13 +580,106 @@ def bign_row(a, ctx, dev, stream, rng, B):
     ctx.close()
 
 
+def decdsa_row(a, ctx, dev, stream, rng, B):
+    """Deterministic ECDSA (ec_decdsa_sign_batch_dev on digests: the nonce of RFC 6979 derived on the device, then the signing core)
+    beside ec_ecdsa_sign_batch_dev with SUPPLIED nonces on the same keys and digests, in the same run, in alternating windows of
+    a.steps calls; and the nonce kernel by itself (ec_rfc6979_nonce_batch_dev) between HIP events.  --hash 1 .. 4: the SHA-2 of the
+    digests and of the HMAC.  Gates: the nonces the device derives are the Python restatement's on --ref-items random items, the
+    signatures are those of the supplied-nonce call fed with them, and every signature is accepted.  One GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload decdsa_sign measures one GPU: run it with --gpus 1, outside torch.distributed.run")
+    import oracles as O
+    import decdsa_ref as D
+    curve = a.curve
+    hname = {1: "SHA224", 2: "SHA256", 3: "SHA384", 4: "SHA512"}[a.hash]
+    cv = ctx.curve(curve)
+    q, ql, hl = O.CURVES[curve]["q"], O.qlen(curve), D.HSIZE[hname]
+    raw = rng.integers(0, 256, size=(B, ql + 8), dtype=np.uint8)
+    privs = b"".join(((int.from_bytes(raw[i].tobytes(), "big") % (q - 1)) + 1).to_bytes(ql, "big") for i in range(B))
+    dgs = rng.integers(0, 256, size=B * hl, dtype=np.uint8).tobytes()       # digests of messages nobody needs to know
+    pubs, st = cv.scalar_mult(privs)
+    assert set(st) == {0}
+
+    def t(b):
+        return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+    d_x, d_dg, d_pub = t(privs), t(dgs), t(pubs)
+    d_k = torch.empty(B * ql, dtype=torch.uint8, device=dev)
+    d_sig, d_sig2 = (torch.empty(B * 2 * ql, dtype=torch.uint8, device=dev) for _ in range(2))
+    d_st, d_st2, d_res = (torch.empty(B, dtype=torch.uint8, device=dev) for _ in range(3))
+    sp = stream.cuda_stream
+
+    def nonces():
+        cv.rfc6979_nonce_dev(a.hash, B, d_x.data_ptr(), d_dg.data_ptr(), d_k.data_ptr(), d_st.data_ptr(), sp)
+
+    def decdsa():
+        cv.decdsa_sign_dev(a.hash, B, d_x.data_ptr(), d_dg.data_ptr(), hl, True, d_sig.data_ptr(), d_st.data_ptr(), sp)
+
+    def supplied():
+        cv.ecdsa_sign_dev(B, d_x.data_ptr(), d_k.data_ptr(), d_dg.data_ptr(), hl, d_sig2.data_ptr(), d_st2.data_ptr(), sp)
+    # ---- gates ----
+    nonces()
+    torch.cuda.synchronize()
+    ks = bytes(d_k.cpu().numpy())
+    if bytes(d_st.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: a nonce was not derived")
+    idx = [int(i) for i in np.sort(np.random.default_rng(2).choice(B, size=min(B, max(1, a.ref_items)), replace=False))]
+    retries = 0
+    for i in idx:
+        k, r = D.nonce_from_digest(curve, hname, privs[ql * i:ql * (i + 1)], dgs[hl * i:hl * (i + 1)])
+        retries += r
+        if k.to_bytes(ql, "big") != ks[ql * i:ql * (i + 1)]:
+            raise SystemExit("PARITY FAILURE: item %d's nonce is not the restatement's" % i)
+    decdsa()
+    supplied()
+    cv.ecdsa_verify_dev(B, d_pub.data_ptr(), d_sig.data_ptr(), d_dg.data_ptr(), hl, d_res.data_ptr(), sp)
+    torch.cuda.synchronize()
+    if bytes(d_sig.cpu().numpy()) != bytes(d_sig2.cpu().numpy()) or bytes(d_st.cpu().numpy()) != bytes(B) or bytes(d_st2.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: the deterministic call does not sign what the supplied-nonce call signs with its nonces")
+    if bytes(d_res.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: a signature the device made was rejected")
+    gate = "%d nonces as the Python restatement derives them (%d rejected candidates among them); all 2^%d signatures equal those of the supplied-nonce call and accepted" % (len(idx), retries, a.batch_log2)
+    # ---- timing: alternating windows; the nonce kernel between events ----
+    for _ in range(a.warmup):
+        supplied()
+        decdsa()
+        nonces()
+    torch.cuda.synchronize()
+    ts, td, tn = [], [], []
+    for _ in range(3):
+        for fn, acc in ((supplied, ts), (decdsa, td)):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            acc.append((time.perf_counter() - t0) / a.steps)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(a.steps):
+            nonces()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        tn.append(e0.elapsed_time(e1) / 1e3 / a.steps)
+    ms, md, mn = float(np.median(ts)), float(np.median(td)), float(np.median(tn))
+    print(json.dumps({"metric": "deterministic ECDSA signatures/sec (%s, %s digests supplied, nonces derived on the device, batch=2^%d, device-resident)"
+                                % (curve.lower(), hname, a.batch_log2),
+                      "value": B / md, "unit": "signatures/s", "decdsa_ms": [1e3 * x for x in td],
+                      "supplied_nonces_same_run": {"value": B / ms, "unit": "signatures/s", "ms": [1e3 * x for x in ts]},
+                      "decdsa_over_supplied": ms / md,
+                      "nonce_kernel": {"ms": [1e3 * x for x in tn], "ns_per_item": 1e9 * mn / B, "items_per_s": B / mn},
+                      "gate": gate,
+                      "config": {"workload": a.workload, "hash": a.hash, "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+    cv.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
     ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa"],
                     help="sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
-    ap.add_argument("--hash", type=int, default=16, choices=[0, 16],
-                    help="bign_verify / bign_sign: 0 the caller hashed (SHA-256 digests supplied), 16 belt-hash of message slots on the device")
+    ap.add_argument("--hash", type=int, default=None, choices=[0, 1, 2, 3, 4, 16],
+                    help="bign_verify / bign_sign: 0 the caller hashed (SHA-256 digests supplied), 16 (default) belt-hash of message slots on the device; "
+                         "decdsa_sign: 1 .. 4, SHA-224 / 256 (default) / 384 / 512")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -599,6 +692,13 @@ def main():
     ap.add_argument("--mad-peak", type=float, default=0.0, help="lane-MADs/s of the v_mad_u64_u32 streams measured by ubench (VGPR multiplier); 0: measure now")
     ap.add_argument("--mad-peak-sgpr", type=float, default=0.0, help="the same with an SGPR multiplier")
     a = ap.parse_args()
+    if a.hash is None:
+        a.hash = 2 if a.workload == "decdsa_sign" else 16
+    # the option means something to these workloads only; the others ignore it, as they always have
+    if a.workload == "decdsa_sign" and a.hash not in (1, 2, 3, 4):
+        raise SystemExit("--workload decdsa_sign: --hash 1 .. 4")
+    if a.workload in ("bign_verify", "bign_sign") and a.hash not in (0, 16):
+        raise SystemExit("--workload %s: --hash 0 or 16" % a.workload)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -641,6 +741,8 @@ def main():
         return schnorr_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("bign_verify", "bign_sign"):
         return bign_row(a, ctx, dev, stream, rng, B)
+    if a.workload == "decdsa_sign":
+        return decdsa_row(a, ctx, dev, stream, rng, B)
     if a.workload == "ecdsa_verify":
         curve = a.curve
         cv = ctx.curve(curve)
