@@ -582,6 +582,36 @@ int ec_eddsa_sign_R_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, 
 int ec_eddsa_sign_S_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const uint8_t *r_hash, const uint8_t *hram,
 			  const uint8_t *a_scalars, uint8_t *S_out);
 
+/* One-call EdDSA signing, every hash on the device: eddsa_import_key_pair_from_priv_key_buf (sig/eddsa.c:1028) + _ec_sign ->
+ * _eddsa_sign (:1554-1870) per item.  alg: libecc's ec_alg_type (lib_ecc_types.h:49-55) -- EDDSA25519 (9), EDDSA25519CTX (10),
+ * EDDSA25519PH (11) on the WEI25519 handle (klen 32, SHA-512); EDDSA448 (12), EDDSA448PH (13) on the WEI448 handle (klen 57, SHAKE256
+ * with 114 octets of output, 64 for EDDSA448PH's pre-hash).  Any other alg, or an alg on the other handle, is a call-level error (-1).
+ *   secret_keys  n x klen, the RFC 8032 secret key octets.  Per item h = H(octets as given), clamped as eddsa_derive_priv_key does
+ *                (:611-688, the clamp at :649-671); a = the first half little-endian, prefix = the second half.
+ *   pubkeys      n x klen encodings of A, hashed as they are -- like _eddsa_sign, this form does NOT check that a public key belongs
+ *                to its secret key --, or NULL: A = encode([a]B) is computed here, the way R is (Ed448: a / 4 on WEI448 and the
+ *                4-isogeny, as eddsa_init_pub_key :840 does).
+ *   adata        ONE context for the call, host memory in both forms, adata_len in 0 .. 255: dom2 / dom4 (:55-130).  EDDSA25519
+ *                hashes no dom and ignores both arguments.  EDDSA25519CTX with adata == NULL (:1683) and adata_len > 255 (:64) are
+ *                call-level errors.  adata == NULL elsewhere hashes OLEN and no octets, as :79 does.
+ *   msg_slots    as ec_decdsa_sign_batch's: per item a little-endian u32 length, then the bytes; msg_stride a multiple of 4 in
+ *                4 .. 4096.  A length that does not fit the stride: status 1 and zero signature bytes for that item only.  The PH
+ *                variants compute PH(M) here.
+ *   sigs         n x 2 klen, R || S.  pub_out (n x klen, or NULL): the encoding of A of every item (given or derived).
+ *   status       0 signed; 1 where the reference returns -1: a bad slot (a failed generator multiplication cannot happen).
+ *                r = 0 mod q signs with the neutral element's encoding, as ec_eddsa_sign_R_batch documents.
+ * r_hash = H(dom || prefix || PH(M)) (:1679-1707) and H(dom || R || A || PH(M)) (:1782-1835) are streamed over their segments; the
+ * prefix never leaves the registers.  a and r_hash lie in the context's scratch between the kernels: wiped when freed and by
+ * ecamd_ctx_wipe_scratch, like the RFC 6979 nonces.  [r]B and [a]B honour ecamd_ctx_set_secret_scalars; chunks follow
+ * ecamd_ctx_set_max_chunk.  n = 0 touches nothing.
+ * ec_eddsa_pub_key_batch: eddsa_import_key_pair_from_priv_key_buf + eddsa_export_pub_key (:970) alone; status as
+ * ec_eddsa_sign_R_batch's. */
+int ec_eddsa_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const uint8_t *secret_keys,
+			    const uint8_t *pubkeys, const uint8_t *adata, uint32_t adata_len, const uint8_t *msg_slots,
+			    uint32_t msg_stride, uint8_t *sigs, uint8_t *pub_out, uint8_t *status);
+int ec_eddsa_pub_key_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const uint8_t *secret_keys, uint8_t *pub_out,
+			   uint8_t *status);
+
 /* Point wire formats (curves/prj_pt.c:462-624): affine X || Y (2*clen bytes, what the entry points above
  * use) and projective X || Y || Z (3*clen bytes: prj_pt_import_from_buf / prj_pt_export_to_buf, the format
  * of `ec_utils scalar_mult` and of structured public keys). */
@@ -725,6 +755,16 @@ int ec_rfc6979_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int has
 			       const void *d_digests, void *d_nonces, void *d_status, void *hip_stream);
 int ec_decdsa_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs, const void *d_in,
 			     uint32_t in_stride, int in_is_digest, void *d_sigs, void *d_status, void *hip_stream);
+/* ec_eddsa_sign_msg_batch / ec_eddsa_pub_key_batch with device pointers: enqueue only (sig/eddsa.c:611-688 and :1554-1870 on the
+ * device).  adata stays host memory: it is copied into the kernel arguments before the call returns.  d_pubkeys and d_pub_out may be
+ * NULL.  d_msg_slots must be 4-byte aligned (the length word is read as one aligned word); keys and encodings need no alignment.
+ * Scratch per item of a chunk: a, r_hash, hram, R, S, PH(M) for the PH variants, and what ec_eddsa_sign_R_batch takes (twice when
+ * the keys are derived here). */
+int ec_eddsa_sign_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const void *d_secret_keys,
+				const void *d_pubkeys, const uint8_t *adata, uint32_t adata_len, const void *d_msg_slots,
+				uint32_t msg_stride, void *d_sigs, void *d_pub_out, void *d_status, void *hip_stream);
+int ec_eddsa_pub_key_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const void *d_secret_keys, void *d_pub_out,
+			       void *d_status, void *hip_stream);
 /* ec_schnorr_verify_batch / ec_schnorr_sign_batch with device pointers: enqueue only.  Scratch: besides what a verification or signing
  * call of the curve takes, a device-to-device copy of the slots of one chunk (min(n, max_chunk) x stride bytes: choose the stride to fit
  * the longest message, or lower ecamd_ctx_set_max_chunk).  d_pubkeys_aff may be NULL, as pubkeys_aff. */

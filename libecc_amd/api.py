@@ -34,7 +34,11 @@ EXPORTED_SYMBOLS = [
     "ec_schnorr_verify_batch", "ec_schnorr_verify_batch_dev", "ec_schnorr_sign_batch", "ec_schnorr_sign_batch_dev",
     "ec_bign_verify_batch", "ec_bign_verify_batch_dev", "ec_bign_sign_batch", "ec_bign_sign_batch_dev",
     "ec_rfc6979_nonce_batch", "ec_rfc6979_nonce_batch_dev", "ec_decdsa_sign_batch", "ec_decdsa_sign_batch_dev",
+    "ec_eddsa_sign_msg_batch", "ec_eddsa_sign_msg_batch_dev", "ec_eddsa_pub_key_batch", "ec_eddsa_pub_key_batch_dev",
 ]
+
+# libecc's ec_alg_type numbers of the EdDSA variants ec_eddsa_sign_msg_batch serves (lib_ecc_types.h:49-55)
+EDDSA25519, EDDSA25519CTX, EDDSA25519PH, EDDSA448, EDDSA448PH = 9, 10, 11, 12, 13
 
 # libecc's ec_alg_type numbers of the schemes ec_sig_verify_batch / ec_sig_sign_batch serve (ECAMD_SIG_* in include/libecc_amd.h)
 SIG_ECGDSA, SIG_ECRDSA, SIG_SM2 = 6, 7, 8
@@ -148,6 +152,10 @@ def load_library():
         L.ec_rfc6979_nonce_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, vp, vp]
         L.ec_decdsa_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u32, C.c_int, u8p, u8p]
         L.ec_decdsa_sign_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u32, C.c_int, vp, vp, vp]
+        L.ec_eddsa_sign_msg_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u32, u8p, u8p, u8p]
+        L.ec_eddsa_sign_msg_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u8p, u32, vp, u32, vp, vp, vp, vp]
+        L.ec_eddsa_pub_key_batch.argtypes = [vp, vp, u32, u8p, u8p, u8p]
+        L.ec_eddsa_pub_key_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp]
         L.ec_ecccdh_derive_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
         L.ec_xdh_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
         L.ec_ecccdh_derive_batch.argtypes = [vp, vp, u32, u8p, u8p, u8p, u8p]
@@ -575,6 +583,27 @@ class Curve:
         _chk(self.L, self.L.ec_eddsa_sign_S_batch(self.ctx.h, self.h, n, r_hash, hram, a_scalars, out), "ec_eddsa_sign_S_batch")
         return out.raw[:kl * n]
 
+    def eddsa_sign_msgs(self, alg, secret_keys, pubkeys, adata, slots, stride, adata_len=None, want_pub=True):
+        """one-call EdDSA signing with every hash on the device (alg: EDDSA25519 .. EDDSA448PH): secret_keys n x klen, pubkeys
+        n x klen or None (derived on the device), adata the call's context (bytes or None), slots n message slots of `stride` bytes
+        -> (sigs n x 2 klen, pub_out n x klen, status)"""
+        kl = 57 if self.clen == 56 else 32
+        n = len(secret_keys) // kl
+        sigs, st = C.create_string_buffer(max(1, 2 * kl * n)), C.create_string_buffer(max(1, n))
+        pub = C.create_string_buffer(max(1, kl * n)) if want_pub else None
+        alen = (len(adata) if adata is not None else 0) if adata_len is None else adata_len
+        _chk(self.L, self.L.ec_eddsa_sign_msg_batch(self.ctx.h, self.h, alg, n, secret_keys, pubkeys, adata, alen, slots, stride, sigs, pub, st),
+             "ec_eddsa_sign_msg_batch")
+        return sigs.raw[:2 * kl * n], (pub.raw[:kl * n] if want_pub else None), st.raw[:n]
+
+    def eddsa_pub_keys(self, secret_keys):
+        """eddsa_import_key_pair_from_priv_key_buf + eddsa_export_pub_key in batch: (n x klen encodings of A, status)"""
+        kl = 57 if self.clen == 56 else 32
+        n = len(secret_keys) // kl
+        pub, st = C.create_string_buffer(max(1, kl * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_eddsa_pub_key_batch(self.ctx.h, self.h, n, secret_keys, pub, st), "ec_eddsa_pub_key_batch")
+        return pub.raw[:kl * n], st.raw[:n]
+
     def eddsa_encode_points(self, points_prj):
         """eddsa_export_pub_key in batch: projective Weierstrass X || Y || Z -> the 32 / 57-byte EdDSA encodings, status"""
         kl = 57 if self.clen == 56 else 32
@@ -705,6 +734,16 @@ class Curve:
     def rfc6979_nonce_dev(self, hash_type, n, d_privs, d_digests, d_nonces, d_status, stream=None):
         _chk(self.L, self.L.ec_rfc6979_nonce_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_digests, d_nonces, d_status, stream),
              "ec_rfc6979_nonce_batch_dev")
+
+    def eddsa_sign_msgs_dev(self, alg, n, d_secret_keys, d_pubkeys, adata, d_slots, stride, d_sigs, d_pub_out, d_status, stream=None):
+        """ec_eddsa_sign_msg_batch with device pointers (adata: host bytes or None; d_pubkeys, d_pub_out: a pointer or None)"""
+        _chk(self.L, self.L.ec_eddsa_sign_msg_batch_dev(self.ctx.h, self.h, alg, n, d_secret_keys, d_pubkeys, adata,
+                                                         len(adata) if adata is not None else 0, d_slots, stride, d_sigs, d_pub_out, d_status,
+                                                         stream), "ec_eddsa_sign_msg_batch_dev")
+
+    def eddsa_pub_keys_dev(self, n, d_secret_keys, d_pub_out, d_status, stream=None):
+        _chk(self.L, self.L.ec_eddsa_pub_key_batch_dev(self.ctx.h, self.h, n, d_secret_keys, d_pub_out, d_status, stream),
+             "ec_eddsa_pub_key_batch_dev")
 
     def decdsa_sign_dev(self, hash_type, n, d_privs, d_in, stride, is_digest, d_sigs, d_status, stream=None):
         _chk(self.L, self.L.ec_decdsa_sign_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_in, stride, 1 if is_digest else 0, d_sigs,

@@ -25,6 +25,7 @@
 #include "ecamd_schnorr.h"
 #include "ecamd_bign.h"
 #include "ecamd_rfc6979.h"
+#include "ecamd_eddsa_sign.h"
 
 // ------------------------------------------------------------------------------------------
 // error reporting
@@ -211,7 +212,7 @@ static const CurveRow g_curve_rows[] = {
 // ------------------------------------------------------------------------------------------
 // objects behind the opaque handles
 // ------------------------------------------------------------------------------------------
-#define ECAMD_NSTAGE 30   /* 24 .. 28: the batch-wide arrays of ec_schnorr_verify_msg_all_batch */
+#define ECAMD_NSTAGE 41   /* 24 .. 28: the batch-wide arrays of ec_schnorr_verify_msg_all_batch; 30 .. 40: ec_eddsa_sign_msg_batch */
 struct ecamd_ctx {
 	int device;
 	hipStream_t stream;
@@ -6108,6 +6109,249 @@ extern "C" int ec_eddsa_sign_S_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint
 		A.out = op[3];
 		HIPCHK(ecamd_launch_ed_sign_S(A, s));
 		return 0;
+	});
+}
+
+// ------------------------------------------------------------------------------------------
+// one-call EdDSA signing (include/libecc_amd.h: ec_eddsa_sign_msg_batch, ec_eddsa_pub_key_batch): eddsa_import_key_pair_from_priv_key_buf
+// (sig/eddsa.c:1028) + _eddsa_sign (:1554-1870) per item with every hash on the device (ecamd_eddsa_sign.hip).  Per chunk of at
+// most max_chunk items:
+//   k_eddsa_expand_r        h = H(sk), clamp, PH(M), r_hash: a into stage 30, r_hash into 31, a zero-extended into 32 (keys derived
+//                           here), PH(M) into 40, the slot check into 36.  30 - 32 are secret: ensure() wipes what it frees,
+//                           ecamd_ctx_wipe_scratch the rest
+//   eddsa_sign_R_dev_locked pubkeys == NULL: A = encode([a]B) from stage 32 (Ed448: a / 4 and the isogeny, as eddsa_init_pub_key :840
+//                           does with a >> 2) into pub_out or stage 39, its status into 38
+//   eddsa_sign_R_dev_locked R = encode([r]B) into stage 34, its status into 37
+//   k_eddsa_hram            H(dom || R || A || M-or-PH(M)) into stage 33, R into the signature
+//   k_ed_sign_S             S = r + hram a mod q into stage 35
+//   k_eddsa_sign_fin        S into the signature; status; zero bytes where the slot was bad
+// Only enqueues.
+// ------------------------------------------------------------------------------------------
+static void eddsa_front_args(EcamdEddsaSignArgs *E, const eced::Dom &dom)
+{
+	memset(E, 0, sizeof(*E));
+	E->dom_len = dom.len;
+	static_assert(sizeof(E->dom) == sizeof(dom.b), "the dom buffer of the kernel arguments");
+	memcpy(E->dom, dom.b, sizeof(E->dom));
+}
+
+static int eddsa_sign_msg_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEdSignArgs &T, int alg, const eced::Dom &dom, uint32_t n,
+				     const uint8_t *d_sk, const uint8_t *d_pub, const uint8_t *d_slots, uint32_t stride, uint8_t *d_sigs,
+				     uint8_t *d_pub_out, uint8_t *d_status, hipStream_t s)
+{
+	const size_t kl = T.is448 ? 57 : 32, hl = 2 * kl;
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	const bool derive = d_pub == nullptr, ph = eced::alg_is_ph(alg);
+	const size_t need[11] = {chunk * kl, chunk * hl, derive ? chunk * hl : 0, chunk * hl, chunk * kl, chunk * kl, chunk, chunk, derive ? chunk : 0,
+				 derive && !d_pub_out ? chunk * kl : 0, ph ? (size_t)chunk * eced::PH_LEN : 0};
+	for (int i = 0; i < 11; i++) {
+		if (need[i] && ensure(&ctx->stage[30 + i], &ctx->stage_bytes[30 + i], need[i])) {
+			return -1;
+		}
+	}
+	uint8_t **S = ctx->stage;
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		EcamdEddsaSignArgs E;
+		eddsa_front_args(&E, dom);
+		E.n = m;
+		E.sk = d_sk + off * kl;
+		E.slots = d_slots + (size_t)off * stride;
+		E.stride = stride;
+		E.a = S[30];
+		E.r_hash = S[31];
+		E.a_wide = derive ? S[32] : nullptr;
+		E.hram = S[33];
+		E.bad = S[36];
+		E.ph = ph ? S[40] : nullptr;
+		HIPCHK(ecamd_launch_eddsa_expand(alg, E, s));
+		const uint8_t *A_enc = derive ? nullptr : d_pub + off * kl;
+		if (derive) {
+			uint8_t *dst = d_pub_out ? d_pub_out + off * kl : S[39];
+			if (eddsa_sign_R_dev_locked(ctx, cv, T, m, S[32], dst, S[38], s)) {
+				return -1;
+			}
+			A_enc = dst;
+		} else if (d_pub_out) {
+			HIPCHK(hipMemcpyAsync(d_pub_out + off * kl, A_enc, m * kl, hipMemcpyDeviceToDevice, s));
+		}
+		if (eddsa_sign_R_dev_locked(ctx, cv, T, m, S[31], S[34], S[37], s)) {
+			return -1;
+		}
+		E.R = S[34];
+		E.A = A_enc;
+		E.sigs = d_sigs + off * 2 * kl;
+		HIPCHK(ecamd_launch_eddsa_hram(alg, E, s));
+		EcamdEdSignArgs G = T;
+		G.n = m;
+		G.r_hash = S[31];
+		G.hram = S[33];
+		G.a = S[30];
+		G.out = S[35];
+		HIPCHK(ecamd_launch_ed_sign_S(G, s));
+		E.S = S[35];
+		E.stR = S[37];
+		E.stA = derive ? S[38] : nullptr;
+		E.status = d_status + off;
+		HIPCHK(ecamd_launch_eddsa_sign_fin(alg, E, s));
+	}
+	return 0;
+}
+
+// stage: 30 a, 32 a zero-extended (both secret)
+static int eddsa_pub_key_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEdSignArgs &T, uint32_t n, const uint8_t *d_sk,
+				    uint8_t *d_pub_out, uint8_t *d_status, hipStream_t s)
+{
+	const size_t kl = T.is448 ? 57 : 32, hl = 2 * kl;
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	if (ensure(&ctx->stage[30], &ctx->stage_bytes[30], chunk * kl) || ensure(&ctx->stage[32], &ctx->stage_bytes[32], chunk * hl)) {
+		return -1;
+	}
+	const int alg = T.is448 ? eced::EDDSA448 : eced::EDDSA25519;   // the key expansion is the family's (sig/eddsa.c:650-671)
+	eced::Dom dom;
+	eced::dom_build(eced::EDDSA25519, nullptr, 0, &dom);
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		EcamdEddsaSignArgs E;
+		eddsa_front_args(&E, dom);
+		E.n = m;
+		E.sk = d_sk + off * kl;
+		E.a = ctx->stage[30];
+		E.a_wide = ctx->stage[32];
+		HIPCHK(ecamd_launch_eddsa_expand(alg, E, s));
+		if (eddsa_sign_R_dev_locked(ctx, cv, T, m, ctx->stage[32], d_pub_out + off * kl, d_status + off, s)) {
+			return -1;
+		}
+	}
+	return 0;
+}
+
+// the call-level checks of ec_eddsa_sign_msg_batch[_dev]; fills T and dom
+static int eddsa_msg_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const void *sk, const uint8_t *adata,
+			     uint32_t adata_len, const void *slots, uint32_t stride, const void *sigs, const void *status, EcamdEdSignArgs *T,
+			     eced::Dom *dom)
+{
+	if (!eced::alg_ok(alg)) {
+		return fail(std::string(fn) + ": alg must be EDDSA25519 (9), EDDSA25519CTX (10), EDDSA25519PH (11), EDDSA448 (12) or EDDSA448PH (13)");
+	}
+	if (!ctx) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (eddsa_sign_setup(fn, ctx, cv, 0, nullptr, nullptr, nullptr, T)) {
+		return -1;
+	}
+	if (eced::alg_is448(alg) != (T->is448 != 0)) {
+		return fail(std::string(fn) + ": EDDSA25519 / CTX / PH run on the WEI25519 handle, EDDSA448 / PH on the WEI448 handle");
+	}
+	if (eced::alg_takes_dom(alg)) {
+		if (alg == eced::EDDSA25519CTX && !adata) {
+			return fail(std::string(fn) + ": EDDSA25519CTX needs a context (sig/eddsa.c:1683)");
+		}
+		if (adata_len > (uint32_t)eced::MAX_ADATA) {
+			return fail(std::string(fn) + ": adata_len must be at most 255 (sig/eddsa.c:64)");
+		}
+	}
+	if (stride < 4 || (stride & 3u) || stride > 4096) {
+		return fail(std::string(fn) + ": msg_stride must be a multiple of 4 in 4 .. 4096");
+	}
+	if (n && (!sk || !slots || !sigs || !status)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	eced::dom_build(alg, adata, adata_len, dom);
+	return 0;
+}
+
+extern "C" int ec_eddsa_sign_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const void *d_secret_keys,
+					   const void *d_pubkeys, const uint8_t *adata, uint32_t adata_len, const void *d_msg_slots,
+					   uint32_t msg_stride, void *d_sigs, void *d_pub_out, void *d_status, void *hip_stream)
+{
+	if (!ctx) {
+		return fail("ec_eddsa_sign_msg_batch_dev: bad argument");
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	EcamdEdSignArgs T;
+	eced::Dom dom;
+	if (eddsa_msg_args_ok("ec_eddsa_sign_msg_batch_dev", ctx, cv, alg, n, d_secret_keys, adata, adata_len, d_msg_slots, msg_stride, d_sigs, d_status,
+			      &T, &dom)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return eddsa_sign_msg_dev_locked(ctx, cv, T, alg, dom, n, (const uint8_t *)d_secret_keys, (const uint8_t *)d_pubkeys, (const uint8_t *)d_msg_slots,
+					 msg_stride, (uint8_t *)d_sigs, (uint8_t *)d_pub_out, (uint8_t *)d_status, s);
+}
+
+extern "C" int ec_eddsa_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *secret_keys,
+				       const uint8_t *pubkeys, const uint8_t *adata, uint32_t adata_len, const uint8_t *msg_slots,
+				       uint32_t msg_stride, uint8_t *sigs, uint8_t *pub_out, uint8_t *status)
+{
+	if (!ctx) {
+		return fail("ec_eddsa_sign_msg_batch: bad argument");
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	EcamdEdSignArgs T;
+	eced::Dom dom;
+	if (eddsa_msg_args_ok("ec_eddsa_sign_msg_batch", ctx, cv, alg, n, secret_keys, adata, adata_len, msg_slots, msg_stride, sigs, status, &T, &dom)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t kl = T.is448 ? 57 : 32;
+	// the optional arrays keep their places: an array with neither pointer is neither copied nor read
+	const std::vector<HostArr> arrs = {{secret_keys, nullptr, kl}, {pubkeys, nullptr, pubkeys ? kl : 0}, {msg_slots, nullptr, msg_stride},
+					   {nullptr, sigs, 2 * kl},    {nullptr, pub_out, pub_out ? kl : 0}, {nullptr, status, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+						       hipStream_t s, const std::function<int()> &) {
+		return eddsa_sign_msg_dev_locked(ctx, cv, T, alg, dom, m, ip[0], ip[1], ip[2], msg_stride, op[3], op[4], op[5], s);
+	});
+}
+
+extern "C" int ec_eddsa_pub_key_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const void *d_secret_keys, void *d_pub_out,
+					  void *d_status, void *hip_stream)
+{
+	if (!ctx) {
+		return fail("ec_eddsa_pub_key_batch_dev: bad argument");
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	EcamdEdSignArgs T;
+	if (eddsa_sign_setup("ec_eddsa_pub_key_batch_dev", ctx, cv, n, d_secret_keys, d_pub_out, d_status, &T)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return eddsa_pub_key_dev_locked(ctx, cv, T, n, (const uint8_t *)d_secret_keys, (uint8_t *)d_pub_out, (uint8_t *)d_status, s);
+}
+
+extern "C" int ec_eddsa_pub_key_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *secret_keys, uint8_t *pub_out,
+				      uint8_t *status)
+{
+	if (!ctx) {
+		return fail("ec_eddsa_pub_key_batch: bad argument");
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	EcamdEdSignArgs T;
+	if (eddsa_sign_setup("ec_eddsa_pub_key_batch", ctx, cv, n, secret_keys, pub_out, status, &T)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	HIPCHK(hipSetDevice(ctx->device));
+	const size_t kl = T.is448 ? 57 : 32;
+	const std::vector<HostArr> arrs = {{secret_keys, nullptr, kl}, {nullptr, pub_out, kl}, {nullptr, status, 1}};
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
+						       hipStream_t s, const std::function<int()> &) {
+		return eddsa_pub_key_dev_locked(ctx, cv, T, m, ip[0], op[1], op[2], s);
 	});
 }
 

@@ -695,6 +695,34 @@ struct EcamdRfc6979Args {
 	uint32_t q[17];          // the generator's order, little-endian words
 };
 hipError_t ecamd_launch_rfc6979_nonce(int hash_type, const EcamdRfc6979Args &a, hipStream_t s);
+// the hashing front end of one-call EdDSA signing (ecamd_eddsa_sign.h / ecamd_eddsa_sign.hip); alg: libecc's ec_alg_type 9 .. 13,
+// klen = 32 / 57, hlen = 64 / 114.  Three steps share the structure:
+//   expand  (k_eddsa_expand_r)  sk, slots -> a, r_hash, a_wide (unless NULL), ph (PH variants), bad; slots == NULL: the key
+//           expansion alone (a, a_wide)
+//   hram    (k_eddsa_hram)      R, A, slots or ph -> hram; R into the first half of the item's signature
+//   fin     (k_eddsa_sign_fin)  S into the second half; an item with bad, stR or stA (may be NULL) set gets status 1 and zero bytes
+struct EcamdEddsaSignArgs {
+	const uint8_t *sk;       // expand: n x klen secret key octets
+	const uint8_t *slots;    // expand, hram: n message slots (u32 length, then the bytes)
+	uint32_t stride;
+	uint8_t *a;              // expand: n x klen clamped scalars, little-endian (secret)
+	uint8_t *a_wide;         // expand: NULL, or n x hlen: the same zero-extended, the `r_hash` whose [.]B is the public key (secret)
+	uint8_t *r_hash;         // expand: n x hlen (secret)
+	uint8_t *ph;             // PH variants: n x 64, written by expand, read by hram
+	uint8_t *bad;            // n: 1 where the slot's length does not fit the stride (written by expand, read by hram and fin)
+	const uint8_t *R, *A;    // hram: n x klen encodings
+	uint8_t *hram;           // hram: n x hlen
+	const uint8_t *S;        // fin: n x klen
+	const uint8_t *stR, *stA; // fin: n statuses of the two encodings (stA may be NULL)
+	uint8_t *sigs;           // hram, fin: n x 2 klen
+	uint8_t *status;         // fin: n
+	uint32_t n;
+	uint32_t dom_len;        // dom2 / dom4 of the call (eced::dom_build), zeros behind it
+	uint8_t dom[296];
+};
+hipError_t ecamd_launch_eddsa_expand(int alg, const EcamdEddsaSignArgs &a, hipStream_t s);
+hipError_t ecamd_launch_eddsa_hram(int alg, const EcamdEddsaSignArgs &a, hipStream_t s);
+hipError_t ecamd_launch_eddsa_sign_fin(int alg, const EcamdEddsaSignArgs &a, hipStream_t s);
 // Front end of ec_schnorr_verify_msg_all_batch (BIP0340 / ECFSDSA from keys, signatures and hash inputs; round 6), per chunk of m items:
 //   k_schnorr_prep  the imported key's x into the blank of the item's hash input (BIP0340), the key as the equation uses it (BIP0340: the
 //                   representative with an even y), s and the commitment (r, or W) into the batch-wide arrays; a key that did not import

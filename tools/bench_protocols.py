@@ -6,7 +6,7 @@ torch.distributed.run, weak scaling, contiguous shards, one RCCL all-gather of t
 bytes per step); not the driver's headline bench.  --workload ecdsa_recover is the exception: one GPU, recovery beside the
 verification of the same signatures in alternating windows (recover_row).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..4 --curve C]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..4 --curve C]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -672,14 +672,115 @@ def decdsa_row(a, ctx, dev, stream, rng, B):
     ctx.close()
 
 
+def eddsa_sign_row(a, ctx, dev, stream, rng, B):
+    """One-call EdDSA signing (ec_eddsa_sign_msg_batch_dev: key expansion, PH(M), r_hash and hram hashed on the device) on 32-byte
+    messages, device-resident, with the public keys supplied or (--derive-pub) derived on the device; beside it, in the same run and in
+    alternating windows of a.steps calls, the existing split path on the same items -- ec_eddsa_sign_R_batch + ec_eddsa_sign_S_batch,
+    which take HOST pointers (the split path has no device-pointer form), with r_hash, hram and the clamped scalars precomputed and
+    not timed.  Gates: --ref-items (at most 512) random signatures are the Python restatement's, all signatures equal the split
+    path's, and every signature is accepted by ec_eddsa_verify_batch.  One GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload eddsa_sign measures one GPU: run it with --gpus 1, outside torch.distributed.run")
+    import eddsa_sign_ref as E
+    alg = {"ed25519": E.EDDSA25519, "ed25519ctx": E.EDDSA25519CTX, "ed25519ph": E.EDDSA25519PH, "ed448": E.EDDSA448, "ed448ph": E.EDDSA448PH}[a.alg]
+    cv = ctx.curve(E.curve_of(alg))
+    kl, ml = E.klen(alg), 32
+    hl = 2 * kl
+    ad = b"bench" if E.takes_ctx(alg) else None
+    stride = 4 + ml
+    sks = rng.integers(0, 256, size=B * kl, dtype=np.uint8).tobytes()
+    msgs = rng.integers(0, 256, size=B * ml, dtype=np.uint8).tobytes()
+    slots = np.zeros((B, stride), dtype=np.uint8)
+    slots[:, 0] = ml
+    slots[:, 4:] = np.frombuffer(msgs, dtype=np.uint8).reshape(B, ml)
+
+    def t(b):
+        return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+    d_sk, d_slots = t(sks), t(slots.tobytes())
+    d_sig = torch.empty(B * 2 * kl, dtype=torch.uint8, device=dev)
+    d_pub = torch.empty(B * kl, dtype=torch.uint8, device=dev)
+    d_st = torch.empty(B, dtype=torch.uint8, device=dev)
+    sp = stream.cuda_stream
+    cv.eddsa_pub_keys_dev(B, d_sk.data_ptr(), d_pub.data_ptr(), d_st.data_ptr(), sp)
+    torch.cuda.synchronize()
+    pubs = bytes(d_pub.cpu().numpy())
+    if bytes(d_st.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: a public key was not derived")
+
+    def one_call():
+        cv.eddsa_sign_msgs_dev(alg, B, d_sk.data_ptr(), None if a.derive_pub else d_pub.data_ptr(), ad, d_slots.data_ptr(), stride,
+                               d_sig.data_ptr(), None, d_st.data_ptr(), sp)
+    # ---- the split path's inputs, on the host and not timed ----
+    sk_l = [sks[kl * i:kl * (i + 1)] for i in range(B)]
+    msg_l = [msgs[ml * i:ml * (i + 1)] for i in range(B)]
+    exp = [E.expand(alg, k) for k in sk_l]
+    a_sc = b"".join(e[0] for e in exp)
+    dom = E.dom(alg, ad or b"")
+    rh = b"".join(E.H(alg, dom + e[1] + E.PH(alg, m)) for e, m in zip(exp, msg_l))
+    Renc, stR = cv.eddsa_sign_R(rh)
+    hr = b"".join(E.H(alg, dom + Renc[kl * i:kl * (i + 1)] + pubs[kl * i:kl * (i + 1)] + E.PH(alg, msg_l[i])) for i in range(B))
+    split_out = {}
+
+    def split():
+        split_out["R"], split_out["st"] = cv.eddsa_sign_R(rh)
+        split_out["S"] = cv.eddsa_sign_S(rh, hr, a_sc)
+    # ---- gates ----
+    one_call()
+    torch.cuda.synchronize()
+    sig = bytes(d_sig.cpu().numpy())
+    if bytes(d_st.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: an item was not signed")
+    split()
+    Rn, Sn = np.frombuffer(split_out["R"], dtype=np.uint8).reshape(B, kl), np.frombuffer(split_out["S"], dtype=np.uint8).reshape(B, kl)
+    if np.concatenate([Rn, Sn], axis=1).tobytes() != sig or split_out["st"] != bytes(B):
+        raise SystemExit("PARITY FAILURE: the one-call signatures are not the split path's")
+    idx = [int(i) for i in np.sort(np.random.default_rng(2).choice(B, size=min(B, 512, max(1, a.ref_items)), replace=False))]
+    for i in idx:
+        A, s1 = E.py_sign(alg, sk_l[i], ad or b"", msg_l[i])
+        if A != pubs[kl * i:kl * (i + 1)] or s1 != sig[2 * kl * i:2 * kl * (i + 1)]:
+            raise SystemExit("PARITY FAILURE: item %d is not the restatement's" % i)
+    if cv.eddsa_verify(pubs, sig, hr) != bytes(B):
+        raise SystemExit("PARITY FAILURE: a signature the device made was rejected")
+    gate = "%d signatures and public keys as the Python restatement gives them; all 2^%d signatures equal the split path's and accepted" % (len(idx), a.batch_log2)
+    # ---- timing: alternating windows ----
+    for _ in range(a.warmup):
+        one_call()
+        split()
+    torch.cuda.synchronize()
+    to, tsp = [], []
+    for _ in range(3):
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            one_call()
+        torch.cuda.synchronize()
+        to.append((time.perf_counter() - t0) / a.steps)
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            split()
+        tsp.append((time.perf_counter() - t0) / a.steps)
+    mo, msp = float(np.median(to)), float(np.median(tsp))
+    print(json.dumps({"metric": "EdDSA signatures/sec (%s, one call, every hash on the device, public keys %s, 32-byte messages, batch=2^%d, device-resident)"
+                                % (a.alg, "derived on the device" if a.derive_pub else "supplied", a.batch_log2),
+                      "value": B / mo, "unit": "signatures/s", "one_call_ms": [1e3 * x for x in to],
+                      "split_path_host_pointers_same_run": {"value": B / msp, "unit": "signatures/s", "ms": [1e3 * x for x in tsp],
+                                                            "note": "ec_eddsa_sign_R_batch + ec_eddsa_sign_S_batch, hashes precomputed and not timed, host-to-device copies of 3 x hlen + klen bytes per item timed"},
+                      "one_call_over_split": msp / mo,
+                      "gate": gate,
+                      "config": {"workload": a.workload, "alg": a.alg, "derive_pub": bool(a.derive_pub), "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+    cv.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
-    ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa"],
-                    help="sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa",
+                                                    "ed25519", "ed25519ctx", "ed25519ph", "ed448", "ed448ph"],
+                    help="eddsa_sign: ed25519, ed25519ctx, ed25519ph, ed448, ed448ph; sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
     ap.add_argument("--hash", type=int, default=None, choices=[0, 1, 2, 3, 4, 16],
                     help="bign_verify / bign_sign: 0 the caller hashed (SHA-256 digests supplied), 16 (default) belt-hash of message slots on the device; "
                          "decdsa_sign: 1 .. 4, SHA-224 / 256 (default) / 384 / 512")
+    ap.add_argument("--derive-pub", action="store_true", help="eddsa_sign: pubkeys = NULL, A = encode([a]B) derived on the device (a second comb multiplication per item)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
@@ -743,6 +844,10 @@ def main():
         return bign_row(a, ctx, dev, stream, rng, B)
     if a.workload == "decdsa_sign":
         return decdsa_row(a, ctx, dev, stream, rng, B)
+    if a.workload == "eddsa_sign":
+        if not a.alg.startswith("ed"):
+            raise SystemExit("--workload eddsa_sign: --alg ed25519 | ed25519ctx | ed25519ph | ed448 | ed448ph")
+        return eddsa_sign_row(a, ctx, dev, stream, rng, B)
     if a.workload == "ecdsa_verify":
         curve = a.curve
         cv = ctx.curve(curve)
