@@ -57,6 +57,189 @@ struct Jac {
 	FZ Z;
 };
 
+// ---- inversion ----
+// P256_INV_FERMAT=1 brings back x^(p-2) (A/B builds: tools/build_variant.py); the default is the divstep inversion below.
+#ifndef P256_INV_FERMAT
+#define P256_INV_FERMAT 0
+#endif
+
+// Constant-time "safegcd" inversion (Bernstein-Yang divsteps, in the form of libsecp256k1's modinv32 with 29-bit limbs): no field
+// multiplication at all.  f = p, g = x, and (d, e) follow (f, g) mod p through the same 2x2 transition matrices, so that
+// d x = f e0 and e x = g e0 (mod p) hold throughout; once g = 0, f = +-1 and d = +-e0 / x.
+//   * State: nine signed 29-bit limbs each (limbs 0..7 in [0, 2^29), the top limb carries the sign); |f|, |g| <= p and d, e stay
+//     in (-2p, p).
+//   * A batch is SAFEGCD_N = 29 divsteps on the low words of f and g alone; it yields a matrix t = (u v; q r) with
+//     t (f, g) = 2^29 (f', g') and |u| + |v|, |q| + |r| <= 2^29, which is then applied to the full (f, g) (exact division) and to
+//     (d, e) mod p: a multiple m p is added that clears the low 29 bits.  p = -1 mod 2^87 makes m the low 29 bits of the sum
+//     itself, and m p = m (p + 1) - m costs four products, not nine (the multipliers of the Montgomery reduction again).
+//   * Count: the variant used starts at delta = 1/2 (zeta = -(delta + 1/2) = -1).  For it, 590 divsteps bring g to 0 for every
+//     odd modulus below 2^256 and every 0 <= g < f: proven by the convex-hull computation of P. Wuille
+//     (github.com/sipa/safegcd-bounds; libsecp256k1 doc/safegcd_implementation.md, whose modinv32 runs 20 x 30 = 600 on that
+//     ground).  Here SAFEGCD_BATCHES x SAFEGCD_N = 21 x 29 = 609 >= 590, ALWAYS all of them: no early exit, every choice is a
+//     mask (the values inverted derive from secret scalars in the masked mode).
+//   * x = 0 keeps g = 0 and d = 0 through every batch: inv(0) = 0, as x^(p-2) gives.
+// tests/test_p256_inv_host.py drives this code on the host against pow(x, p - 2, p) and checks g = 0, f = +-1 at the end.
+typedef int32_t i32;
+typedef int64_t i64;
+constexpr int SAFEGCD_N = 29;
+constexpr int SAFEGCD_BATCHES = 21;
+static_assert(SAFEGCD_N == W && SAFEGCD_N * SAFEGCD_BATCHES >= 590, "divstep count below the proven bound");
+struct DivMat {
+	i32 u, v, q, r;
+};
+
+// SAFEGCD_N divsteps on the low words; zeta = -(delta + 1/2).  Unsigned arithmetic throughout (wrap-around is meant).
+U29_FN i32 divsteps29(i32 zeta, u32 f, u32 g, DivMat &t)
+{
+	u32 u = 1, v = 0, q = 0, r = 1;
+#pragma unroll
+	for (int i = 0; i < SAFEGCD_N; i++) {
+		u32 m1 = (u32)(zeta >> 31);          // zeta < 0
+		const u32 m2 = 0u - (g & 1u);       // g odd
+		const u32 x = (f ^ m1) - m1, y = (u ^ m1) - m1, z = (v ^ m1) - m1;  // +-(f, u, v)
+		g += x & m2;
+		q += y & m2;
+		r += z & m2;
+		m1 &= m2;                            // swap: zeta < 0 and g odd
+		zeta = (i32)((u32)zeta ^ m1) - 1;    // -zeta - 2 or zeta - 1
+		f += g & m1;
+		u += q & m1;
+		v += r & m1;
+		g >>= 1;
+		u <<= 1;
+		v <<= 1;
+	}
+	t.u = (i32)u;
+	t.v = (i32)v;
+	t.q = (i32)q;
+	t.r = (i32)r;
+	return zeta;
+}
+
+// (f, g) <- t (f, g) / 2^29, exact
+U29_FN void safegcd_update_fg(i32 *f, i32 *g, const DivMat &t)
+{
+	i64 cf = (i64)t.u * f[0] + (i64)t.v * g[0];
+	i64 cg = (i64)t.q * f[0] + (i64)t.r * g[0];
+	cf >>= W;
+	cg >>= W;
+#pragma unroll
+	for (int i = 1; i < 9; i++) {
+		cf += (i64)t.u * f[i] + (i64)t.v * g[i];
+		cg += (i64)t.q * f[i] + (i64)t.r * g[i];
+		f[i - 1] = (i32)((u32)cf & MASK);
+		g[i - 1] = (i32)((u32)cg & MASK);
+		cf >>= W;
+		cg >>= W;
+	}
+	f[8] = (i32)cf;
+	g[8] = (i32)cg;
+}
+
+// (d, e) <- t (d, e) / 2^29 mod p, kept in (-2p, p)
+U29_FN void safegcd_update_de(i32 *d, i32 *e, const DivMat &t)
+{
+	constexpr i32 pq[9] = {0, 0, 0, (i32)P256::Q3, 0, 0, (i32)P256::Q6, (i32)P256::Q7, (i32)P256::Q8};  // p + 1
+	const i32 sd = d[8] >> 31, se = e[8] >> 31;
+	// multiples of p that bring a negative d / e back above -p ...
+	i32 md = (t.u & sd) + (t.v & se);
+	i32 me = (t.q & sd) + (t.r & se);
+	i64 cd = (i64)t.u * d[0] + (i64)t.v * e[0];
+	i64 ce = (i64)t.q * d[0] + (i64)t.r * e[0];
+	// ... lowered to m = the sum's low 29 bits (mod 2^29): sum + m p = sum - m + m (p + 1) is then a multiple of 2^29
+	md -= (i32)(((u32)md - (u32)cd) & MASK);
+	me -= (i32)(((u32)me - (u32)ce) & MASK);
+	cd -= md;
+	ce -= me;
+	cd >>= W;
+	ce >>= W;
+#pragma unroll
+	for (int i = 1; i < 9; i++) {
+		cd += (i64)t.u * d[i] + (i64)t.v * e[i];
+		ce += (i64)t.q * d[i] + (i64)t.r * e[i];
+		if (pq[i] != 0) {
+			cd += (i64)pq[i] * md;
+			ce += (i64)pq[i] * me;
+		}
+		d[i - 1] = (i32)((u32)cd & MASK);
+		e[i - 1] = (i32)((u32)ce & MASK);
+		cd >>= W;
+		ce >>= W;
+	}
+	d[8] = (i32)cd;
+	e[8] = (i32)ce;
+}
+
+// All SAFEGCD_BATCHES batches from f = p, g = x (0 <= x < p), d = 0, e = e0 (0 <= e0 < p); returns the number of divsteps done.
+U29_FN int safegcd_run(i32 *f, i32 *g, i32 *d, const u32 *x, const u32 *e0)
+{
+	i32 e[9];
+#pragma unroll
+	for (int i = 0; i < 9; i++) {
+		f[i] = (i32)P256::P[i];
+		g[i] = (i32)x[i];
+		d[i] = 0;
+		e[i] = (i32)e0[i];
+	}
+	i32 zeta = -1;
+	int steps = 0;
+#pragma unroll 1
+	for (int b = 0; b < SAFEGCD_BATCHES; b++) {
+		DivMat t;
+		zeta = divsteps29(zeta, (u32)f[0] | ((u32)f[1] << W), (u32)g[0] | ((u32)g[1] << W), t);
+		safegcd_update_de(d, e, t);
+		safegcd_update_fg(f, g, t);
+		steps += SAFEGCD_N;
+	}
+	return steps;
+}
+
+// d in (-2p, p), to be negated when f is negative  ->  the residue in [0, p)
+U29_FN Fcanon safegcd_normalize(i32 *d, i32 fsign)
+{
+	i32 add = d[8] >> 31;
+#pragma unroll
+	for (int i = 0; i < 9; i++) {
+		d[i] += (i32)P256::P[i] & add;  // now in (-p, p)
+	}
+	const i32 neg = fsign >> 31;
+#pragma unroll
+	for (int i = 0; i < 9; i++) {
+		d[i] = (d[i] ^ neg) - neg;
+	}
+#pragma unroll
+	for (int i = 0; i < 8; i++) {
+		d[i + 1] += d[i] >> W;
+		d[i] &= (i32)MASK;
+	}
+	add = d[8] >> 31;
+#pragma unroll
+	for (int i = 0; i < 9; i++) {
+		d[i] += (i32)P256::P[i] & add;
+	}
+#pragma unroll
+	for (int i = 0; i < 8; i++) {
+		d[i + 1] += d[i] >> W;
+		d[i] &= (i32)MASK;
+	}
+	Fcanon r;
+#pragma unroll
+	for (int i = 0; i < 9; i++) {
+		r.l[i] = (u32)d[i];
+	}
+	return r;
+}
+
+// x = a R  ->  a^-1 R:  the divsteps invert the integer a R, and e0 = R^2 mod p puts the result back into the Montgomery domain
+// for nothing (d = +-e0 / x = a^-1 R), where a Montgomery multiplication by R^3 mod p would otherwise follow.
+U29_FN Fmul inv_safegcd(const Fmul &x)
+{
+	const Fcanon xc = canonical(x);
+	i32 f[9], g[9], d[9];
+	safegcd_run(f, g, d, xc.l, K::R2);
+	return weaken<Fmul>(safegcd_normalize(d, f[8]));
+}
+
 // x^(p-2): e2, e4, e8, e16, e32 ladder then the 2^32, 2^128, 2^32, 2^16, 2^8, 2^4, 2^2, 2^2 tail
 // (255 squarings + 13 multiplications; exponent checked in tools/u29_consts.py)
 U29_FN Fmul sqr_n(Fmul x, int n)
@@ -68,7 +251,7 @@ U29_FN Fmul sqr_n(Fmul x, int n)
 	return x;
 }
 #define P256_MULW(a, b) weaken<Fmul>(mul(a, b))
-U29_FN Fmul inv(const Fmul &x)
+U29_FN Fmul inv_fermat(const Fmul &x)
 {
 	const Fmul e2 = P256_MULW(sqr_n(x, 1), x);
 	const Fmul e4 = P256_MULW(sqr_n(e2, 2), e2);
@@ -84,6 +267,15 @@ U29_FN Fmul inv(const Fmul &x)
 	r = P256_MULW(sqr_n(r, 2), e2);
 	r = P256_MULW(sqr_n(r, 2), x);
 	return r;
+}
+
+U29_FN Fmul inv(const Fmul &x)
+{
+#if P256_INV_FERMAT
+	return inv_fermat(x);
+#else
+	return inv_safegcd(x);
+#endif
 }
 
 // ---- doubling: (X, Y, Z) -> 2 (X, Y, Z) ----

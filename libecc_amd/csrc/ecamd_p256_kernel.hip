@@ -7,7 +7,8 @@
 //   * scalar: signed fixed window w = 4 over k' = k + 0x88...8 (digit = nibble - 8 in [-8, 7]),
 //     left to right, 4 doublings + 1 MIXED addition (8M + 3S) per window, AFFINE table [1..8]P;
 //     variable-base items take odd-digit windows over a co-Z table instead (section A2/B2/C2 below);
-//   * four kernels per batch, all inversions shared by Montgomery's trick over 8 items per lane:
+//   * four kernels per batch, all inversions (constant-time divsteps, ecamd_p256.h:inv) shared by Montgomery's trick over 8 items
+//     per lane:
 //       k_p256_table     import + on-curve check, Jacobian multiples 2P..8P
 //       k_p256_affine    table -> affine (one inversion per 56 table entries)
 //       k_p256_loop      the window loop, Jacobian result
@@ -43,12 +44,19 @@ static_assert(TAB_ITEM_WORDS * 4 <= P256_TAB_BYTES && STG_ITEM_QUADS <= P256_STG
 #define FIN_K 8                  /* items per lane in k_p256_finalize */
 #endif
 #ifndef AFF_K
-#define AFF_K 8                  /* items per lane in k_p256_affine (x 7 table entries each); 2/4/8 measured equal AT 2^20 items */
+#define AFF_K 8                  /* items per lane in k_p256_affine / k_p256_affine_coz */
 #endif
-// Items that share one Fermat inversion in the affine and finalisation kernels, chosen from the batch size (round 4): a lane's
-// inversion is a serial chain of 255 squarings, so the kernel wants every SIMD busy more than it wants the 1/8 share -- the strong-
-// scaling shards of a 2^20-item job (2^17 ... 2^19 items per GPU) and small batches keep the chip filled with 4 and 2 items per lane
-// (the generic units do the same, ecamd_g29_kernel.hip).  kmax: the compile-time A/B value (8).
+// Items that share one inversion in the affine and finalisation kernels, chosen from the batch size (round 4): a lane's inversion
+// is one serial chain (609 divsteps; 255 squarings with P256_INV_FERMAT), so the kernel wants every SIMD busy more than it wants
+// the 1/8 share -- the strong-scaling shards of a 2^20-item job (2^17 ... 2^19 items per GPU) and small batches keep the chip
+// filled with 4 and 2 items per lane (the generic units do the same, ecamd_g29_kernel.hip).  kmax: the compile-time A/B value (8).
+// Measured again with the divstep inversion (profiles/r11_p256_safegcd.md; -DAFF_K=k -DFIN_K=k builds, M scalar mults/s of the
+// step and affine_coz + finalize ms):
+//   2^20 items:  8: 78.13 (0.480 + 0.176)   4: 77.81 (0.455 + 0.220)   2: 76.81 (0.463 + 0.298)   -- 8 still wins the step
+//   2^19 items:  8: 76.16 (0.291 + 0.124)   4: 76.32 (0.256 + 0.136)   2: 75.75 (0.245 + 0.187)   -- 8 and 4 within the spread
+//   2^17 items:  4: 67.47 (0.098 + 0.055)   2: 68.04 (0.074 + 0.049)                               -- one run each
+// so the thresholds stay.  The two kernels no longer agree: the affine kernel alone is fastest at 4 (2^20) and 2 (below), the
+// finalisation at 8 down to 2^19; a split setting would be worth about 0.03 ms of the 13.4 ms step and was not measured.
 static inline int p256_items_per_inversion(uint32_t n, int kmax)
 {
 	const int k = n >= (1u << 19) ? 8 : (n >= (1u << 17) ? 4 : 2);

@@ -45,6 +45,26 @@ def inv_chain():
     return r
 
 
+# ---- the divstep inversion of ecamd_p256.h (inv_safegcd) ----
+SAFEGCD_N = W                 # divsteps per batch: one limb
+SAFEGCD_BATCHES = 21
+SAFEGCD_BOUND = 590           # divsteps that always suffice for a 256-bit modulus in the variant that starts at delta = 1/2
+SAFEGCD_E0 = R * R % p        # e starts here: d ends as +-e0 / (a R) = +-a^-1 R, back in the Montgomery domain
+
+
+def safegcd_checks():
+    """what the divstep inversion takes for granted about p and its constants"""
+    assert SAFEGCD_N * SAFEGCD_BATCHES >= SAFEGCD_BOUND and p < 2**256
+    # the multiple of p that clears a sum's low limb is the low limb itself: p^-1 = -1 mod 2^29 ...
+    assert pow(p, -1, 1 << SAFEGCD_N) == (1 << SAFEGCD_N) - 1
+    # ... and m p = m (p + 1) - m, with p + 1 on limbs 3, 6, 7 and 8 only
+    assert [i for i, v in enumerate(digits(p + 1)) if v] == [3, 6, 7, 8]
+    # the state fits nine signed limbs: |f|, |g| <= p and d, e in (-2p, p), top limb included
+    assert 2 * p < 1 << (W * (NL - 1) + 31)
+    x = 0x1234567 * R % p
+    assert pow(x, -1, p) * SAFEGCD_E0 % p == pow(0x1234567, -1, p) * R % p
+
+
 if __name__ == "__main__":
     print("p   ", [hex(v) for v in digits(p)])
     print("p+1 ", [hex(v) for v in digits(p + 1)])
@@ -55,3 +75,5 @@ if __name__ == "__main__":
     print(fmt("THREE_M", 3 * R % p))
     inv_chain()
     print("inversion chain ok")
+    safegcd_checks()
+    print(f"divstep inversion: {SAFEGCD_BATCHES} x {SAFEGCD_N} = {SAFEGCD_BATCHES * SAFEGCD_N} divsteps, e0 = R2")
