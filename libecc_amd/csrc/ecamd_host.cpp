@@ -212,7 +212,77 @@ static const CurveRow g_curve_rows[] = {
 // ------------------------------------------------------------------------------------------
 // objects behind the opaque handles
 // ------------------------------------------------------------------------------------------
-#define ECAMD_NSTAGE 41   /* 24 .. 28: the batch-wide arrays of ec_schnorr_verify_msg_all_batch; 30 .. 40: ec_eddsa_sign_msg_batch */
+// ------------------------------------------------------------------------------------------
+// The scratch slots of ecamd_ctx::stage[].  Every device core works in a FRAME: a set of named slots, sized by stage_need()
+// when the core starts and dead when it returns.  Frames of different cores share indices on purpose (one context runs one
+// call at a time, ctx->mu), so a buffer grown by one family serves the next.  This block is the one place that says which
+// frames exist, who uses them, and which may be live at the same time; two names with one value in frames that can be
+// live together are a bug.
+//
+//   frame (prefix)            slots         used by                                                live beside it
+//   HW_  hand-staged host     0..3          pt_batch, ec_prj_pt_op_batch_fmt, ec_prj_pt_unprotected_mult_batch, ec_fp_op_batch   nothing
+//   PF_  point formats        0..7          pt_fmt_batch                                           (smul_dev_locked: no slots)
+//   YX_  square roots         0..3          y_from_x_common                                        nothing
+//   MH_  EdDSA whole batch    0..3, 14      eddsa_msm_host_locked, eddsa448_msm_host_locked        EV_ 3..9, 12, 13 (Ed448 only: hence 14, not 3)
+//   MS_  Schnorr whole batch  0..4          schnorr_msm_host_locked                                nothing (the evaluation works in ctx->msm)
+//   XD_  X25519 / X448        2..5, 7, 8    xdh_dev_locked                                         nothing
+//   CD_  ECCCDH               3..8          ecccdh_dev_locked                                      nothing
+//   ST_  verification         3..15         two_mul_dev / two_mul_sum_dev and their callers: ecdsa_two_smul_dev, ecdsa_fused_g_dev,
+//                                           hsig_ / bign_ / schnorr_item_verify_dev_locked         ST_SLOTS.., ST_TARGET, SI_, EF_, BW_
+//   VP_  secp256r1 loop       3..5, 7       ecdsa_verify_dev_locked (ST_U, ST_V and VP_*); its redo pass is the ST_ frame, after it   ST_TARGET, EF_
+//   RC_  recovery             10..14        ecdsa_recover_dev_locked, on top of ST_U .. ST_FLAGS (it has no [q]Y pass and no W' of its own)
+//   SG_  signing              3..5, 7, 20   ecdsa_ / sig_ / hsig_ / bign_ / schnorr_item_sign_dev_locked, ec_ecdsa_sign_msg_batch,
+//                                           decdsa_sign_dev_locked (SG_NONCES)                     ST_FLAGS, ST_SLOTS, ST_DIGESTS, ST_BELT
+//   EV_  EdDSA verification   3..15, 18, 19 eddsa_verify_dev_locked, eddsa448_verify_dev_locked, eddsa448_msm_dev_locked   ST_DIGESTS (h), EP_, EB_, MH_
+//   SR_  EdDSA [r]B           3..5          eddsa_sign_R_dev_locked                                ES_ (it runs inside the one-call signing)
+//   EN_  EdDSA point encoding 3, 4          ec_eddsa_encode_point_batch                            nothing
+//   BL_  blinded scalars      12, 13        ec_prj_pt_mul_blind_batch                              (smul_dev_locked: no slots)
+//   EF_  projective ECDSA keys 12, 14..16   ecdsa_verify_host_fmt: the imported keys; the regrouped items of keys at infinity   ST_ 3..11, VP_, ST_DIGESTS, ST_TARGET
+//        slots and digests    16..18        ST_SLOTS, ST_DIGESTS, ST_BELT: the staged message slots and what is hashed from them, for every family
+//   SI_  Schnorr item extras  18, 20..23    schnorr_item_verify_dev_locked; 20 / 21 also ec_schnorr_verify_msg_all_batch's key import   ST_, BW_
+//   EP_  EdDSA projective     20..23        eddsa_verify_msg_prj_impl, per chunk                   EV_, EB_, ST_DIGESTS
+//   BW_  Schnorr batch-wide   24..28        ec_schnorr_verify_msg_all_batch: filed chunk by chunk, read when the last chunk is in,
+//                                           so they outlive every per-chunk frame of the call     SI_PRJ_*, ST_DIGESTS, ST_ (item-by-item fallback)
+//   EB_  EdDSA batch-wide     24..27        eddsa_verify_msg_prj_impl, the same way                EP_, EV_, ST_DIGESTS
+//        sig_target           29            ST_TARGET: the comparison target of ECGDSA / ECRDSA / SM2, beside ST_ and VP_
+//   ES_  one-call EdDSA sign  30..40        eddsa_sign_msg_dev_locked, eddsa_pub_key_dev_locked    SR_
+//
+// smul_dev_locked itself takes no slot (ctx->tbl, ctx->tbl_fast); host_pipeline stages in ctx->hbuf.
+// ------------------------------------------------------------------------------------------
+enum StageSlot {
+	HW_IN0 = 0, HW_IN1 = 1, HW_OUT = 2, HW_STATUS = 3,
+	PF_SCALARS = 0, PF_IN = 1, PF_AFF = 2, PF_PRE = 3, PF_RES = 4, PF_RST = 5, PF_OUT = 6, PF_OST = 7,
+	YX_IN = 0, YX_Y1 = 1, YX_Y2 = 2, YX_ST = 3,
+	MH_PUB = 0, MH_SIG = 1, MH_HRAM = 2, MH_VERDICTS = 3, MH_VERDICT448 = 14,
+	MS_S = 0, MS_NE = 1, MS_KEYS = 2, MS_VERDICTS = 3, MS_R = 4,
+	XD_SCALARS = 2, XD_POINTS = 3, XD_FLAGS = 4, XD_REC = 5, XD_OUT = 7, XD_STK = 8,
+	CD_OUT = 3, CD_ST = 4, CD_HQ = 5, CD_STH = 6, CD_QP = 7, CD_STSUB = 8,
+	// W' = [u]G + [v]Y: the multipliers, A = [u]G, B = [v]Y and their status bytes, the flag byte of the prep kernel, the status and the
+	// point of the [q]Y pass, W' and its status, and the sinks of k_recover_fin's second sum A - B
+	ST_U = 3, ST_V = 4, ST_A = 5, ST_B = 6, ST_STA = 7, ST_STB = 8, ST_FLAGS = 9, ST_SUB = 10, ST_QY = 11,
+	ST_W = 12, ST_WSINK = 13, ST_STW = 14, ST_STWSINK = 15,
+	VP_FLAGS = 5, VP_KEYS = 7,   // VP_KEYS: the zeroed points of rejected keys, then the key status
+	RC_YST = 10, RC_X = 11, RC_Y1 = 12, RC_Y2 = 13, RC_R = 14,
+	SG_KG = 3, SG_STKG = 4, SG_Y = 5, SG_STY = 7, SG_NONCES = 20,   // SG_Y, SG_STY: BIP0340's public key
+	// 3: the key as a Weierstrass point, or v and |u| of the half-length scalars; 13: the status of [h]A, or the lattice kernel's meta bytes
+	EV_A = 3, EV_R = 4, EV_FLAGSA = 5, EV_FLAGSR = 6, EV_FLAGSS = 7, EV_S = 8, EV_H = 9, EV_EDA = 10, EV_REC = 11,
+	EV_HA = 12, EV_STHA = 13, EV_SG = 14, EV_STSG = 15, EV_TBL = 18, EV_EDR = 19,
+	EV_NE = 12, EV_GATE = 13,    // eddsa448_msm_dev_locked: q - h, and the gate word with the piece's verdict behind it
+	SR_R = 3, SR_RW = 4, SR_STR = 5,
+	EN_AFF = 3, EN_PRE = 4,
+	BL_SCALARS = 12, BL_BAD = 13,
+	EF_AFF = 12, EF_INF_SIGS = 14, EF_INF_DATA = 15, EF_INF_RES = 16,
+	ST_SLOTS = 16, ST_DIGESTS = 17, ST_BELT = 18,
+	SI_KEY = 18, SI_PRJ_AFF = 20, SI_PRJ_ST = 21, SI_WPT = 22, SI_WST = 23,   // the key as the equation uses it; the projective import; ECFSDSA's W
+	EP_AFF = 20, EP_PRE = 21, EP_KEY = 22, EP_KST = 23,
+	BW_S = 24, BW_NE = 25, BW_KEYS = 26, BW_R = 27, BW_VERDICTS = 28,
+	EB_KEYS = 24, EB_SIGS = 25, EB_HRAM = 26, EB_MARKS = 27,
+	ST_TARGET = 29,
+	ES_A = 30, ES_RHASH = 31, ES_AWIDE = 32, ES_HRAM = 33, ES_R = 34, ES_S = 35, ES_BAD = 36, ES_STR = 37, ES_STA = 38, ES_AENC = 39, ES_PH = 40,
+	ECAMD_NSTAGE
+};
+static_assert(ECAMD_NSTAGE == ES_PH + 1, "ECAMD_NSTAGE counts the slots: the last frame ends the array");
+
 struct ecamd_ctx {
 	int device;
 	hipStream_t stream;
@@ -770,6 +840,22 @@ static int ensure(uint8_t **buf, size_t *have, size_t need)
 	*have = need;
 	return 0;
 }
+
+// Size slots of a frame by name (the StageSlot block above ecamd_ctx): ensured in the order given; 0 bytes asks for nothing.
+struct StageNeed {
+	StageSlot slot;
+	size_t bytes;
+};
+static int stage_need(ecamd_ctx *ctx, std::initializer_list<StageNeed> needs)
+{
+	for (const StageNeed &k : needs) {
+		if (ensure(&ctx->stage[k.slot], &ctx->stage_bytes[k.slot], k.bytes)) {
+			return -1;
+		}
+	}
+	return 0;
+}
+static int stage_need(ecamd_ctx *ctx, StageSlot slot, size_t bytes) { return stage_need(ctx, {{slot, bytes}}); }
 
 
 // ------------------------------------------------------------------------------------------
@@ -1690,6 +1776,13 @@ struct HostArr {
 	size_t stride;       // bytes per item
 };
 
+// what host_pipeline hands its core for one chunk: the item count, the device copies of the caller's arrays (index = position in `arrs`;
+// NULL where the array is not an input / output), the stream, and `between` (see below)
+using DevIn = std::vector<const uint8_t *>;
+using DevOut = std::vector<uint8_t *>;
+using Between = std::function<int()>;
+using HostCore = std::function<int(uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &between)>;
+
 template <class Core>
 static int host_pipeline(ecamd_ctx *ctx, int pbits, uint32_t n, const std::vector<HostArr> &arrs, Core core, uint32_t even_chunk = 0)
 {
@@ -1820,6 +1913,28 @@ static int host_pipeline(ecamd_ctx *ctx, int pbits, uint32_t n, const std::vecto
 	return 0;
 }
 
+// ------------------------------------------------------------------------------------------
+// The head of an entry point, after its own argument checks and the n == 0 return.  Device pointers: the lock, the device, the
+// caller's stream or the context's, the StreamScope, then body(s).  Host pointers: the lock, the device, host_pipeline.
+// Entry points that take the lock earlier (a setup step under it), drop it in between or open no scope keep their own head.
+// ------------------------------------------------------------------------------------------
+template <class Body>
+static int dev_call(ecamd_ctx *ctx, void *hip_stream, Body body)
+{
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
+	StreamScope scope(ctx, s);
+	return body(s);
+}
+
+static int host_call(ecamd_ctx *ctx, int pbits, uint32_t n, const std::vector<HostArr> &arrs, const HostCore &core)
+{
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	return host_pipeline(ctx, pbits, n, arrs, core);
+}
+
 extern "C" int ecamd_ctx_set_host_ready_hook(ecamd_ctx *ctx, ecamd_host_ready_fn fn, void *arg)
 {
 	if (!ctx) {
@@ -1844,12 +1959,10 @@ extern "C" int ec_prj_pt_mul_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, ui
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return smul_dev_locked(ctx, cv, n, (const uint8_t *)d_scalars, slen, (const uint8_t *)d_points,
-			       (uint8_t *)d_out, (uint8_t *)d_status, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return smul_dev_locked(ctx, cv, n, (const uint8_t *)d_scalars, slen, (const uint8_t *)d_points,
+				       (uint8_t *)d_out, (uint8_t *)d_status, s);
+	});
 }
 
 extern "C" int ec_prj_pt_mul_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *scalars,
@@ -1864,12 +1977,9 @@ extern "C" int ec_prj_pt_mul_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t plen = (size_t)2 * cv->clen;
 	const std::vector<HostArr> arrs = {{scalars, nullptr, slen}, {points, nullptr, plen}, {nullptr, out, plen}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return smul_dev_locked(ctx, cv, m, ip[0], slen, ip[1], op[2], op[3], s);
 	});
 }
@@ -1893,21 +2003,17 @@ extern "C" int ec_prj_pt_mul_blind_batch(ecamd_ctx *ctx, const ecamd_curve *cv, 
 	if (ow > 18 || (outlen + 3) / 4 > 72) {
 		return fail("ec_prj_pt_mul_blind_batch: blinded scalar too long");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t plen = (size_t)2 * cv->clen;
-	// stage: 12 blinded scalars, 13 "bad blind" flags (beside the host pipeline's own buffers)
 	const std::vector<HostArr> arrs = {{scalars, nullptr, slen}, {blinds, nullptr, blen}, {points, nullptr, plen}, {nullptr, out, plen}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op, hipStream_t s,
-					       const std::function<int()> &) {
-		if (ensure(&ctx->stage[12], &ctx->stage_bytes[12], (size_t)m * outlen) || ensure(&ctx->stage[13], &ctx->stage_bytes[13], m)) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		if (stage_need(ctx, BL_SCALARS, (size_t)m * outlen) || stage_need(ctx, BL_BAD, m)) {
 			return -1;
 		}
 		EcamdBlindArgs B;
 		B.m = ip[0];
 		B.b = ip[1];
-		B.out = ctx->stage[12];
-		B.bad = ctx->stage[13];
+		B.out = ctx->stage[BL_SCALARS];
+		B.bad = ctx->stage[BL_BAD];
 		B.n = m;
 		B.mlen = slen;
 		B.blen = blen;
@@ -1917,11 +2023,11 @@ extern "C" int ec_prj_pt_mul_blind_batch(ecamd_ctx *ctx, const ecamd_curve *cv, 
 			B.order[w] = w < cv->order.size() ? cv->order[w] : 0u;
 		}
 		HIPCHK(ecamd_launch_blind_scalar(B, s));
-		if (smul_dev_locked(ctx, cv, m, ctx->stage[12], outlen, ip[2], op[3], op[4], s)) {
+		if (smul_dev_locked(ctx, cv, m, ctx->stage[BL_SCALARS], outlen, ip[2], op[3], op[4], s)) {
 			return -1;
 		}
 		// a blind outside [1, #E) is not something the reference would have drawn: report it as an error of the item
-		HIPCHK(ecamd_launch_status_or(op[4], ctx->stage[13], op[3], (uint32_t)plen, m, s));
+		HIPCHK(ecamd_launch_status_or(op[4], ctx->stage[BL_BAD], op[3], (uint32_t)plen, m, s));
 		return 0;
 	});
 }
@@ -1938,33 +2044,33 @@ static int pt_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uin
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: stages by hand on the context's stream, and sizes its slots before the scope opens
 	HIPCHK(hipSetDevice(ctx->device));
 	const size_t plen = (size_t)2 * cv->clen;
-	if (ensure(&ctx->stage[0], &ctx->stage_bytes[0], (size_t)n * plen) ||
-	    ensure(&ctx->stage[1], &ctx->stage_bytes[1], (size_t)n * plen) ||
-	    ensure(&ctx->stage[2], &ctx->stage_bytes[2], (size_t)n * plen) ||
-	    ensure(&ctx->stage[3], &ctx->stage_bytes[3], (size_t)n)) {
+	if (stage_need(ctx, HW_IN0, (size_t)n * plen) ||
+	    stage_need(ctx, HW_IN1, (size_t)n * plen) ||
+	    stage_need(ctx, HW_OUT, (size_t)n * plen) ||
+	    stage_need(ctx, HW_STATUS, (size_t)n)) {
 		return -1;
 	}
 	hipStream_t s = ctx->stream;
 	StreamScope scope(ctx, s);
-	HIPCHK(hipMemcpyAsync(ctx->stage[0], p1, (size_t)n * plen, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(ctx->stage[HW_IN0], p1, (size_t)n * plen, hipMemcpyHostToDevice, s));
 	if (!dbl) {
-		HIPCHK(hipMemcpyAsync(ctx->stage[1], p2, (size_t)n * plen, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[HW_IN1], p2, (size_t)n * plen, hipMemcpyHostToDevice, s));
 	}
 	EcamdPtArgs A;
-	A.p1 = ctx->stage[0];
-	A.p2 = ctx->stage[1];
-	A.out = ctx->stage[2];
-	A.status = ctx->stage[3];
+	A.p1 = ctx->stage[HW_IN0];
+	A.p2 = ctx->stage[HW_IN1];
+	A.out = ctx->stage[HW_OUT];
+	A.status = ctx->stage[HW_STATUS];
 	A.n = n;
 	A.clen = (uint32_t)cv->clen;
 	A.dbl = dbl;
 	A.slot = cv->slot;
 	HIPCHK(ecamd_launch_pt(cv->nw, A, s));
-	HIPCHK(hipMemcpyAsync(out, ctx->stage[2], (size_t)n * plen, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipMemcpyAsync(status, ctx->stage[3], (size_t)n, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(out, ctx->stage[HW_OUT], (size_t)n * plen, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(status, ctx->stage[HW_STATUS], (size_t)n, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	return 0;
 }
@@ -1996,7 +2102,7 @@ extern "C" int ec_prj_pt_op_batch_fmt(ecamd_ctx *ctx, const ecamd_curve *cv, int
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: stages by hand on the context's stream, and sizes its slots before the scope opens
 	HIPCHK(hipSetDevice(ctx->device));
 	// the two predicates hand back one byte per item, the other operations a point
 	const size_t iw = (size_t)(in_fmt ? 3 : 2) * cv->clen, ow = op >= ECAMD_PT_OP_CMP ? 1 : (size_t)(out_fmt ? 3 : 2) * cv->clen;
@@ -2004,20 +2110,20 @@ extern "C" int ec_prj_pt_op_batch_fmt(ecamd_ctx *ctx, const ecamd_curve *cv, int
 	StreamScope scope(ctx, s);
 	for (uint32_t off = 0; off < n; off += ctx->max_chunk) {
 		const uint32_t m = (n - off) < ctx->max_chunk ? (n - off) : ctx->max_chunk;
-		if (ensure(&ctx->stage[0], &ctx->stage_bytes[0], (size_t)m * iw) || ensure(&ctx->stage[1], &ctx->stage_bytes[1], (size_t)m * iw) ||
-		    ensure(&ctx->stage[2], &ctx->stage_bytes[2], (size_t)m * ow) || ensure(&ctx->stage[3], &ctx->stage_bytes[3], (size_t)m)) {
+		if (stage_need(ctx, HW_IN0, (size_t)m * iw) || stage_need(ctx, HW_IN1, (size_t)m * iw) ||
+		    stage_need(ctx, HW_OUT, (size_t)m * ow) || stage_need(ctx, HW_STATUS, (size_t)m)) {
 			return -1;
 		}
-		HIPCHK(hipMemcpyAsync(ctx->stage[0], p1 + (size_t)off * iw, (size_t)m * iw, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[HW_IN0], p1 + (size_t)off * iw, (size_t)m * iw, hipMemcpyHostToDevice, s));
 		if (two) {
-			HIPCHK(hipMemcpyAsync(ctx->stage[1], p2 + (size_t)off * iw, (size_t)m * iw, hipMemcpyHostToDevice, s));
+			HIPCHK(hipMemcpyAsync(ctx->stage[HW_IN1], p2 + (size_t)off * iw, (size_t)m * iw, hipMemcpyHostToDevice, s));
 		}
 		EcamdPtfArgs A;
 		memset(&A, 0, sizeof(A));
-		A.p1 = ctx->stage[0];
-		A.p2 = ctx->stage[1];
-		A.out = ctx->stage[2];
-		A.status = ctx->stage[3];
+		A.p1 = ctx->stage[HW_IN0];
+		A.p2 = ctx->stage[HW_IN1];
+		A.out = ctx->stage[HW_OUT];
+		A.status = ctx->stage[HW_STATUS];
 		A.n = m;
 		A.clen = (uint32_t)cv->clen;
 		A.op = op;
@@ -2026,9 +2132,9 @@ extern "C" int ec_prj_pt_op_batch_fmt(ecamd_ctx *ctx, const ecamd_curve *cv, int
 		A.slot = cv->slot;
 		HIPCHK(ecamd_launch_ptf(cv->nw, A, s));
 		if (op != 2) {
-			HIPCHK(hipMemcpyAsync(out + (size_t)off * ow, ctx->stage[2], (size_t)m * ow, hipMemcpyDeviceToHost, s));
+			HIPCHK(hipMemcpyAsync(out + (size_t)off * ow, ctx->stage[HW_OUT], (size_t)m * ow, hipMemcpyDeviceToHost, s));
 		}
-		HIPCHK(hipMemcpyAsync(status + off, ctx->stage[3], (size_t)m, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipMemcpyAsync(status + off, ctx->stage[HW_STATUS], (size_t)m, hipMemcpyDeviceToHost, s));
 		HIPCHK(hipStreamSynchronize(s));
 	}
 	return 0;
@@ -2045,7 +2151,7 @@ extern "C" int ec_prj_pt_unprotected_mult_batch(ecamd_ctx *ctx, const ecamd_curv
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: stages by hand on the context's stream, and sizes its slots before the scope opens
 	HIPCHK(hipSetDevice(ctx->device));
 	const size_t iw = (size_t)(in_fmt ? 3 : 2) * cv->clen, ow = (size_t)(out_fmt ? 3 : 2) * cv->clen;
 	hipStream_t s = ctx->stream;
@@ -2053,18 +2159,18 @@ extern "C" int ec_prj_pt_unprotected_mult_batch(ecamd_ctx *ctx, const ecamd_curv
 	for (uint32_t off = 0; off < n; off += ctx->max_chunk) {
 		const uint32_t m = (n - off) < ctx->max_chunk ? (n - off) : ctx->max_chunk;
 		const size_t sbytes = scalar_stride ? (size_t)m * scalar_len : (size_t)scalar_len;
-		if (ensure(&ctx->stage[0], &ctx->stage_bytes[0], (size_t)m * iw) || ensure(&ctx->stage[1], &ctx->stage_bytes[1], sbytes) ||
-		    ensure(&ctx->stage[2], &ctx->stage_bytes[2], (size_t)m * ow) || ensure(&ctx->stage[3], &ctx->stage_bytes[3], (size_t)m)) {
+		if (stage_need(ctx, HW_IN0, (size_t)m * iw) || stage_need(ctx, HW_IN1, sbytes) ||
+		    stage_need(ctx, HW_OUT, (size_t)m * ow) || stage_need(ctx, HW_STATUS, (size_t)m)) {
 			return -1;
 		}
-		HIPCHK(hipMemcpyAsync(ctx->stage[0], points + (size_t)off * iw, (size_t)m * iw, hipMemcpyHostToDevice, s));
-		HIPCHK(hipMemcpyAsync(ctx->stage[1], scalars + (size_t)off * scalar_stride, sbytes, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[HW_IN0], points + (size_t)off * iw, (size_t)m * iw, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[HW_IN1], scalars + (size_t)off * scalar_stride, sbytes, hipMemcpyHostToDevice, s));
 		EcamdUnprotArgs A;
 		memset(&A, 0, sizeof(A));
-		A.points = ctx->stage[0];
-		A.scalars = ctx->stage[1];
-		A.out = ctx->stage[2];
-		A.status = ctx->stage[3];
+		A.points = ctx->stage[HW_IN0];
+		A.scalars = ctx->stage[HW_IN1];
+		A.out = ctx->stage[HW_OUT];
+		A.status = ctx->stage[HW_STATUS];
 		A.n = m;
 		A.clen = (uint32_t)cv->clen;
 		A.slen = scalar_len;
@@ -2073,8 +2179,8 @@ extern "C" int ec_prj_pt_unprotected_mult_batch(ecamd_ctx *ctx, const ecamd_curv
 		A.out_fmt = out_fmt;
 		A.slot = cv->slot;
 		HIPCHK(ecamd_launch_unprot(cv->nw, A, s));
-		HIPCHK(hipMemcpyAsync(out + (size_t)off * ow, ctx->stage[2], (size_t)m * ow, hipMemcpyDeviceToHost, s));
-		HIPCHK(hipMemcpyAsync(status + off, ctx->stage[3], (size_t)m, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipMemcpyAsync(out + (size_t)off * ow, ctx->stage[HW_OUT], (size_t)m * ow, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipMemcpyAsync(status + off, ctx->stage[HW_STATUS], (size_t)m, hipMemcpyDeviceToHost, s));
 		HIPCHK(hipStreamSynchronize(s));
 	}
 	return 0;
@@ -2092,28 +2198,28 @@ extern "C" int ec_fp_op_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int op, uin
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: stages by hand on the context's stream, and sizes its slots before the scope opens
 	HIPCHK(hipSetDevice(ctx->device));
 	const uint32_t nl = (uint32_t)(cv->pbits + 63) / 64;
 	const size_t bytes = (size_t)n * nl * 8;
-	if (ensure(&ctx->stage[0], &ctx->stage_bytes[0], bytes) || ensure(&ctx->stage[1], &ctx->stage_bytes[1], bytes) ||
-	    ensure(&ctx->stage[2], &ctx->stage_bytes[2], bytes)) {
+	if (stage_need(ctx, HW_IN0, bytes) || stage_need(ctx, HW_IN1, bytes) ||
+	    stage_need(ctx, HW_OUT, bytes)) {
 		return -1;
 	}
 	hipStream_t s = ctx->stream;
 	StreamScope scope(ctx, s);
-	HIPCHK(hipMemcpyAsync(ctx->stage[0], a, bytes, hipMemcpyHostToDevice, s));
-	HIPCHK(hipMemcpyAsync(ctx->stage[1], b, bytes, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(ctx->stage[HW_IN0], a, bytes, hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(ctx->stage[HW_IN1], b, bytes, hipMemcpyHostToDevice, s));
 	EcamdFpArgs A;
-	A.a = (const uint32_t *)ctx->stage[0];
-	A.b = (const uint32_t *)ctx->stage[1];
-	A.out = (uint32_t *)ctx->stage[2];
+	A.a = (const uint32_t *)ctx->stage[HW_IN0];
+	A.b = (const uint32_t *)ctx->stage[HW_IN1];
+	A.out = (uint32_t *)ctx->stage[HW_OUT];
 	A.n = n;
 	A.wstride = 2 * nl;
 	A.op = op;
 	A.slot = cv->slot;
 	HIPCHK(ecamd_launch_fp(cv->nw, A, s));
-	HIPCHK(hipMemcpyAsync(out, ctx->stage[2], bytes, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(out, ctx->stage[HW_OUT], bytes, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	return 0;
 }
@@ -2122,7 +2228,7 @@ extern "C" int ec_fp_op_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int op, uin
 // batched ECDSA verification (digest supplied by the caller)
 // ------------------------------------------------------------------------------------------
 // `alg` (SIG_ECDSA, or ECAMD_SIG_ECGDSA / ECRDSA / SM2) selects the front end of the three verification paths below; for the
-// three other schemes the back ends compare W'.x with the front end's comparison target (stage 29, in the layout of a signature
+// three other schemes the back ends compare W'.x with the front end's comparison target (ST_TARGET, in the layout of a signature
 // array) instead of the caller's signatures.  ECDSA: exactly the launches there were before `alg` existed.
 static const uint8_t *sig_target(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *d_sig, uint8_t **target)
 {
@@ -2130,14 +2236,111 @@ static const uint8_t *sig_target(ecamd_ctx *ctx, const ecamd_curve *cv, int alg,
 	if (alg == SIG_ECDSA) {
 		return d_sig;
 	}
-	if (ensure(&ctx->stage[29], &ctx->stage_bytes[29], (size_t)n * 2 * cv->qlen)) {
+	if (stage_need(ctx, ST_TARGET, (size_t)n * 2 * cv->qlen)) {
 		return nullptr;
 	}
-	*target = ctx->stage[29];
-	return ctx->stage[29];
+	*target = ctx->stage[ST_TARGET];
+	return ctx->stage[ST_TARGET];
 }
-// The reference's structure: two independent scalar multiplications and one addition per item.
-// All pointers are device pointers; intermediates live in stage[3..11].
+// ------------------------------------------------------------------------------------------
+// W' = [u]G + [v]Y, the body of every verification but EdDSA's and of public-key recovery, in the ST_ frame: the caller's prep
+// kernel has left u in ST_U, v in ST_V and its flag byte in ST_FLAGS.  Only enqueues; PublicScalars is the caller's.
+// ------------------------------------------------------------------------------------------
+// the slots both halves below work in, for chunks of `chunk` items; ST_SUB and up are sized by the callers, whose uses differ
+static int two_mul_need(ecamd_ctx *ctx, const ecamd_curve *cv, size_t chunk)
+{
+	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen;
+	return stage_need(ctx, {{ST_U, chunk * ql}, {ST_V, chunk * ql}, {ST_A, chunk * plen}, {ST_B, chunk * plen}, {ST_STA, chunk}, {ST_STB, chunk},
+				{ST_FLAGS, chunk}});
+}
+
+// A = [u]G into ST_A / ST_STA and B = [v]Y into ST_B / ST_STB: two independent prj_pt_mul, as in the reference (sig/ecdsa_common.c:788,793).
+// d_Y == NULL: every Y is the point at infinity, B is not computed.
+// subgroup: Y is a public key.  On a curve with a cofactor ec_pub_key_import_from_aff_buf also requires [q]Y == infinity
+// (sig/ec_key.c:199-205): one more pass with the broadcast scalar q (it sits behind the generator in HBM) into ST_QY / ST_SUB, and
+// a key outside the subgroup becomes an import error (status 1) in ST_STB for the final stage, on the device.
+// d_only: a status array; only the items marked ECAMD_STATUS_REDO in it are computed (by the complete-formula kernel), the others
+// keep what they have.
+static int two_mul_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, const uint8_t *d_Y, bool subgroup, const uint8_t *d_only, hipStream_t s)
+{
+	uint8_t **S = ctx->stage;
+	const size_t plen = (size_t)2 * cv->clen;
+	const uint32_t ql = (uint32_t)cv->qlen;
+	const bool redo = d_only != nullptr;
+	if (redo) {
+		// the marks select the lanes of the complete-formula kernel (A.only_redo)
+		HIPCHK(hipMemcpyAsync(S[ST_STA], d_only, m, hipMemcpyDeviceToDevice, s));
+		HIPCHK(hipMemcpyAsync(S[ST_STB], d_only, m, hipMemcpyDeviceToDevice, s));
+	}
+	if (smul_dev_locked(ctx, cv, m, S[ST_U], ql, nullptr, S[ST_A], S[ST_STA], s, 0xffffffffu, redo)) {
+		return -1;
+	}
+	if (!d_Y) {
+		HIPCHK(hipMemsetAsync(S[ST_B], 0, m * plen, s));
+		HIPCHK(hipMemsetAsync(S[ST_STB], 2, m, s));
+		return 0;
+	}
+	if (smul_dev_locked(ctx, cv, m, S[ST_V], ql, d_Y, S[ST_B], S[ST_STB], s, 0xffffffffu, redo)) {
+		return -1;
+	}
+	if (subgroup && big_cmp(cv->order, cv->q) != 0) {
+		if (redo) {
+			HIPCHK(hipMemcpyAsync(S[ST_SUB], d_only, m, hipMemcpyDeviceToDevice, s));
+		}
+		if (smul_dev_locked(ctx, cv, m, cv->d_gen + plen, ql, d_Y, S[ST_QY], S[ST_SUB], s, 0, redo)) {
+			return -1;
+		}
+		// ST_SUB holds 2 (infinity) for keys in the subgroup; anything else rejects: fold into stB
+		// (redo pass: items that were not marked keep their old result byte there, and the final stage skips them)
+		HIPCHK(ecamd_launch_status_require(S[ST_STB], S[ST_SUB], 2, m, s));
+	}
+	return 0;
+}
+
+// The two multiplications, then W' = A + B as affine bytes into out1 / st1: k_recover_fin, one shared inversion per eight items, and
+// k_recover_redo, the items with A or B at infinity or x_A = x_B on the complete formulas (nothing marked: a near-empty launch).
+// The kernels also write A - B into out2 / st2: recovery's second key; the verifications pass the sinks ST_WSINK / ST_STWSINK and
+// never read them.  d_yst: a second byte per item that, like ST_FLAGS, says "no sum for this item" when it is not zero.
+static int two_mul_sum_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, const uint8_t *d_Y, bool subgroup, const uint8_t *d_yst,
+			   uint8_t *out1, uint8_t *out2, uint8_t *st1, uint8_t *st2, hipStream_t s)
+{
+	if (two_mul_dev(ctx, cv, m, d_Y, subgroup, nullptr, s)) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	EcamdRecoverFinArgs F;
+	F.A = S[ST_A];
+	F.stA = S[ST_STA];
+	F.B = S[ST_B];
+	F.stB = S[ST_STB];
+	F.flags = S[ST_FLAGS];
+	F.yst = d_yst;
+	F.out1 = out1;
+	F.out2 = out2;
+	F.st1 = st1;
+	F.st2 = st2;
+	F.n = m;
+	F.clen = (uint32_t)cv->clen;
+	F.slot = cv->slot;
+	HIPCHK(ecamd_launch_recover_fin(cv->nw, F, s));
+	HIPCHK(ecamd_launch_recover_redo(cv->nw, F, s));
+	return 0;
+}
+// the verifications: a public key, W' into ST_W / ST_STW
+static int verify_sum_need(ecamd_ctx *ctx, const ecamd_curve *cv, size_t chunk)
+{
+	const size_t plen = (size_t)2 * cv->clen;
+	return two_mul_need(ctx, cv, chunk) || stage_need(ctx, {{ST_SUB, chunk}, {ST_QY, chunk * plen + 256}, {ST_W, chunk * plen},
+							       {ST_WSINK, chunk * plen}, {ST_STW, chunk}, {ST_STWSINK, chunk}});
+}
+static int verify_sum_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, const uint8_t *d_Y, hipStream_t s)
+{
+	uint8_t **S = ctx->stage;
+	return two_mul_sum_dev(ctx, cv, m, d_Y, true, S[ST_FLAGS], S[ST_W], S[ST_WSINK], S[ST_STW], S[ST_STWSINK], s);
+}
+
+// ECDSA the reference's way: two independent scalar multiplications and one addition per item (k_ecdsa_fin: x mod q == r over the
+// candidates r + j q < p).  All pointers are device pointers.
 // d_pub == NULL: every public key is the point at infinity (libecc imports (0 : 1 : 0) as a key, and its verification
 // then computes W' = uG + v*infinity = uG, sig/ecdsa_common.c:788-800): [u2]Y is not computed and W' = [u1]G.
 // d_only (may be d_res itself): a status array; only the items marked ECAMD_STATUS_REDO in it are verified (by the complete-formula
@@ -2156,22 +2359,18 @@ static int ecdsa_two_smul_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n,
 		}
 		return 0;
 	}
-	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen;
+	const size_t plen = (size_t)2 * cv->clen;
 	PublicScalars pub_scope(ctx);   // u1, u2 and the group order are public
-	// stage: 3 u1, 4 u2, 5 A, 6 B, 7 stA, 8 stB, 9 flags, 10 subgroup status, 11 q scalar / tmp
-	const size_t need[12] = {0, 0, 0, n * ql, n * ql, n * plen, n * plen, n, n, n, n, n * plen + 256};
-	for (int i = 3; i < 12; i++) {
-		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	if (two_mul_need(ctx, cv, n) || stage_need(ctx, {{ST_SUB, n}, {ST_QY, n * plen + 256}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	EcamdEcdsaPrepArgs P;
 	P.sigs = d_sig;
 	P.digests = d_dig;
-	P.u1 = S[3];
-	P.u2 = S[4];
-	P.flags = S[9];
+	P.u1 = S[ST_U];
+	P.u2 = S[ST_V];
+	P.flags = S[ST_FLAGS];
 	P.n = n;
 	P.qlen = (uint32_t)cv->qlen;
 	P.hlen = hlen;
@@ -2184,44 +2383,16 @@ static int ecdsa_two_smul_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n,
 		return -1;
 	}
 	HIPCHK(launch_ecdsa_prep(ctx, cv, P, s, alg, target));
-	const bool redo = d_only != nullptr;
-	if (redo) {
-		// the marks select the lanes of the complete-formula kernel (A.only_redo); the other items keep what they have
-		HIPCHK(hipMemcpyAsync(S[7], d_only, n, hipMemcpyDeviceToDevice, s));
-		HIPCHK(hipMemcpyAsync(S[8], d_only, n, hipMemcpyDeviceToDevice, s));
-	}
-	// uG and vY: two independent prj_pt_mul, as in the reference (sig/ecdsa_common.c:788,793)
-	if (smul_dev_locked(ctx, cv, n, S[3], (uint32_t)cv->qlen, nullptr, S[5], S[7], s, 0xffffffffu, redo)) {
+	if (two_mul_dev(ctx, cv, n, d_pub, true, d_only, s)) {
 		return -1;
-	}
-	if (!d_pub) {
-		HIPCHK(hipMemsetAsync(S[6], 0, n * plen, s));
-		HIPCHK(hipMemsetAsync(S[8], 2, n, s));   // [u2]Y = infinity
-	} else if (smul_dev_locked(ctx, cv, n, S[4], (uint32_t)cv->qlen, d_pub, S[6], S[8], s, 0xffffffffu, redo)) {
-		return -1;
-	}
-	if (d_pub && big_cmp(cv->order, cv->q) != 0) {
-		// cofactor != 1: ec_pub_key_import_from_aff_buf also requires [q]Y == infinity
-		// (sig/ec_key.c:199-205).  One more pass with the broadcast scalar q (it sits behind the generator in HBM); a key
-		// outside the subgroup is turned into an import error (status 1) for the final stage, on the device.
-		const uint8_t *qs = cv->d_gen + plen;
-		if (redo) {
-			HIPCHK(hipMemcpyAsync(S[10], d_only, n, hipMemcpyDeviceToDevice, s));
-		}
-		if (smul_dev_locked(ctx, cv, n, qs, (uint32_t)ql, d_pub, S[11], S[10], s, 0, redo)) {
-			return -1;
-		}
-		// S[10] holds 2 (infinity) for keys in the subgroup; anything else rejects: fold into stB
-		// (redo pass: items that were not marked keep their old result byte there, and the final stage skips them)
-		HIPCHK(ecamd_launch_status_require(S[8], S[10], 2, n, s));
 	}
 	EcamdEcdsaFinArgs Fn;
-	Fn.A = S[5];
-	Fn.stA = S[7];
-	Fn.B = S[6];
-	Fn.stB = S[8];
+	Fn.A = S[ST_A];
+	Fn.stA = S[ST_STA];
+	Fn.B = S[ST_B];
+	Fn.stB = S[ST_STB];
 	Fn.sigs = cmp_sig;
-	Fn.flags = S[9];
+	Fn.flags = S[ST_FLAGS];
 	Fn.result = d_res;
 	Fn.n = n;
 	Fn.clen = (uint32_t)cv->clen;
@@ -2337,12 +2508,9 @@ static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 	if (!sig_target(ctx, cv, alg, chunk, d_sig, &target)) {
 		return -1;
 	}
-	// stage: 3 u1, 4 u2, 5 W' affine, 7 its status, 8 "the other point is infinity", 9 flags
-	const size_t need[10] = {0, 0, 0, chunk * ql, chunk * ql, chunk * plen, 0, chunk, chunk, chunk};
-	for (int i = 3; i < 10; i++) {
-		if (need[i] && ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	// ST_A / ST_STA: the affine W' and its status; ST_STB says "the other point is infinity" for the final stage
+	if (stage_need(ctx, {{ST_U, chunk * ql}, {ST_V, chunk * ql}, {ST_A, chunk * plen}, {ST_STA, chunk}, {ST_STB, chunk}, {ST_FLAGS, chunk}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	uint32_t jmax = 0;
@@ -2358,9 +2526,9 @@ static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 		EcamdEcdsaPrepArgs P;
 		P.sigs = d_sig + (size_t)off * 2 * ql;
 		P.digests = d_dig + (size_t)off * hlen;
-		P.u1 = S[3];
-		P.u2 = S[4];
-		P.flags = S[9];
+		P.u1 = S[ST_U];
+		P.u2 = S[ST_V];
+		P.flags = S[ST_FLAGS];
 		P.n = m;
 		P.qlen = (uint32_t)cv->qlen;
 		P.hlen = hlen;
@@ -2373,17 +2541,17 @@ static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 			return -1;
 		}
 		HIPCHK(launch_ecdsa_prep(ctx, cv, P, s, alg, target));
-		if (smul_dev_locked(ctx, cv, m, S[4], (uint32_t)ql, d_pub + (size_t)off * plen, S[5], S[7], s, 0xffffffffu, false, S[3])) {
+		if (smul_dev_locked(ctx, cv, m, S[ST_V], (uint32_t)ql, d_pub + (size_t)off * plen, S[ST_A], S[ST_STA], s, 0xffffffffu, false, S[ST_U])) {
 			return -1;
 		}
-		HIPCHK(hipMemsetAsync(S[8], 2, m, s));
+		HIPCHK(hipMemsetAsync(S[ST_STB], 2, m, s));
 		EcamdEcdsaFinArgs Fn;
-		Fn.A = S[5];
-		Fn.stA = S[7];
-		Fn.B = S[5];            // never read: its status says infinity
-		Fn.stB = S[8];
+		Fn.A = S[ST_A];
+		Fn.stA = S[ST_STA];
+		Fn.B = S[ST_A];            // never read: its status says infinity
+		Fn.stB = S[ST_STB];
 		Fn.sigs = target ? target : d_sig + (size_t)off * 2 * ql;
-		Fn.flags = S[9];
+		Fn.flags = S[ST_FLAGS];
 		Fn.result = d_res + off;
 		Fn.n = m;
 		Fn.clen = (uint32_t)cv->clen;
@@ -2402,7 +2570,7 @@ static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 
 static int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_pub,
 				   const uint8_t *d_sig, const uint8_t *d_dig, uint32_t hlen, uint8_t *d_res, hipStream_t s,
-				   const std::function<int()> *between = nullptr, int alg = SIG_ECDSA)
+				   const Between *between = nullptr, int alg = SIG_ECDSA)
 {
 	if (!cv->is_p256 || !cv->d_gtab) {
 		if (fused_verify_ok(ctx, cv, n) ? ecdsa_fused_g_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s, alg)
@@ -2430,12 +2598,8 @@ static int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 	if (!sig_target(ctx, cv, alg, chunk, d_sig, &target)) {
 		return -1;
 	}
-	// stage: 3 u1, 4 u2, 5 flags, 7 zeroed points of rejected keys + key status
-	const size_t need[8] = {0, 0, 0, (size_t)chunk * 32, (size_t)chunk * 32, chunk, 0, (size_t)chunk * 64 + chunk};
-	for (int i = 3; i < 8; i++) {
-		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	if (stage_need(ctx, {{ST_U, (size_t)chunk * 32}, {ST_V, (size_t)chunk * 32}, {VP_FLAGS, chunk}, {VP_KEYS, (size_t)chunk * 64 + chunk}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	for (uint32_t off = 0; off < n; off += chunk) {
@@ -2443,9 +2607,9 @@ static int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 		EcamdEcdsaPrepArgs P;
 		P.sigs = d_sig + (size_t)off * 64;
 		P.digests = d_dig + (size_t)off * hlen;
-		P.u1 = S[3];
-		P.u2 = S[4];
-		P.flags = S[5];
+		P.u1 = S[ST_U];
+		P.u2 = S[ST_V];
+		P.flags = S[VP_FLAGS];
 		P.n = m;
 		P.qlen = 32;
 		P.hlen = hlen;
@@ -2462,15 +2626,15 @@ static int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 		memset(&K, 0, sizeof(K));
 		K.points = d_pub + (size_t)off * 64;
 		K.pstride = 64;
-		K.out = S[7];           // zeroed for rejected keys; otherwise unused
-		K.status = S[7] + (size_t)m * 64;
+		K.out = S[VP_KEYS];           // zeroed for rejected keys; otherwise unused
+		K.status = S[VP_KEYS] + (size_t)m * 64;
 		K.tbl = ctx->tbl_fast;
 		K.stg = ctx->tbl_fast + (size_t)((chunk + 63u) & ~63u) * (P256_TAB_BYTES / 4);
 		K.n = m;
 		K.clen = 32;
 		K.slot = cv->slot;
 		hipEvent_t *dom = (ctx->timing && off == 0) ? ctx->ev_dom : nullptr;
-		HIPCHK(ecamd_launch_verify_p256(K, S[3], S[4], target ? target : d_sig + (size_t)off * 64, S[5],
+		HIPCHK(ecamd_launch_verify_p256(K, S[ST_U], S[ST_V], target ? target : d_sig + (size_t)off * 64, S[VP_FLAGS],
 						cv->d_comb ? cv->d_comb : cv->d_gtab, cv->d_comb ? 1 : 0, cv->qdig, d_res + off, s, dom, prep_done));
 		ctx->ev_dom_valid = ctx->ev_dom_valid || (dom != nullptr);
 	}
@@ -2515,27 +2679,25 @@ extern "C" int ec_ecdsa_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, 
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return ecdsa_verify_dev_locked(ctx, cv, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs,
-				       (const uint8_t *)d_digests, hlen, (uint8_t *)d_result, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return ecdsa_verify_dev_locked(ctx, cv, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs,
+					       (const uint8_t *)d_digests, hlen, (uint8_t *)d_result, s);
+	});
 }
 
 // Messages instead of digests (round 4): `data` then holds one fixed-stride SLOT per item -- a little-endian u32 length and the
 // message bytes (ecamd_hash.hip) -- and the digests H(m) are computed on the device (hash_type: libecc's hash_alg_type numbers,
-// SHA224 = 1 ... SHA512 = 4) into stage 17 before the verification core runs; dig_out (host, n x digest length, may be NULL)
+// SHA224 = 1 ... SHA512 = 4) into ST_DIGESTS before the verification core runs; dig_out (host, n x digest length, may be NULL)
 // receives them for the callers that need a digest on the host again.
 static int ecdsa_hash_stage(ecamd_ctx *ctx, int hash_type, uint32_t m, const uint8_t *d_slots, uint32_t stride, uint32_t dlen, hipStream_t s)
 {
-	if (ensure(&ctx->stage[17], &ctx->stage_bytes[17], (size_t)m * dlen)) {
+	if (stage_need(ctx, ST_DIGESTS, (size_t)m * dlen)) {
 		return -1;
 	}
 	if (hash_type == 5) {
-		HIPCHK(ecamd_launch_shake256_slots(d_slots, stride, m, ctx->stage[17], dlen, dlen, s));   // SHAKE256, dlen octets of output
+		HIPCHK(ecamd_launch_shake256_slots(d_slots, stride, m, ctx->stage[ST_DIGESTS], dlen, dlen, s));   // SHAKE256, dlen octets of output
 	} else {
-		HIPCHK(ecamd_launch_sha2_slots(hash_type, d_slots, stride, m, ctx->stage[17], dlen, s));
+		HIPCHK(ecamd_launch_sha2_slots(hash_type, d_slots, stride, m, ctx->stage[ST_DIGESTS], dlen, s));
 	}
 	return 0;
 }
@@ -2549,18 +2711,15 @@ static int ecdsa_verify_host_aff(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t plen = (size_t)2 * cv->clen, slen2 = (size_t)2 * cv->qlen;
 	const std::vector<HostArr> arrs = {{pubkeys, nullptr, plen}, {sigs, nullptr, slen2}, {data, nullptr, data_stride}, {nullptr, result, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &between) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &between) {
 		const uint8_t *d_dig = ip[2];
 		if (hash_type) {
 			if (ecdsa_hash_stage(ctx, hash_type, m, ip[2], data_stride, hlen, s)) {
 				return -1;
 			}
-			d_dig = ctx->stage[17];
+			d_dig = ctx->stage[ST_DIGESTS];
 		}
 		return ecdsa_verify_dev_locked(ctx, cv, m, ip[0], ip[1], d_dig, hlen, op[3], s, &between);
 	});
@@ -2596,13 +2755,12 @@ static int ecdsa_verify_host_fmt(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t
 	{
 		// keys, signatures and digests go to the device once, chunk by chunk behind the double-buffered staging; the keys are
 		// imported and normalised there (k_prj_import) and the verification core consumes the affine form in HBM
-		std::lock_guard<std::mutex> lk(ctx->mu);
+		std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the lock is dropped for the host pass over the import status and retaken below
 		HIPCHK(hipSetDevice(ctx->device));
 		std::vector<HostArr> arrs = {{pubkeys, nullptr, 3 * (size_t)cv->clen}, {sigs, nullptr, sl}, {data, nullptr, data_stride},
 					     {nullptr, result, 1}, {nullptr, st.data(), 1}};
-		if (host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-						     hipStream_t s, const std::function<int()> &between) {
-			    if (ensure(&ctx->stage[12], &ctx->stage_bytes[12], (size_t)m * alen)) {
+		if (host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &between) {
+			    if (stage_need(ctx, EF_AFF, (size_t)m * alen)) {
 				    return -1;
 			    }
 			    const uint8_t *d_dig = ip[2];
@@ -2610,18 +2768,18 @@ static int ecdsa_verify_host_fmt(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t
 				    if (ecdsa_hash_stage(ctx, hash_type, m, ip[2], data_stride, hlen, s)) {
 					    return -1;
 				    }
-				    d_dig = ctx->stage[17];
+				    d_dig = ctx->stage[ST_DIGESTS];
 			    }
 			    EcamdPrjInArgs I;
 			    I.in = ip[0];
-			    I.aff = ctx->stage[12];
+			    I.aff = ctx->stage[EF_AFF];
 			    I.pre = op[4];
 			    I.n = m;
 			    I.clen = (uint32_t)cv->clen;
 			    I.for_mul = 0;
 			    I.slot = cv->slot;
 			    HIPCHK(launch_prj_import(cv, I, s));
-			    return ecdsa_verify_dev_locked(ctx, cv, m, ctx->stage[12], ip[1], d_dig, hlen, op[3], s, &between);
+			    return ecdsa_verify_dev_locked(ctx, cv, m, ctx->stage[EF_AFF], ip[1], d_dig, hlen, op[3], s, &between);
 		    })) {
 			return -1;
 		}
@@ -2656,28 +2814,25 @@ static int ecdsa_verify_host_fmt(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t
 	}
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	HIPCHK(hipSetDevice(ctx->device));
-	const size_t gneed[3] = {(size_t)r * sl, (size_t)r * dl, r};
-	for (int i = 0; i < 3; i++) {
-		if (ensure(&ctx->stage[14 + i], &ctx->stage_bytes[14 + i], gneed[i])) {
-			return -1;
-		}
+	if (stage_need(ctx, {{EF_INF_SIGS, (size_t)r * sl}, {EF_INF_DATA, (size_t)r * dl}, {EF_INF_RES, r}})) {
+		return -1;
 	}
 	hipStream_t s = ctx->stream;
 	StreamScope scope(ctx, s);
 	uint8_t **S = ctx->stage;
-	HIPCHK(hipMemcpyAsync(S[14], hs.data(), hs.size(), hipMemcpyHostToDevice, s));
-	HIPCHK(hipMemcpyAsync(S[15], hd.data(), hd.size(), hipMemcpyHostToDevice, s));
-	const uint8_t *d_dig = S[15];
+	HIPCHK(hipMemcpyAsync(S[EF_INF_SIGS], hs.data(), hs.size(), hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(S[EF_INF_DATA], hd.data(), hd.size(), hipMemcpyHostToDevice, s));
+	const uint8_t *d_dig = S[EF_INF_DATA];
 	if (hash_type) {
-		if (ecdsa_hash_stage(ctx, hash_type, r, S[15], data_stride, hlen, s)) {
+		if (ecdsa_hash_stage(ctx, hash_type, r, S[EF_INF_DATA], data_stride, hlen, s)) {
 			return -1;
 		}
-		d_dig = S[17];
+		d_dig = S[ST_DIGESTS];
 	}
-	if (ecdsa_two_smul_dev(ctx, cv, r, nullptr, S[14], d_dig, hlen, S[16], s)) {
+	if (ecdsa_two_smul_dev(ctx, cv, r, nullptr, S[EF_INF_SIGS], d_dig, hlen, S[EF_INF_RES], s)) {
 		return -1;
 	}
-	HIPCHK(hipMemcpyAsync(hr.data(), S[16], r, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(hr.data(), S[EF_INF_RES], r, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	for (uint32_t j = 0; j < r; j++) {
 		result[inf[j]] = hr[j];
@@ -2708,7 +2863,7 @@ extern "C" int ec_ecdsa_verify_msg_batch_fmt(ecamd_ctx *ctx, const ecamd_curve *
 // ------------------------------------------------------------------------------------------
 // batched ECDSA signing with caller-supplied nonces
 // ------------------------------------------------------------------------------------------
-// Device core of ECDSA signing: every pointer a device pointer; kG and its status live in stage[3], stage[4].
+// Device core of ECDSA signing: every pointer a device pointer; kG and its status live in SG_KG, SG_STKG.
 static int ecdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_privs,
 				 const uint8_t *d_nonces, const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs,
 				 uint8_t *d_status, hipStream_t s)
@@ -2724,19 +2879,19 @@ static int ecdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t
 		}
 		return 0;
 	}
-	if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], n * plen) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], n)) {
+	if (stage_need(ctx, SG_KG, n * plen) || stage_need(ctx, SG_STKG, n)) {
 		return -1;
 	}
 	uint8_t **S = ctx->stage;
-	if (smul_dev_locked(ctx, cv, n, d_nonces, (uint32_t)ql, nullptr, S[3], S[4], s)) {  // kG (:479)
+	if (smul_dev_locked(ctx, cv, n, d_nonces, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {  // kG (:479)
 		return -1;
 	}
 	EcamdEcdsaSignArgs A;
 	A.privs = d_privs;
 	A.nonces = d_nonces;
 	A.digests = d_digests;
-	A.kG = S[3];
-	A.stkG = S[4];
+	A.kG = S[SG_KG];
+	A.stkG = S[SG_STKG];
 	A.sigs = d_sigs;
 	A.status = d_status;
 	A.n = n;
@@ -2783,12 +2938,10 @@ extern "C" int ec_ecdsa_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, ui
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return ecdsa_sign_dev_locked(ctx, cv, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_digests,
-				     hlen, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return ecdsa_sign_dev_locked(ctx, cv, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_digests,
+					     hlen, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
 }
 
 extern "C" int ec_ecdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *privs,
@@ -2801,13 +2954,10 @@ extern "C" int ec_ecdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t ql = (size_t)cv->qlen;
 	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {digests, nullptr, hlen},
 					   {nullptr, sigs, 2 * ql}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return ecdsa_sign_dev_locked(ctx, cv, m, ip[0], ip[1], ip[2], hlen, op[3], op[4], s);
 	});
 }
@@ -2834,12 +2984,10 @@ extern "C" int ec_sig_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, in
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return ecdsa_verify_dev_locked(ctx, cv, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_digests, hlen,
-				       (uint8_t *)d_result, s, nullptr, alg);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return ecdsa_verify_dev_locked(ctx, cv, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_digests, hlen,
+					       (uint8_t *)d_result, s, nullptr, alg);
+	});
 }
 
 extern "C" int ec_sig_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *pubkeys, const uint8_t *sigs,
@@ -2851,17 +2999,14 @@ extern "C" int ec_sig_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int al
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t plen = (size_t)2 * cv->clen, slen2 = (size_t)2 * cv->qlen;
 	const std::vector<HostArr> arrs = {{pubkeys, nullptr, plen}, {sigs, nullptr, slen2}, {digests, nullptr, hlen}, {nullptr, result, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &between) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &between) {
 		return ecdsa_verify_dev_locked(ctx, cv, m, ip[0], ip[1], ip[2], hlen, op[3], s, &between, alg);
 	});
 }
 
-// Device core of signing: every pointer a device pointer; [k]G and its status live in stage[3], stage[4] as for ECDSA.
+// Device core of signing: every pointer a device pointer; [k]G and its status live in SG_KG, SG_STKG as for ECDSA.
 static int sig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
 			       const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
 {
@@ -2876,19 +3021,19 @@ static int sig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, u
 		}
 		return 0;
 	}
-	if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], n * plen) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], n)) {
+	if (stage_need(ctx, SG_KG, n * plen) || stage_need(ctx, SG_STKG, n)) {
 		return -1;
 	}
 	uint8_t **S = ctx->stage;
-	if (smul_dev_locked(ctx, cv, n, d_nonces, (uint32_t)ql, nullptr, S[3], S[4], s)) {  // [k]G, secret-scalar mode as the context says
+	if (smul_dev_locked(ctx, cv, n, d_nonces, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {  // [k]G, secret-scalar mode as the context says
 		return -1;
 	}
 	EcamdSigSignArgs A;
 	A.a.privs = d_privs;
 	A.a.nonces = d_nonces;
 	A.a.digests = d_digests;
-	A.a.kG = S[3];
-	A.a.stkG = S[4];
+	A.a.kG = S[SG_KG];
+	A.a.stkG = S[SG_STKG];
 	A.a.sigs = d_sigs;
 	A.a.status = d_status;
 	A.a.n = n;
@@ -2921,12 +3066,10 @@ extern "C" int ec_sig_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int 
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return sig_sign_dev_locked(ctx, cv, alg, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_digests, hlen,
-				   (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return sig_sign_dev_locked(ctx, cv, alg, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_digests, hlen,
+					   (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
 }
 
 extern "C" int ec_sig_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *privs, const uint8_t *nonces,
@@ -2938,13 +3081,10 @@ extern "C" int ec_sig_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg,
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t ql = (size_t)cv->qlen;
 	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {digests, nullptr, hlen},
 					   {nullptr, sigs, 2 * ql}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return sig_sign_dev_locked(ctx, cv, alg, m, ip[0], ip[1], ip[2], hlen, op[3], op[4], s);
 	});
 }
@@ -2992,12 +3132,9 @@ extern "C" int ec_nn_random_mod_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uin
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t ql = (size_t)cv->qlen;
 	const std::vector<HostArr> arrs = {{raw, nullptr, 2 * ql}, {nullptr, out, ql}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return rand_mod_dev_locked(ctx, cv, m, ip[0], op[1], s);
 	});
 }
@@ -3018,15 +3155,12 @@ extern "C" int ec_ecdsa_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, ui
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t ql = (size_t)cv->qlen;
 	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonce_raw, nullptr, 2 * ql}, {msg_slots, nullptr, msg_stride},
 					   {nullptr, sigs, 2 * ql}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
-		// stage 20: the nonces (secret: ensure() wipes what it frees, ecamd_ctx_wipe_scratch the rest); 17: the digests
-		if (ensure(&ctx->stage[20], &ctx->stage_bytes[20], (size_t)m * ql) || rand_mod_dev_locked(ctx, cv, m, ip[1], ctx->stage[20], s)) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		// SG_NONCES: secret (ensure() wipes what it frees, ecamd_ctx_wipe_scratch the rest)
+		if (stage_need(ctx, SG_NONCES, (size_t)m * ql) || rand_mod_dev_locked(ctx, cv, m, ip[1], ctx->stage[SG_NONCES], s)) {
 			return -1;
 		}
 		const uint8_t *d_dig = ip[2];
@@ -3034,17 +3168,17 @@ extern "C" int ec_ecdsa_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, ui
 			if (ecdsa_hash_stage(ctx, hash_type, m, ip[2], msg_stride, hlen, s)) {
 				return -1;
 			}
-			d_dig = ctx->stage[17];
+			d_dig = ctx->stage[ST_DIGESTS];
 		}
-		return ecdsa_sign_dev_locked(ctx, cv, m, ip[0], ctx->stage[20], d_dig, hlen, op[3], op[4], s);
+		return ecdsa_sign_dev_locked(ctx, cv, m, ip[0], ctx->stage[SG_NONCES], d_dig, hlen, op[3], op[4], s);
 	});
 }
 
 // ------------------------------------------------------------------------------------------
 // deterministic ECDSA (include/libecc_amd.h: ec_rfc6979_nonce_batch, ec_decdsa_sign_batch): the nonce of RFC 6979 section 3.2
 // derived on the device (k_rfc6979_nonce, ecamd_rfc6979.hip), then the ECDSA signing core.  Per chunk of at most max_chunk items:
-//   k_sha2_slots       in_is_digest = 0: h1 = H(m) into stage 17
-//   k_rfc6979_nonce    k into stage 20 (secret: ensure() wipes what it frees, ecamd_ctx_wipe_scratch the rest); a slot whose length
+//   k_sha2_slots       in_is_digest = 0: h1 = H(m) into ST_DIGESTS
+//   k_rfc6979_nonce    k into SG_NONCES (secret: ensure() wipes what it frees, ecamd_ctx_wipe_scratch the rest); a slot whose length
 //                      does not fit gets k = 0
 //   ecdsa_sign_dev_locked   [k]G as the context's secret-scalar mode says, r, s; k = 0 is status 1 with zero bytes
 // Only enqueues.
@@ -3098,12 +3232,10 @@ extern "C" int ec_rfc6979_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv,
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return rfc6979_nonce_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_digests, nullptr, 0, (uint8_t *)d_nonces,
-					(uint8_t *)d_status, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return rfc6979_nonce_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_digests, nullptr, 0, (uint8_t *)d_nonces,
+						(uint8_t *)d_status, s);
+	});
 }
 
 extern "C" int ec_rfc6979_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
@@ -3118,13 +3250,10 @@ extern "C" int ec_rfc6979_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t ql = (size_t)cv->qlen;
 	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {digests, nullptr, (size_t)ecrfc::hash_size(hash_type)}, {nullptr, nonces, ql},
 					   {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-						       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return rfc6979_nonce_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], nullptr, 0, op[2], op[3], s);
 	});
 }
@@ -3135,7 +3264,7 @@ static int decdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int has
 	const size_t ql = (size_t)cv->qlen;
 	const uint32_t hlen = (uint32_t)ecrfc::hash_size(hash_type);
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (ensure(&ctx->stage[20], &ctx->stage_bytes[20], (size_t)chunk * ql)) {
+	if (stage_need(ctx, SG_NONCES, (size_t)chunk * ql)) {
 		return -1;
 	}
 	for (uint32_t off = 0; off < n; off += chunk) {
@@ -3145,12 +3274,12 @@ static int decdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int has
 			if (ecdsa_hash_stage(ctx, hash_type, m, in, stride, hlen, s)) {
 				return -1;
 			}
-			d_dig = ctx->stage[17];
+			d_dig = ctx->stage[ST_DIGESTS];
 		}
 		// (the nonce kernel's status lands in the caller's status bytes and is replaced by the signing core's: a zero nonce is status 1 there)
-		if (rfc6979_nonce_dev_locked(ctx, cv, hash_type, m, d_privs + off * ql, d_dig, in_is_digest ? nullptr : in, stride, ctx->stage[20],
+		if (rfc6979_nonce_dev_locked(ctx, cv, hash_type, m, d_privs + off * ql, d_dig, in_is_digest ? nullptr : in, stride, ctx->stage[SG_NONCES],
 					     d_status + off, s) ||
-		    ecdsa_sign_dev_locked(ctx, cv, m, d_privs + off * ql, ctx->stage[20], d_dig, hlen, d_sigs + off * 2 * ql, d_status + off, s)) {
+		    ecdsa_sign_dev_locked(ctx, cv, m, d_privs + off * ql, ctx->stage[SG_NONCES], d_dig, hlen, d_sigs + off * 2 * ql, d_status + off, s)) {
 			return -1;
 		}
 	}
@@ -3184,12 +3313,10 @@ extern "C" int ec_decdsa_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, i
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return decdsa_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_in, in_stride, in_is_digest, (uint8_t *)d_sigs,
-				      (uint8_t *)d_status, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return decdsa_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_in, in_stride, in_is_digest, (uint8_t *)d_sigs,
+					      (uint8_t *)d_status, s);
+	});
 }
 
 extern "C" int ec_decdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *in,
@@ -3201,12 +3328,9 @@ extern "C" int ec_decdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int h
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t ql = (size_t)cv->qlen;
 	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {in, nullptr, in_stride}, {nullptr, sigs, 2 * ql}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-						       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return decdsa_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], in_stride, in_is_digest, op[2], op[3], s);
 	});
 }
@@ -3225,12 +3349,9 @@ extern "C" int ec_key_pair_gen_raw_batch(ecamd_ctx *ctx, const ecamd_curve *cv, 
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t ql = (size_t)cv->qlen, plen = (size_t)2 * cv->clen;
 	const std::vector<HostArr> arrs = {{raw, nullptr, 2 * ql}, {nullptr, priv_out, ql}, {nullptr, pub_out, plen}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		if (rand_mod_dev_locked(ctx, cv, m, ip[0], op[1], s)) {
 			return -1;
 		}
@@ -3241,7 +3362,7 @@ extern "C" int ec_key_pair_gen_raw_batch(ecamd_ctx *ctx, const ecamd_curve *cv, 
 // ------------------------------------------------------------------------------------------
 // batched ECC-CDH (ecccdh_derive_secret, ecdh/ecccdh.c:167-233)
 // ------------------------------------------------------------------------------------------
-// Device core: stage 3 [d]Q', 4 its status, 5 [h]Q, 6 status of [h]Q, 7 [q]Q (discarded), 8 its status.
+// Device core: CD_OUT / CD_ST [d]Q' and its status, CD_HQ / CD_STH [h]Q, CD_QP / CD_STSUB [q]Q (discarded) and its status.
 static int ecccdh_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_privs,
 			     const uint8_t *d_peers, uint8_t *d_secrets, uint8_t *d_status, hipStream_t s)
 {
@@ -3257,11 +3378,9 @@ static int ecccdh_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 		return 0;
 	}
 	const bool cof = cv->cofactor != 1;
-	const size_t need[9] = {0, 0, 0, n * plen, n, cof ? n * plen : 0, cof ? n : 0, cof ? n * plen : 0, cof ? n : 0};
-	for (int i = 3; i < 9; i++) {
-		if (need[i] && ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	if (stage_need(ctx, {{CD_OUT, n * plen}, {CD_ST, n}, {CD_HQ, cof ? n * plen : 0}, {CD_STH, cof ? n : 0}, {CD_QP, cof ? n * plen : 0},
+			     {CD_STSUB, cof ? n : 0}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	EcamdCdhArgs A;
@@ -3274,22 +3393,22 @@ static int ecccdh_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 		// sig/ec_key.c:199-205), then Q' = [h]Q must not be infinity, then [d]Q'
 		const uint8_t *d_q = cv->d_gen + plen, *d_h = d_q + ql;
 		PublicScalars pub_scope(ctx);   // the order and the cofactor are public; the private key below is not
-		if (smul_dev_locked(ctx, cv, n, d_q, (uint32_t)ql, d_peers, S[7], S[8], s, 0) ||
-		    smul_dev_locked(ctx, cv, n, d_h, 1, d_peers, S[5], S[6], s, 0)) {
+		if (smul_dev_locked(ctx, cv, n, d_q, (uint32_t)ql, d_peers, S[CD_QP], S[CD_STSUB], s, 0) ||
+		    smul_dev_locked(ctx, cv, n, d_h, 1, d_peers, S[CD_HQ], S[CD_STH], s, 0)) {
 			return -1;
 		}
-		A.st_sub = S[8];
-		A.st_h = S[6];
-		A.hq = S[5];
+		A.st_sub = S[CD_STSUB];
+		A.st_h = S[CD_STH];
+		A.hq = S[CD_HQ];
 		HIPCHK(ecamd_launch_cdh_gate(A, s));
-		pts_in = S[5];
+		pts_in = S[CD_HQ];
 	}
 	// cofactor 1: import + prj_pt_mul + prj_pt_unique in one pass
-	if (smul_dev_locked(ctx, cv, n, d_privs, (uint32_t)ql, pts_in, S[3], S[4], s)) {
+	if (smul_dev_locked(ctx, cv, n, d_privs, (uint32_t)ql, pts_in, S[CD_OUT], S[CD_ST], s)) {
 		return -1;
 	}
-	A.pts = S[3];
-	A.st = S[4];
+	A.pts = S[CD_OUT];
+	A.st = S[CD_ST];
 	A.secrets = d_secrets;
 	A.status = d_status;
 	HIPCHK(ecamd_launch_cdh_fin(A, s));
@@ -3317,12 +3436,10 @@ extern "C" int ec_ecccdh_derive_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv,
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return ecccdh_dev_locked(ctx, cv, n, (const uint8_t *)d_privs, (const uint8_t *)d_peers, (uint8_t *)d_secrets,
-				 (uint8_t *)d_status, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return ecccdh_dev_locked(ctx, cv, n, (const uint8_t *)d_privs, (const uint8_t *)d_peers, (uint8_t *)d_secrets,
+					 (uint8_t *)d_status, s);
+	});
 }
 
 extern "C" int ec_ecccdh_derive_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *privs,
@@ -3334,13 +3451,10 @@ extern "C" int ec_ecccdh_derive_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uin
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen;
 	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {peers, nullptr, plen}, {nullptr, secrets, (size_t)cv->clen},
 					   {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return ecccdh_dev_locked(ctx, cv, m, ip[0], ip[1], op[2], op[3], s);
 	});
 }
@@ -3466,35 +3580,31 @@ static int xdh_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, const uin
 		return 0;
 	}
 	const size_t len = (size_t)cv->clen, plen = 2 * len;
-	// stage: 2 scalars BE, 3 points, 4 flags, 7 [k]Q, 8 stk   (0, 1, 9, 10 belong to the host-pointer wrapper)
-	const size_t need[ECAMD_NSTAGE] = {0, 0, n * len, n * plen, n, 0, 0, n * plen, n};
-	for (int i = 0; i < ECAMD_NSTAGE; i++) {
-		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	if (stage_need(ctx, {{XD_SCALARS, n * len}, {XD_POINTS, n * plen}, {XD_FLAGS, n}, {XD_OUT, n * plen}, {XD_STK, n}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	const int nw = cv->nw;
 	EcamdXdhPrepArgs P = cv->xdh_tmpl;
 	P.k = d_k;
 	P.u = d_u;
-	P.scalars = S[2];
-	P.points = S[3];
-	P.flags = S[4];
+	P.scalars = S[XD_SCALARS];
+	P.points = S[XD_POINTS];
+	P.flags = S[XD_FLAGS];
 	P.n = n;
 	if (cv->gflavour == 2 && cv->gslot >= 0) {
 		// X25519 on the radix-2^29 field of the 2^255 - 19 unit: validation + clamping, then the x-only
 		// Montgomery ladder with a shared inversion (the u coordinate is all the reference exposes)
 		HIPCHK(ecamd_launch_xdh_prep_c25519(P, cv->gslot, s));
 		if (getenv("ECAMD_NO_X25519_LADDER") == nullptr) {
-			if (ensure(&ctx->stage[5], &ctx->stage_bytes[5], (size_t)n * ECAMD_XDH_REC_WORDS * 4)) {
+			if (stage_need(ctx, XD_REC, (size_t)n * ECAMD_XDH_REC_WORDS * 4)) {
 				return -1;
 			}
 			EcamdXdhLadderArgs L;
 			L.u = d_u;
-			L.scalars = S[2];
-			L.flags = S[4];
-			L.rec = (uint32_t *)S[5];
+			L.scalars = S[XD_SCALARS];
+			L.flags = S[XD_FLAGS];
+			L.rec = (uint32_t *)S[XD_REC];
 			L.out = d_out;
 			L.status = d_status;
 			L.n = n;
@@ -3506,14 +3616,14 @@ static int xdh_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, const uin
 		HIPCHK(ecamd_launch_xdh_prep_c448(P, cv->gslot, s));   // X448: the same front end on the Goldilocks radix-2^29 field
 		if (getenv("ECAMD_NO_X448_LADDER") == nullptr) {
 			// and the x-only Montgomery ladder with a shared inversion, as for X25519
-			if (ensure(&ctx->stage[5], &ctx->stage_bytes[5], (size_t)n * ECAMD_X448_REC_WORDS * 4)) {
+			if (stage_need(ctx, XD_REC, (size_t)n * ECAMD_X448_REC_WORDS * 4)) {
 				return -1;
 			}
 			EcamdXdhLadderArgs L;
 			L.u = d_u;
-			L.scalars = S[2];
-			L.flags = S[4];
-			L.rec = (uint32_t *)S[5];
+			L.scalars = S[XD_SCALARS];
+			L.flags = S[XD_FLAGS];
+			L.rec = (uint32_t *)S[XD_REC];
 			L.out = d_out;
 			L.status = d_status;
 			L.n = n;
@@ -3525,14 +3635,14 @@ static int xdh_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, const uin
 		HIPCHK(ecamd_launch_xdh_prep(nw, P, s));
 	}
 	// [k]Q  ([h]Q != infinity was checked by the prep kernel)
-	if (smul_dev_locked(ctx, cv, n, S[2], (uint32_t)len, S[3], S[7], S[8], s)) {
+	if (smul_dev_locked(ctx, cv, n, S[XD_SCALARS], (uint32_t)len, S[XD_POINTS], S[XD_OUT], S[XD_STK], s)) {
 		return -1;
 	}
 	EcamdXdhFinArgs Fn;
 	memset(&Fn, 0, sizeof(Fn));
-	Fn.pts = S[7];
-	Fn.stk = S[8];
-	Fn.flags = S[4];
+	Fn.pts = S[XD_OUT];
+	Fn.stk = S[XD_STK];
+	Fn.flags = S[XD_FLAGS];
 	Fn.out = d_out;
 	Fn.status = d_status;
 	Fn.n = n;
@@ -3565,7 +3675,7 @@ extern "C" int ec_xdh_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32
 	if (!ctx) {
 		return fail("ec_xdh_batch_dev: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	if (xdh_args_ok("ec_xdh_batch_dev", ctx, cv_in, n, d_k, d_u, d_out, d_status)) {
 		return -1;
 	}
@@ -3585,7 +3695,7 @@ extern "C" int ec_xdh_batch(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n
 	if (!ctx) {
 		return fail("ec_xdh_batch: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	if (xdh_args_ok("ec_xdh_batch", ctx, cv_in, n, k, u, out, status)) {
 		return -1;
 	}
@@ -3596,8 +3706,7 @@ extern "C" int ec_xdh_batch(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n
 	ecamd_curve *cv = const_cast<ecamd_curve *>(cv_in);
 	const size_t len = (size_t)cv->clen;
 	const std::vector<HostArr> arrs = {{k, nullptr, len}, {u, nullptr, len}, {nullptr, out, len}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return xdh_dev_locked(ctx, cv, m, ip[0], ip[1], op[2], op[3], s);
 	});
 }
@@ -3785,14 +3894,9 @@ static int eddsa_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 	}
 	const size_t len = 32, plen = 64;
 	const uint32_t cof_dbl = cv->ed_cof_dbl;
-	// stage: 3 A (Weierstrass), 4 R, 5 flagsA, 6 flagsR, 7 flagsS, 8 S, 9 h, 12 [h]A, 13 sthA, 14 [S]G, 15 stSG
-	//        (0..2 and 16 belong to the host-pointer wrapper)
-	const size_t need[ECAMD_NSTAGE] = {0, 0, 0, n * plen, n * plen, n, n, n, n * len, n * len,
-					   0, 0, n * plen, n, n * plen, n, 0, 0};
-	for (int i = 0; i < ECAMD_NSTAGE; i++) {
-		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	if (stage_need(ctx, {{EV_A, n * plen}, {EV_R, n * plen}, {EV_FLAGSA, n}, {EV_FLAGSR, n}, {EV_FLAGSS, n}, {EV_S, n * len}, {EV_H, n * len},
+			     {EV_HA, n * plen}, {EV_STHA, n}, {EV_SG, n * plen}, {EV_STSG, n}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	const int nw = cv->nw;
@@ -3802,25 +3906,25 @@ static int eddsa_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 	D.strideA = (uint32_t)len;
 	D.encR = d_sig;
 	D.strideR = (uint32_t)plen;
-	D.pointsA = S[3];
-	D.pointsR = S[4];
-	D.flagsA = S[5];
-	D.flagsR = S[6];
+	D.pointsA = S[EV_A];
+	D.pointsR = S[EV_R];
+	D.flagsA = S[EV_FLAGSA];
+	D.flagsR = S[EV_FLAGSR];
 	D.cof_dbl = cof_dbl;
 	const bool unit25519 = cv->gflavour == 2 && cv->gslot >= 0;
 	const bool edwards_hA = unit25519 && getenv("ECAMD_NO_EDWARDS_SMUL") == nullptr;
 	D.edA = nullptr;
 	if (edwards_hA) {
-		// stage 10: A on the Edwards curve, 11: extended result records, 18: window tables
-		if (ensure(&ctx->stage[10], &ctx->stage_bytes[10], (size_t)n * 20 * 4) ||
-		    ensure(&ctx->stage[11], &ctx->stage_bytes[11], (size_t)n * ECAMD_EDR_REC_WORDS * 4) ||
-		    ensure(&ctx->stage[18], &ctx->stage_bytes[18], (size_t)n * ECAMD_EDT_ITEM_WORDS * 4)) {
+		// A on the Edwards curve, extended result records, window tables
+		if (stage_need(ctx, EV_EDA, (size_t)n * 20 * 4) ||
+		    stage_need(ctx, EV_REC, (size_t)n * ECAMD_EDR_REC_WORDS * 4) ||
+		    stage_need(ctx, EV_TBL, (size_t)n * ECAMD_EDT_ITEM_WORDS * 4)) {
 			return -1;
 		}
-		D.edA = (uint32_t *)S[10];
+		D.edA = (uint32_t *)S[EV_EDA];
 	}
 	// Edwards path: R's map to the Weierstrass model rides on the shared inversion of k_ed_hA_fin instead of costing the
-	// decode kernel an inversion per item (stage 19: R on the Edwards curve)
+	// decode kernel an inversion per item (EV_EDR: R on the Edwards curve)
 	const bool late_map = edwards_hA && getenv("ECAMD_NO_ED_LATE_MAP") == nullptr;
 	// round 4: the whole tail on the Edwards curve ([S]B from the Edwards comb table; no map, no inversion, no Weierstrass pass)
 	bool ed_tail = false;
@@ -3830,22 +3934,22 @@ static int eddsa_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 	}
 	// round 4, second step: half-length scalars (k_ed_lat) and one window loop over the tables of A and R (k_ed_smul2_c25519)
 	const bool lattice = ed_tail && len == 32 && getenv("ECAMD_NO_ED_LATTICE") == nullptr;
-	if (lattice && ensure(&ctx->stage[18], &ctx->stage_bytes[18], (size_t)n * 2 * ECAMD_EDT_ITEM_WORDS * 4)) {
+	if (lattice && stage_need(ctx, EV_TBL, (size_t)n * 2 * ECAMD_EDT_ITEM_WORDS * 4)) {
 		return -1;
 	}
 	// k_ed_lat (S < q, h mod q, the truncated Euclid: integer work with data-dependent trip counts, 0.43 VALU busy) beside the decode
 	// kernel (two square-root chains, MAD bound) on the side stream: both read only the caller's arrays.  $ECAMD_NO_ED_LAT_BESIDE: in line.
 	bool lat_beside = false;
-	EcamdEdLatArgs L;   // stage 3 (n x 64, free on this path): v and |u|, 12 words per item; 9: s' = u S mod q; 13: meta
+	EcamdEdLatArgs L;   // EV_A (n x 64, free on this path): v and |u|, 12 words per item; EV_H: s' = u S mod q; EV_STHA: meta
 	memset(&L, 0, sizeof(L));
 	if (lattice) {
 		L.sigs = d_sig;
 		L.hram = d_hram;
-		L.S_be = S[8];
-		L.sp_be = S[9];
-		L.uv = (uint32_t *)S[3];
-		L.meta = S[13];
-		L.flags = S[7];
+		L.S_be = S[EV_S];
+		L.sp_be = S[EV_H];
+		L.uv = (uint32_t *)S[EV_A];
+		L.meta = S[EV_STHA];
+		L.flags = S[EV_FLAGSS];
 		L.n = n;
 		L.hlen = hram_len;
 		L.qslot = cv->qslot;
@@ -3858,10 +3962,10 @@ static int eddsa_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 		}
 	}
 	if (late_map) {
-		if (ensure(&ctx->stage[19], &ctx->stage_bytes[19], (size_t)n * 20 * 4)) {
+		if (stage_need(ctx, EV_EDR, (size_t)n * 20 * 4)) {
 			return -1;
 		}
-		D.edR = (uint32_t *)ctx->stage[19];
+		D.edR = (uint32_t *)ctx->stage[EV_EDR];
 		HIPCHK(ecamd_launch_ed_decode_ed_c25519(D, cv->gslot, s));
 	} else if (unit25519) {
 		HIPCHK(ecamd_launch_ed_decode_c25519(D, cv->gslot, s));  // the same decoding on the radix-2^29 field
@@ -3876,29 +3980,29 @@ static int eddsa_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 		}
 		EcamdEdSmul2Args E;
 		memset(&E, 0, sizeof(E));
-		E.edA = (const uint32_t *)S[10];
-		E.edR = (const uint32_t *)ctx->stage[19];
-		E.flagsA = S[5];
-		E.flagsR = S[6];
-		E.flagsS = S[7];
-		E.uv = (const uint32_t *)S[3];
-		E.meta = S[13];
-		E.tbl = (uint32_t *)ctx->stage[18];
-		E.rec = (uint32_t *)S[11];
+		E.edA = (const uint32_t *)S[EV_EDA];
+		E.edR = (const uint32_t *)ctx->stage[EV_EDR];
+		E.flagsA = S[EV_FLAGSA];
+		E.flagsR = S[EV_FLAGSR];
+		E.flagsS = S[EV_FLAGSS];
+		E.uv = (const uint32_t *)S[EV_A];
+		E.meta = S[EV_STHA];
+		E.tbl = (uint32_t *)ctx->stage[EV_TBL];
+		E.rec = (uint32_t *)S[EV_REC];
 		E.n = n;
 		memcpy(E.g_2d, cv->ed_2d, sizeof(E.g_2d));
 		HIPCHK(ecamd_launch_ed_smul2_c25519(E, cv->gslot, s, ctx->timing ? ctx->ev_dom : nullptr));
 		ctx->ev_dom_valid = ctx->ev_dom_valid || ctx->timing;
 		EcamdEdTailArgs T;
 		memset(&T, 0, sizeof(T));
-		T.rec = (const uint32_t *)S[11];
-		T.edR = (const uint32_t *)ctx->stage[19];
-		T.flagsA = S[5];
-		T.flagsR = S[6];
-		T.flagsS = S[7];
-		T.S_be = S[8];
-		T.sp_be = S[9];
-		T.meta = S[13];
+		T.rec = (const uint32_t *)S[EV_REC];
+		T.edR = (const uint32_t *)ctx->stage[EV_EDR];
+		T.flagsA = S[EV_FLAGSA];
+		T.flagsR = S[EV_FLAGSR];
+		T.flagsS = S[EV_FLAGSS];
+		T.S_be = S[EV_S];
+		T.sp_be = S[EV_H];
+		T.meta = S[EV_STHA];
 		T.comb = cv->d_edcomb;
 		T.result = d_res;
 		T.n = n;
@@ -3911,9 +4015,9 @@ static int eddsa_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 	memset(&C, 0, sizeof(C));
 	C.sigs = d_sig;
 	C.hram = d_hram;
-	C.S_be = S[8];
-	C.h_be = S[9];
-	C.flags = S[7];
+	C.S_be = S[EV_S];
+	C.h_be = S[EV_H];
+	C.flags = S[EV_FLAGSS];
 	C.n = n;
 	C.len = (uint32_t)len;
 	C.hlen = hram_len;
@@ -3924,21 +4028,21 @@ static int eddsa_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 		// [h]A on the Edwards curve itself (complete extended-coordinate formulas), mapped to the Weierstrass model
 		EcamdEdSmulArgs E;
 		memset(&E, 0, sizeof(E));
-		E.edA = (const uint32_t *)S[10];
-		E.scalars = S[9];
-		E.flags = S[5];
-		E.tbl = (uint32_t *)S[18];
-		E.rec = (uint32_t *)S[11];
-		E.out = S[12];
-		E.status = S[13];
+		E.edA = (const uint32_t *)S[EV_EDA];
+		E.scalars = S[EV_H];
+		E.flags = S[EV_FLAGSA];
+		E.tbl = (uint32_t *)S[EV_TBL];
+		E.rec = (uint32_t *)S[EV_REC];
+		E.out = S[EV_HA];
+		E.status = S[EV_STHA];
 		E.n = n;
 		memcpy(E.g_2d, cv->ed_2d, sizeof(E.g_2d));
 		memcpy(E.g_alpha, cv->ed_tmpl.g_alpha, sizeof(E.g_alpha));
 		memcpy(E.g_A3, cv->ed_tmpl.g_A3, sizeof(E.g_A3));
 		if (late_map) {
-			E.edR = (const uint32_t *)ctx->stage[19];
-			E.flagsR = S[6];
-			E.outR = S[4];
+			E.edR = (const uint32_t *)ctx->stage[EV_EDR];
+			E.flagsR = S[EV_FLAGSR];
+			E.outR = S[EV_R];
 		}
 		if (ed_tail) {
 			E.out = nullptr;   // no k_ed_hA_fin: [h]A stays in E.rec
@@ -3949,12 +4053,12 @@ static int eddsa_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 	if (ed_tail) {
 		EcamdEdTailArgs T;
 		memset(&T, 0, sizeof(T));
-		T.rec = (const uint32_t *)S[11];
-		T.edR = (const uint32_t *)ctx->stage[19];
-		T.flagsA = S[5];
-		T.flagsR = S[6];
-		T.flagsS = S[7];
-		T.S_be = S[8];
+		T.rec = (const uint32_t *)S[EV_REC];
+		T.edR = (const uint32_t *)ctx->stage[EV_EDR];
+		T.flagsA = S[EV_FLAGSA];
+		T.flagsR = S[EV_FLAGSR];
+		T.flagsS = S[EV_FLAGSS];
+		T.S_be = S[EV_S];
 		T.comb = cv->d_edcomb;
 		T.result = d_res;
 		T.n = n;
@@ -3965,21 +4069,21 @@ static int eddsa_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 	}
 	{
 		PublicScalars pub_scope(ctx);   // h and S of a signature are public
-		if ((!edwards_hA && smul_dev_locked(ctx, cv, n, S[9], (uint32_t)len, S[3], S[12], S[13], s)) ||
-		    smul_dev_locked(ctx, cv, n, S[8], (uint32_t)len, nullptr, S[14], S[15], s)) {
+		if ((!edwards_hA && smul_dev_locked(ctx, cv, n, S[EV_H], (uint32_t)len, S[EV_A], S[EV_HA], S[EV_STHA], s)) ||
+		    smul_dev_locked(ctx, cv, n, S[EV_S], (uint32_t)len, nullptr, S[EV_SG], S[EV_STSG], s)) {
 			return -1;
 		}
 	}
 	EcamdEdFinArgs F;
 	memset(&F, 0, sizeof(F));
-	F.SG = S[14];
-	F.stSG = S[15];
-	F.hA = S[12];
-	F.sthA = S[13];
-	F.R = S[4];
-	F.flagsA = S[5];
-	F.flagsR = S[6];
-	F.flagsS = S[7];
+	F.SG = S[EV_SG];
+	F.stSG = S[EV_STSG];
+	F.hA = S[EV_HA];
+	F.sthA = S[EV_STHA];
+	F.R = S[EV_R];
+	F.flagsA = S[EV_FLAGSA];
+	F.flagsR = S[EV_FLAGSR];
+	F.flagsS = S[EV_FLAGSS];
 	F.result = d_res;
 	F.n = n;
 	F.clen = (uint32_t)len;
@@ -4111,14 +4215,10 @@ static int eddsa448_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t 
 		return 0;
 	}
 	const size_t len = 56, plen = 112;
-	// stage: 3 A (Weierstrass), 4 R, 5 flagsA, 6 flagsR, 7 flagsS, 8 S, 9 k = 4h 4^-1 mod 4q, 12 [k]A, 13 its status,
-	//        14 [S]G, 15 stSG
-	const size_t need[ECAMD_NSTAGE] = {0, 0, 0, n * plen, n * plen, n, n, n, n * len, n * len,
-					   0, 0, n * plen, n, n * plen, n};
-	for (int i = 0; i < ECAMD_NSTAGE; i++) {
-		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	// EV_H holds k = 4h 4^-1 mod 4q, EV_HA / EV_STHA [k]A and its status
+	if (stage_need(ctx, {{EV_A, n * plen}, {EV_R, n * plen}, {EV_FLAGSA, n}, {EV_FLAGSR, n}, {EV_FLAGSS, n}, {EV_S, n * len}, {EV_H, n * len},
+			     {EV_HA, n * plen}, {EV_STHA, n}, {EV_SG, n * plen}, {EV_STSG, n}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	EcamdEd448DecodeArgs D = cv->ed448_tmpl;
@@ -4127,10 +4227,10 @@ static int eddsa448_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t 
 	D.strideA = 57;
 	D.encR = d_sig;
 	D.strideR = 114;
-	D.pointsA = S[3];
-	D.pointsR = S[4];
-	D.flagsA = S[5];
-	D.flagsR = S[6];
+	D.pointsA = S[EV_A];
+	D.pointsR = S[EV_R];
+	D.flagsA = S[EV_FLAGSA];
+	D.flagsR = S[EV_FLAGSR];
 	if (cv->gflavour == 5 && cv->gslot >= 0 && getenv("ECAMD_NO_G448_DECODE") == nullptr) {
 		HIPCHK(ecamd_launch_ed448_decode_g(D, cv->gslot, s));   // the same decoding on the Goldilocks radix-2^29 field
 	} else {
@@ -4140,9 +4240,9 @@ static int eddsa448_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t 
 	memset(&C, 0, sizeof(C));
 	C.sigs = d_sig;
 	C.hram = d_hram;
-	C.S_be = S[8];
-	C.h_be = S[9];
-	C.flags = S[7];
+	C.S_be = S[EV_S];
+	C.h_be = S[EV_H];
+	C.flags = S[EV_FLAGSS];
 	C.n = n;
 	C.len = 57;
 	C.hlen = 114;
@@ -4152,26 +4252,26 @@ static int eddsa448_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t 
 	// the reference's [4h mod q]([4^-1 mod q]A) as one multiplication of A (k_ed448_scal), and [S]G
 	{
 		PublicScalars pub_scope(ctx);   // h and S of a signature are public
-		if (smul_dev_locked(ctx, cv, n, S[9], (uint32_t)len, S[3], S[12], S[13], s) ||
-		    smul_dev_locked(ctx, cv, n, S[8], (uint32_t)len, nullptr, S[14], S[15], s)) {
+		if (smul_dev_locked(ctx, cv, n, S[EV_H], (uint32_t)len, S[EV_A], S[EV_HA], S[EV_STHA], s) ||
+		    smul_dev_locked(ctx, cv, n, S[EV_S], (uint32_t)len, nullptr, S[EV_SG], S[EV_STSG], s)) {
 			return -1;
 		}
 	}
 	EcamdEdFinArgs F;
 	memset(&F, 0, sizeof(F));
-	F.SG = S[14];
-	F.stSG = S[15];
-	F.hA = S[12];
-	F.sthA = S[13];
-	F.R = S[4];
-	F.flagsA = S[5];
-	F.flagsR = S[6];
-	F.flagsS = S[7];
+	F.SG = S[EV_SG];
+	F.stSG = S[EV_STSG];
+	F.hA = S[EV_HA];
+	F.sthA = S[EV_STHA];
+	F.R = S[EV_R];
+	F.flagsA = S[EV_FLAGSA];
+	F.flagsR = S[EV_FLAGSR];
+	F.flagsS = S[EV_FLAGSS];
 	F.result = d_res;
 	F.n = n;
 	F.clen = (uint32_t)len;
 	F.cof_dbl = 2;
-	F.Akey = S[3];      // [4]A = infinity <=> the stored key [4^-1 mod q]A has small order
+	F.Akey = S[EV_A];      // [4]A = infinity <=> the stored key [4^-1 mod q]A has small order
 	F.stA = nullptr;
 	F.slot = cv->slot;
 	if (cv->gflavour == 5 && cv->gslot >= 0 && getenv("ECAMD_NO_ED_FIN_G") == nullptr) {
@@ -4193,7 +4293,37 @@ static int eddsa448_verify_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t 
 // exact; a batch with an item that fails its cofactored equation passes with probability ~2^-128.  d_verdict[0] is SET to 1 for "not
 // decided here" and never cleared (the pieces of one call share it).  Only enqueues.
 // ------------------------------------------------------------------------------------------
-static int msm_seed(ecamd_ctx *ctx, uint8_t seed[32]);
+// key of the z_i of the batch equation: the caller's 32 bytes when ecamd_ctx_set_msm_seed left some (used once), else getrandom
+static int msm_seed(ecamd_ctx *ctx, uint8_t seed[32])
+{
+	if (ctx->msm_seed_valid) {
+		memcpy(seed, ctx->msm_seed_bytes, 32);
+		memset(ctx->msm_seed_bytes, 0, 32);
+		ctx->msm_seed_valid = false;
+		return 0;
+	}
+	size_t got = 0;
+	while (got < 32) {
+		const ssize_t r = getrandom(seed + got, 32 - got, 0);
+		if (r <= 0) {
+			return fail("ec_eddsa_verify_all_batch: getrandom failed (the z_i of the batch equation must be unpredictable)");
+		}
+		got += (size_t)r;
+	}
+	return 0;
+}
+// the seed of ecamd_ctx_set_msm_seed keys ONE whole-batch call: whichever path that call took (Ed448, a batch below msm_min,
+// mode 0, an error), it is gone afterwards (ADVICE round 3)
+static void msm_seed_discard(ecamd_ctx *ctx)
+{
+	if (ctx) {
+		std::lock_guard<std::mutex> lk(ctx->mu);
+		if (ctx->msm_seed_valid) {
+			memset(ctx->msm_seed_bytes, 0, sizeof(ctx->msm_seed_bytes));
+			ctx->msm_seed_valid = false;
+		}
+	}
+}
 // the bucket evaluation FILED CHUNK BY CHUNK (ec_schnorr_verify_msg_all_batch): which part of schnorr_msm_dev_locked a call runs
 struct SchnorrStreamStep {
 	int mode;                // 1: scratch sized, flag word and counters cleared; 2: the items [first, first + count) imported, their scalars
@@ -4218,16 +4348,10 @@ static int eddsa448_msm_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 		return fail("internal: eddsa448_msm_dev_locked serves one piece of at most max_chunk items");
 	}
 	const size_t len = 56, plen = 112;
-	// stage: 3 A (Weierstrass, affine), 4 R, 5 flagsA, 6 flagsR, 7 flagsS, 8 S, 9 k (unused here), 12 (q - h) mod q, 13 gate word + piece verdict
-	size_t need[ECAMD_NSTAGE] = {0};
-	need[3] = need[4] = n * plen;
-	need[5] = need[6] = need[7] = n;
-	need[8] = need[9] = need[12] = n * len;
-	need[13] = 256;
-	for (int i = 0; i < 16; i++) {
-		if (need[i] && ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	// (EV_H: k, unused here)
+	if (stage_need(ctx, {{EV_A, n * plen}, {EV_R, n * plen}, {EV_FLAGSA, n}, {EV_FLAGSR, n}, {EV_FLAGSS, n}, {EV_S, n * len}, {EV_H, n * len},
+			     {EV_NE, n * len}, {EV_GATE, 256}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	EcamdEd448DecodeArgs D = cv->ed448_tmpl;
@@ -4236,10 +4360,10 @@ static int eddsa448_msm_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 	D.strideA = 57;
 	D.encR = d_sig;
 	D.strideR = 114;
-	D.pointsA = S[3];
-	D.pointsR = S[4];
-	D.flagsA = S[5];
-	D.flagsR = S[6];
+	D.pointsA = S[EV_A];
+	D.pointsR = S[EV_R];
+	D.flagsA = S[EV_FLAGSA];
+	D.flagsR = S[EV_FLAGSR];
 	if (cv->gflavour == 5 && cv->gslot >= 0 && getenv("ECAMD_NO_G448_DECODE") == nullptr) {
 		HIPCHK(ecamd_launch_ed448_decode_g(D, cv->gslot, s));
 	} else {
@@ -4249,25 +4373,25 @@ static int eddsa448_msm_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, 
 	memset(&C, 0, sizeof(C));
 	C.sigs = d_sig;
 	C.hram = d_hram;
-	C.S_be = S[8];
-	C.h_be = S[9];
-	C.ne_be = S[12];
-	C.flags = S[7];
+	C.S_be = S[EV_S];
+	C.h_be = S[EV_H];
+	C.ne_be = S[EV_NE];
+	C.flags = S[EV_FLAGSS];
 	C.n = n;
 	C.len = 57;
 	C.hlen = 114;
 	C.qslot = cv->qslot;
 	C.c4_mod4 = cv->ed448_c4[55] & 3u;
 	HIPCHK(ecamd_launch_ed448_scal(C, s));
-	uint32_t *d_gate = (uint32_t *)S[13];
-	uint8_t *d_piece = S[13] + 16;
-	HIPCHK(hipMemsetAsync(S[13], 0, 16, s));
+	uint32_t *d_gate = (uint32_t *)S[EV_GATE];
+	uint8_t *d_piece = S[EV_GATE] + 16;
+	HIPCHK(hipMemsetAsync(S[EV_GATE], 0, 16, s));
 	HIPCHK(hipMemsetAsync(d_piece, 1, 1, s));
 	// (the keys of small order, [4]A = infinity: seen by the combination's own import of the keys on the fast unit -- cof_dbl of EcamdMsmArgs)
-	HIPCHK(ecamd_launch_ed_msm_gate(cv->nw, S[3], S[5], S[6], S[7], n, (uint32_t)len, 0, cv->slot, d_gate, s));
+	HIPCHK(ecamd_launch_ed_msm_gate(cv->nw, S[EV_A], S[EV_FLAGSA], S[EV_FLAGSR], S[EV_FLAGSS], n, (uint32_t)len, 0, cv->slot, d_gate, s));
 	{
 		PublicScalars pub_scope(ctx);   // everything a verification multiplies by is public
-		if (schnorr_msm_dev_locked(ctx, cv, n, S[8], S[12], S[3], S[4], 0, seed, piece, d_piece, nullptr, nullptr, s, 2)) {
+		if (schnorr_msm_dev_locked(ctx, cv, n, S[EV_S], S[EV_NE], S[EV_A], S[EV_R], 0, seed, piece, d_piece, nullptr, nullptr, s, 2)) {
 			return -1;
 		}
 	}
@@ -4286,18 +4410,18 @@ static int eddsa448_msm_host_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n,
 	hipStream_t s = ctx->stream;
 	StreamScope scope(ctx, s);
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (ensure(&ctx->stage[0], &ctx->stage_bytes[0], (size_t)chunk * 57) || ensure(&ctx->stage[1], &ctx->stage_bytes[1], (size_t)chunk * 114) ||
-	    ensure(&ctx->stage[2], &ctx->stage_bytes[2], (size_t)chunk * 114) || ensure(&ctx->stage[14], &ctx->stage_bytes[14], 256)) {
+	if (stage_need(ctx, MH_PUB, (size_t)chunk * 57) || stage_need(ctx, MH_SIG, (size_t)chunk * 114) ||
+	    stage_need(ctx, MH_HRAM, (size_t)chunk * 114) || stage_need(ctx, MH_VERDICT448, 256)) {
 		return -1;
 	}
-	uint8_t *d_verdict = ctx->stage[14];
+	uint8_t *d_verdict = ctx->stage[MH_VERDICT448];
 	HIPCHK(hipMemsetAsync(d_verdict, 0, 1, s));
 	for (uint32_t off = 0, pc = 0; off < n; off += chunk, pc++) {
 		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		HIPCHK(hipMemcpyAsync(ctx->stage[0], pubkeys + (size_t)off * 57, (size_t)m * 57, hipMemcpyHostToDevice, s));
-		HIPCHK(hipMemcpyAsync(ctx->stage[1], sigs + (size_t)off * 114, (size_t)m * 114, hipMemcpyHostToDevice, s));
-		HIPCHK(hipMemcpyAsync(ctx->stage[2], hram + (size_t)off * 114, (size_t)m * 114, hipMemcpyHostToDevice, s));
-		if (eddsa448_msm_dev_locked(ctx, cv, m, ctx->stage[0], ctx->stage[1], ctx->stage[2], seed, pc, d_verdict, s)) {
+		HIPCHK(hipMemcpyAsync(ctx->stage[MH_PUB], pubkeys + (size_t)off * 57, (size_t)m * 57, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[MH_SIG], sigs + (size_t)off * 114, (size_t)m * 114, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[MH_HRAM], hram + (size_t)off * 114, (size_t)m * 114, hipMemcpyHostToDevice, s));
+		if (eddsa448_msm_dev_locked(ctx, cv, m, ctx->stage[MH_PUB], ctx->stage[MH_SIG], ctx->stage[MH_HRAM], seed, pc, d_verdict, s)) {
 			(void)hipStreamSynchronize(s);
 			return -1;
 		}
@@ -4348,7 +4472,7 @@ extern "C" int ec_eddsa_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv_i
 	if (!ctx) {
 		return fail("ec_eddsa_verify_batch_dev: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	if (eddsa_args_ok("ec_eddsa_verify_batch_dev", ctx, cv_in, n, d_pubkeys, d_sigs, d_hram, d_result, hram_len)) {
 		return -1;
 	}
@@ -4372,7 +4496,7 @@ extern "C" int ec_eddsa_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv_in, u
 	if (!ctx) {
 		return fail("ec_eddsa_verify_batch: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	if (eddsa_args_ok("ec_eddsa_verify_batch", ctx, cv_in, n, pubkeys, sigs, hram, result, hram_len)) {
 		return -1;
 	}
@@ -4384,8 +4508,7 @@ extern "C" int ec_eddsa_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv_in, u
 	const bool e448 = cv->pbits == 448;
 	const std::vector<HostArr> arrs = {{pubkeys, nullptr, e448 ? 57u : 32u}, {sigs, nullptr, e448 ? 114u : 64u},
 					   {hram, nullptr, hram_len}, {nullptr, result, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return e448 ? eddsa448_verify_dev_locked(ctx, cv, m, ip[0], ip[1], ip[2], op[3], s)
 			    : eddsa_verify_dev_locked(ctx, cv, m, ip[0], ip[1], ip[2], hram_len, op[3], s);
 	});
@@ -4399,7 +4522,7 @@ extern "C" int ec_eddsa_verify_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv_i
 	if (!ctx || stride < 4 || (stride & 3u) || stride > 4096) {
 		return fail("ec_eddsa_verify_msg_batch: bad argument (stride: a multiple of 4 in 4 .. 4096)");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	if (eddsa_args_ok("ec_eddsa_verify_msg_batch", ctx, cv_in, n, pubkeys, sigs, hash_slots, result, 64)) {
 		return -1;
 	}
@@ -4412,12 +4535,11 @@ extern "C" int ec_eddsa_verify_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv_i
 	}
 	HIPCHK(hipSetDevice(ctx->device));
 	const std::vector<HostArr> arrs = {{pubkeys, nullptr, 32u}, {sigs, nullptr, 64u}, {hash_slots, nullptr, stride}, {nullptr, result, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		if (ecdsa_hash_stage(ctx, 4, m, ip[2], stride, 64, s)) {
 			return -1;
 		}
-		return eddsa_verify_dev_locked(ctx, cv, m, ip[0], ip[1], ctx->stage[17], 64, op[3], s);
+		return eddsa_verify_dev_locked(ctx, cv, m, ip[0], ip[1], ctx->stage[ST_DIGESTS], 64, op[3], s);
 	});
 }
 
@@ -4455,16 +4577,11 @@ static int eddsa_bkt_stream_begin(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, c
 static int eddsa_bkt_stream_chunk(ecamd_curve *cv, EdBktRun &R, uint32_t first, uint32_t count, hipStream_t s);
 static int eddsa_bkt_stream_end(ecamd_ctx *ctx, ecamd_curve *cv, EdBktRun &R, uint8_t *d_verdict, hipStream_t s);
 static bool eddsa_msm_available(const ecamd_curve *cv);
-static bool eddsa448_msm_available(const ecamd_curve *cv);
-static int eddsa448_msm_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, const uint8_t *d_pub, const uint8_t *d_sig, const uint8_t *d_hram,
-				   const uint8_t seed[32], uint32_t piece, uint8_t *d_verdict, hipStream_t s);
-static int msm_seed(ecamd_ctx *ctx, uint8_t seed[32]);
-static void msm_seed_discard(ecamd_ctx *ctx);
 static int eddsa_msm_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, const uint8_t *d_pub, const uint8_t *d_sig,
 				const uint8_t *d_hram, const uint8_t seed[32], uint32_t piece, uint8_t *d_verdict, uint8_t *d_z_dump,
 				uint32_t *d_sum_dump, hipStream_t s);
 // all_valid != NULL (round 6, Ed25519 only): ONE accept bit instead of per-item results -- the front end of every chunk (import, encoding, hashes)
-// files the encoded keys, the signatures and the hashes in batch-wide arrays (stage 24 - 26; 27: per-item "the key has no encoding"), and when
+// files the encoded keys, the signatures and the hashes in batch-wide arrays (EB_KEYS, EB_SIGS, EB_HRAM; EB_MARKS: per-item "the key has no encoding"), and when
 // the last chunk is in the batch equation is evaluated once per max_chunk items (eddsa_msm_dev_locked: by buckets from 2^18 items on).
 // *all_valid = 0: not decided here (ec_eddsa_verify_all_batch's contract without its item-by-item pass: the caller has one).
 static int eddsa_verify_msg_prj_impl(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const uint8_t *keys_prj, const uint8_t *sigs,
@@ -4486,7 +4603,7 @@ static int eddsa_verify_msg_prj_impl(const char *fn, ecamd_ctx *ctx, const ecamd
 	if (msg_slots && (msg_stride < 4 || (msg_stride & 3u) || msg_stride > 4096)) {
 		return fail(f + ": bad argument (msg_stride: a multiple of 4 in 4 .. 4096)");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	EcamdEdSignArgs T;
 	uint8_t dummy = 0;
 	if (eddsa_sign_setup(fn, ctx, cv_in, n, keys_prj, sigs, hash_slots, &T) ||
@@ -4506,8 +4623,8 @@ static int eddsa_verify_msg_prj_impl(const char *fn, ecamd_ctx *ctx, const ecamd
 		if (e448 ? !eddsa448_msm_available(cv) : !eddsa_msm_available(cv)) {
 			return 0;   // not decided here
 		}
-		if (msm_seed(ctx, seed) || ensure(&ctx->stage[24], &ctx->stage_bytes[24], (size_t)n * kl) || ensure(&ctx->stage[25], &ctx->stage_bytes[25], (size_t)n * sl) ||
-		    ensure(&ctx->stage[26], &ctx->stage_bytes[26], (size_t)n * hl) || ensure(&ctx->stage[27], &ctx->stage_bytes[27], (size_t)n + 256)) {
+		if (msm_seed(ctx, seed) || stage_need(ctx, EB_KEYS, (size_t)n * kl) || stage_need(ctx, EB_SIGS, (size_t)n * sl) ||
+		    stage_need(ctx, EB_HRAM, (size_t)n * hl) || stage_need(ctx, EB_MARKS, (size_t)n + 256)) {
 			return -1;
 		}
 	}
@@ -4521,15 +4638,14 @@ static int eddsa_verify_msg_prj_impl(const char *fn, ecamd_ctx *ctx, const ecamd
 	const bool streamed = all_valid && !e448 && n <= ctx->max_chunk && eddsa_msm_use_buckets(n) && getenv("ECAMD_NO_ED_STREAM") == nullptr;
 	if (streamed) {
 		StreamScope scope(ctx, ctx->stream);
-		if (eddsa_bkt_stream_begin(ctx, cv, n, ctx->stage[24], ctx->stage[25], ctx->stage[26], seed, run, ctx->stream)) {
+		if (eddsa_bkt_stream_begin(ctx, cv, n, ctx->stage[EB_KEYS], ctx->stage[EB_SIGS], ctx->stage[EB_HRAM], seed, run, ctx->stream)) {
 			return -1;
 		}
 	}
-	const int prc = host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
-		// stage: 20 affine keys, 21 import status, 22 encodings, 23 their status (the verification core owns 3 .. 19)
-		if (ensure(&ctx->stage[20], &ctx->stage_bytes[20], (size_t)m * 2 * cl) || ensure(&ctx->stage[21], &ctx->stage_bytes[21], m) ||
-		    ensure(&ctx->stage[22], &ctx->stage_bytes[22], (size_t)m * kl) || ensure(&ctx->stage[23], &ctx->stage_bytes[23], m)) {
+	const int prc = host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		// EP_: the affine keys and their import status, the encodings and theirs (the verification core owns the EV_ frame)
+		if (stage_need(ctx, EP_AFF, (size_t)m * 2 * cl) || stage_need(ctx, EP_PRE, m) ||
+		    stage_need(ctx, EP_KEY, (size_t)m * kl) || stage_need(ctx, EP_KST, m)) {
 			return -1;
 		}
 		uint8_t *slots = const_cast<uint8_t *>(ip[2]);   // the staged copy of the caller's slots
@@ -4539,12 +4655,12 @@ static int eddsa_verify_msg_prj_impl(const char *fn, ecamd_ctx *ctx, const ecamd
 			if (ecdsa_hash_stage(ctx, hash_type, m, ip[4], msg_stride, 64, s)) {
 				return -1;
 			}
-			HIPCHK(ecamd_launch_slot_patch(slots, stride, a_offset + kl, ctx->stage[17], 64, nullptr, m, s));
+			HIPCHK(ecamd_launch_slot_patch(slots, stride, a_offset + kl, ctx->stage[ST_DIGESTS], 64, nullptr, m, s));
 		}
 		EcamdPrjInArgs I;
 		I.in = ip[0];
-		I.aff = ctx->stage[20];
-		I.pre = ctx->stage[21];
+		I.aff = ctx->stage[EP_AFF];
+		I.pre = ctx->stage[EP_PRE];
 		I.n = m;
 		I.clen = (uint32_t)cl;
 		I.for_mul = 0;
@@ -4552,13 +4668,13 @@ static int eddsa_verify_msg_prj_impl(const char *fn, ecamd_ctx *ctx, const ecamd
 		HIPCHK(launch_prj_import(cv, I, s));
 		EcamdEdSignArgs A = T;
 		A.n = m;
-		A.Rw = ctx->stage[20];
-		A.stR = ctx->stage[21];
+		A.Rw = ctx->stage[EP_AFF];
+		A.stR = ctx->stage[EP_PRE];
 		// (the whole-batch form files the encodings and their "no encoding" marks in batch-wide arrays: Ed25519's 32-octet encodings are written
 		// there directly; Ed448's 57-octet ones keep their aligned staging and a copy)
 		const bool direct = all_valid && !e448;
-		A.out = direct ? ctx->stage[24] + (size_t)done * kl : ctx->stage[22];
-		A.status = direct ? ctx->stage[27] + (size_t)done : ctx->stage[23];
+		A.out = direct ? ctx->stage[EB_KEYS] + (size_t)done * kl : ctx->stage[EP_KEY];
+		A.status = direct ? ctx->stage[EB_MARKS] + (size_t)done : ctx->stage[EP_KST];
 		HIPCHK(launch_ed_sign_enc(cv, A, s));
 		HIPCHK(ecamd_launch_slot_patch(slots, stride, a_offset, A.out, kl, A.status, m, s));
 		if (all_valid) {
@@ -4567,11 +4683,11 @@ static int eddsa_verify_msg_prj_impl(const char *fn, ecamd_ctx *ctx, const ecamd
 				return -1;
 			}
 			if (!direct) {
-				HIPCHK(hipMemcpyAsync(ctx->stage[24] + (size_t)done * kl, ctx->stage[22], (size_t)m * kl, hipMemcpyDeviceToDevice, s));
-				HIPCHK(hipMemcpyAsync(ctx->stage[27] + (size_t)done, ctx->stage[23], m, hipMemcpyDeviceToDevice, s));
+				HIPCHK(hipMemcpyAsync(ctx->stage[EB_KEYS] + (size_t)done * kl, ctx->stage[EP_KEY], (size_t)m * kl, hipMemcpyDeviceToDevice, s));
+				HIPCHK(hipMemcpyAsync(ctx->stage[EB_MARKS] + (size_t)done, ctx->stage[EP_KST], m, hipMemcpyDeviceToDevice, s));
 			}
-			HIPCHK(hipMemcpyAsync(ctx->stage[25] + (size_t)done * sl, ip[1], (size_t)m * sl, hipMemcpyDeviceToDevice, s));
-			HIPCHK(hipMemcpyAsync(ctx->stage[26] + (size_t)done * hl, ctx->stage[17], (size_t)m * hl, hipMemcpyDeviceToDevice, s));
+			HIPCHK(hipMemcpyAsync(ctx->stage[EB_SIGS] + (size_t)done * sl, ip[1], (size_t)m * sl, hipMemcpyDeviceToDevice, s));
+			HIPCHK(hipMemcpyAsync(ctx->stage[EB_HRAM] + (size_t)done * hl, ctx->stage[ST_DIGESTS], (size_t)m * hl, hipMemcpyDeviceToDevice, s));
 			if (streamed && eddsa_bkt_stream_chunk(cv, run, done, m, s)) {
 				return -1;
 			}
@@ -4579,11 +4695,11 @@ static int eddsa_verify_msg_prj_impl(const char *fn, ecamd_ctx *ctx, const ecamd
 			return 0;
 		}
 		if (ecdsa_hash_stage(ctx, hash_type, m, slots, stride, hl, s) ||
-		    (e448 ? eddsa448_verify_dev_locked(ctx, cv, m, ctx->stage[22], ip[1], ctx->stage[17], op[3], s)
-			  : eddsa_verify_dev_locked(ctx, cv, m, ctx->stage[22], ip[1], ctx->stage[17], 64, op[3], s))) {
+		    (e448 ? eddsa448_verify_dev_locked(ctx, cv, m, ctx->stage[EP_KEY], ip[1], ctx->stage[ST_DIGESTS], op[3], s)
+			  : eddsa_verify_dev_locked(ctx, cv, m, ctx->stage[EP_KEY], ip[1], ctx->stage[ST_DIGESTS], 64, op[3], s))) {
 			return -1;
 		}
-		HIPCHK(ecamd_launch_reject_where(op[3], ctx->stage[23], m, s));
+		HIPCHK(ecamd_launch_reject_where(op[3], ctx->stage[EP_KST], m, s));
 		return 0;
 	}, streamed ? (1u << 17) : 0u);
 	if (prc || !all_valid) {
@@ -4592,7 +4708,7 @@ static int eddsa_verify_msg_prj_impl(const char *fn, ecamd_ctx *ctx, const ecamd
 	// the batch equation over the filed arrays, a piece of max_chunk items at a time; the verdict byte rests behind the marks
 	hipStream_t s = ctx->stream;
 	StreamScope scope(ctx, s);
-	uint8_t *d_verdict = ctx->stage[27] + n;
+	uint8_t *d_verdict = ctx->stage[EB_MARKS] + n;
 	HIPCHK(hipMemsetAsync(d_verdict, 0, 1, s));
 	uint32_t pc = 0;
 	if (streamed && eddsa_bkt_stream_end(ctx, cv, run, d_verdict, s)) {
@@ -4601,16 +4717,16 @@ static int eddsa_verify_msg_prj_impl(const char *fn, ecamd_ctx *ctx, const ecamd
 	}
 	for (uint32_t off = 0; off < n && !streamed; off += ctx->max_chunk, pc++) {
 		const uint32_t m = (n - off) < ctx->max_chunk ? (n - off) : ctx->max_chunk;
-		if (e448 ? eddsa448_msm_dev_locked(ctx, cv, m, ctx->stage[24] + (size_t)off * kl, ctx->stage[25] + (size_t)off * sl, ctx->stage[26] + (size_t)off * hl,
+		if (e448 ? eddsa448_msm_dev_locked(ctx, cv, m, ctx->stage[EB_KEYS] + (size_t)off * kl, ctx->stage[EB_SIGS] + (size_t)off * sl, ctx->stage[EB_HRAM] + (size_t)off * hl,
 						   seed, pc, d_verdict, s)
-			 : eddsa_msm_dev_locked(ctx, cv, m, ctx->stage[24] + (size_t)off * 32, ctx->stage[25] + (size_t)off * 64, ctx->stage[26] + (size_t)off * 64, seed, pc,
+			 : eddsa_msm_dev_locked(ctx, cv, m, ctx->stage[EB_KEYS] + (size_t)off * 32, ctx->stage[EB_SIGS] + (size_t)off * 64, ctx->stage[EB_HRAM] + (size_t)off * 64, seed, pc,
 						d_verdict, nullptr, nullptr, s)) {
 			(void)hipStreamSynchronize(s);
 			return -1;
 		}
 	}
 	std::vector<uint8_t> marks((size_t)n + 1, 1);
-	HIPCHK(hipMemcpyAsync(marks.data(), ctx->stage[27], (size_t)n + 1, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(marks.data(), ctx->stage[EB_MARKS], (size_t)n + 1, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	memset(seed, 0, sizeof(seed));
 	int ok = marks[n] == 0;
@@ -4968,26 +5084,6 @@ static int eddsa_msm_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, con
 	return 0;
 }
 
-// key of the z_i of the batch equation: the caller's 32 bytes when ecamd_ctx_set_msm_seed left some (used once), else getrandom
-static int msm_seed(ecamd_ctx *ctx, uint8_t seed[32])
-{
-	if (ctx->msm_seed_valid) {
-		memcpy(seed, ctx->msm_seed_bytes, 32);
-		memset(ctx->msm_seed_bytes, 0, 32);
-		ctx->msm_seed_valid = false;
-		return 0;
-	}
-	size_t got = 0;
-	while (got < 32) {
-		const ssize_t r = getrandom(seed + got, 32 - got, 0);
-		if (r <= 0) {
-			return fail("ec_eddsa_verify_all_batch: getrandom failed (the z_i of the batch equation must be unpredictable)");
-		}
-		got += (size_t)r;
-	}
-	return 0;
-}
-
 // host arrays -> one verdict: pieces of max_chunk items, each with its own combination.  *accept = 1 when every piece accepts.
 static int eddsa_msm_host_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, const uint8_t *pubkeys, const uint8_t *sigs,
 				 const uint8_t *hram, const uint8_t *fixed_seed, int *accept, uint8_t *z_out, uint32_t *sum_out)
@@ -5002,21 +5098,21 @@ static int eddsa_msm_host_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, co
 	StreamScope scope(ctx, s);
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
 	const uint32_t pieces = (n + chunk - 1) / chunk;
-	if (ensure(&ctx->stage[0], &ctx->stage_bytes[0], (size_t)chunk * 32) || ensure(&ctx->stage[1], &ctx->stage_bytes[1], (size_t)chunk * 64) ||
-	    ensure(&ctx->stage[2], &ctx->stage_bytes[2], (size_t)chunk * 64) ||
-	    ensure(&ctx->stage[3], &ctx->stage_bytes[3], (size_t)pieces + (z_out ? (size_t)chunk * 16 : 0) + 256 + ECAMD_EDM_REC_WORDS * 4)) {
+	if (stage_need(ctx, MH_PUB, (size_t)chunk * 32) || stage_need(ctx, MH_SIG, (size_t)chunk * 64) ||
+	    stage_need(ctx, MH_HRAM, (size_t)chunk * 64) ||
+	    stage_need(ctx, MH_VERDICTS, (size_t)pieces + (z_out ? (size_t)chunk * 16 : 0) + 256 + ECAMD_EDM_REC_WORDS * 4)) {
 		return -1;
 	}
-	uint8_t *d_verdicts = ctx->stage[3];
+	uint8_t *d_verdicts = ctx->stage[MH_VERDICTS];
 	HIPCHK(hipMemsetAsync(d_verdicts, 0, pieces, s));
-	uint32_t *d_sum = (uint32_t *)(ctx->stage[3] + ((pieces + 255) & ~(size_t)255));
+	uint32_t *d_sum = (uint32_t *)(ctx->stage[MH_VERDICTS] + ((pieces + 255) & ~(size_t)255));
 	uint8_t *d_z = z_out ? (uint8_t *)(d_sum + ECAMD_EDM_REC_WORDS) : nullptr;
 	for (uint32_t off = 0, pc = 0; off < n; off += chunk, pc++) {
 		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		HIPCHK(hipMemcpyAsync(ctx->stage[0], pubkeys + (size_t)off * 32, (size_t)m * 32, hipMemcpyHostToDevice, s));
-		HIPCHK(hipMemcpyAsync(ctx->stage[1], sigs + (size_t)off * 64, (size_t)m * 64, hipMemcpyHostToDevice, s));
-		HIPCHK(hipMemcpyAsync(ctx->stage[2], hram + (size_t)off * 64, (size_t)m * 64, hipMemcpyHostToDevice, s));
-		if (eddsa_msm_dev_locked(ctx, cv, m, ctx->stage[0], ctx->stage[1], ctx->stage[2], seed, pc, d_verdicts + pc, d_z,
+		HIPCHK(hipMemcpyAsync(ctx->stage[MH_PUB], pubkeys + (size_t)off * 32, (size_t)m * 32, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[MH_SIG], sigs + (size_t)off * 64, (size_t)m * 64, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[MH_HRAM], hram + (size_t)off * 64, (size_t)m * 64, hipMemcpyHostToDevice, s));
+		if (eddsa_msm_dev_locked(ctx, cv, m, ctx->stage[MH_PUB], ctx->stage[MH_SIG], ctx->stage[MH_HRAM], seed, pc, d_verdicts + pc, d_z,
 					 sum_out ? d_sum : nullptr, s)) {
 			(void)hipStreamSynchronize(s);
 			return -1;
@@ -5490,22 +5586,22 @@ static int schnorr_msm_host_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 	int pb, fl, sl;
 	(void)schnorr_msm_unit(cv, &pb, &fl, &sl);
 	const size_t recw = ecamd_g29_msm_rec_words(pb, fl);
-	if (ensure(&ctx->stage[0], &ctx->stage_bytes[0], (size_t)chunk * ql) || ensure(&ctx->stage[1], &ctx->stage_bytes[1], (size_t)chunk * ql) ||
-	    ensure(&ctx->stage[2], &ctx->stage_bytes[2], (size_t)chunk * 2 * cl) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], (size_t)chunk * rl) ||
-	    ensure(&ctx->stage[3], &ctx->stage_bytes[3], (size_t)pieces + (z_out ? (size_t)chunk * 16 : 0) + 512 + recw * 4)) {
+	if (stage_need(ctx, MS_S, (size_t)chunk * ql) || stage_need(ctx, MS_NE, (size_t)chunk * ql) ||
+	    stage_need(ctx, MS_KEYS, (size_t)chunk * 2 * cl) || stage_need(ctx, MS_R, (size_t)chunk * rl) ||
+	    stage_need(ctx, MS_VERDICTS, (size_t)pieces + (z_out ? (size_t)chunk * 16 : 0) + 512 + recw * 4)) {
 		return -1;
 	}
-	uint8_t *d_verdicts = ctx->stage[3];
+	uint8_t *d_verdicts = ctx->stage[MS_VERDICTS];
 	HIPCHK(hipMemsetAsync(d_verdicts, 1, pieces, s));
-	uint32_t *d_sum = (uint32_t *)(ctx->stage[3] + ((pieces + 255) & ~(size_t)255));
+	uint32_t *d_sum = (uint32_t *)(ctx->stage[MS_VERDICTS] + ((pieces + 255) & ~(size_t)255));
 	uint8_t *d_z = z_out ? (uint8_t *)(d_sum + recw) : nullptr;
 	for (uint32_t off = 0, pc = 0; off < n; off += chunk, pc++) {
 		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		HIPCHK(hipMemcpyAsync(ctx->stage[0], sv + (size_t)off * ql, (size_t)m * ql, hipMemcpyHostToDevice, s));
-		HIPCHK(hipMemcpyAsync(ctx->stage[1], ne + (size_t)off * ql, (size_t)m * ql, hipMemcpyHostToDevice, s));
-		HIPCHK(hipMemcpyAsync(ctx->stage[2], keys + (size_t)off * 2 * cl, (size_t)m * 2 * cl, hipMemcpyHostToDevice, s));
-		HIPCHK(hipMemcpyAsync(ctx->stage[4], r + (size_t)off * rl, (size_t)m * rl, hipMemcpyHostToDevice, s));
-		if (schnorr_msm_dev_locked(ctx, cv, m, ctx->stage[0], ctx->stage[1], ctx->stage[2], ctx->stage[4], r_fmt, seed, pc, d_verdicts + pc, d_z,
+		HIPCHK(hipMemcpyAsync(ctx->stage[MS_S], sv + (size_t)off * ql, (size_t)m * ql, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[MS_NE], ne + (size_t)off * ql, (size_t)m * ql, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[MS_KEYS], keys + (size_t)off * 2 * cl, (size_t)m * 2 * cl, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(ctx->stage[MS_R], r + (size_t)off * rl, (size_t)m * rl, hipMemcpyHostToDevice, s));
+		if (schnorr_msm_dev_locked(ctx, cv, m, ctx->stage[MS_S], ctx->stage[MS_NE], ctx->stage[MS_KEYS], ctx->stage[MS_R], r_fmt, seed, pc, d_verdicts + pc, d_z,
 					   sum_out ? d_sum : nullptr, s)) {
 			(void)hipStreamSynchronize(s);
 			return -1;
@@ -5530,7 +5626,6 @@ static int schnorr_msm_host_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 	return 0;
 }
 
-static void msm_seed_discard(ecamd_ctx *ctx);
 extern "C" int ec_schnorr_verify_all_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *s, const uint8_t *ne,
 					   const uint8_t *keys_aff, const uint8_t *r, int r_fmt, int *all_valid)
 {
@@ -5617,12 +5712,12 @@ extern "C" int ec_schnorr_verify_msg_all_batch(ecamd_ctx *ctx, const ecamd_curve
 			const size_t kw = (key_fmt == ECAMD_PT_PROJECTIVE ? 3 : 2) * cl;
 			// batch-wide arrays: 24 s, 25 q - e, 26 keys, 27 commitments, 28 the front end's flag word and the verdicts
 			const uint32_t pieces = (n + ctx->max_chunk - 1) / ctx->max_chunk;
-			if (!msm_seed(ctx, seed) && !ensure(&ctx->stage[24], &ctx->stage_bytes[24], (size_t)n * ql) &&
-			    !ensure(&ctx->stage[25], &ctx->stage_bytes[25], (size_t)n * ql) && !ensure(&ctx->stage[26], &ctx->stage_bytes[26], (size_t)n * 2 * cl) &&
-			    !ensure(&ctx->stage[27], &ctx->stage_bytes[27], (size_t)n * rl) && !ensure(&ctx->stage[28], &ctx->stage_bytes[28], 256 + (size_t)pieces)) {
+			if (!msm_seed(ctx, seed) && !stage_need(ctx, BW_S, (size_t)n * ql) &&
+			    !stage_need(ctx, BW_NE, (size_t)n * ql) && !stage_need(ctx, BW_KEYS, (size_t)n * 2 * cl) &&
+			    !stage_need(ctx, BW_R, (size_t)n * rl) && !stage_need(ctx, BW_VERDICTS, 256 + (size_t)pieces)) {
 				uint8_t **S = ctx->stage;
-				uint32_t *d_flag = (uint32_t *)S[28];
-				uint8_t *d_verdicts = S[28] + 256;
+				uint32_t *d_flag = (uint32_t *)S[BW_VERDICTS];
+				uint8_t *d_verdicts = S[BW_VERDICTS] + 256;
 				uint32_t done = 0;
 				PublicScalars pub_scope(ctx);   // everything a verification multiplies by is public
 				EcamdSchnorrPrepArgs P;
@@ -5643,10 +5738,10 @@ extern "C" int ec_schnorr_verify_msg_all_batch(ecamd_ctx *ctx, const ecamd_curve
 				int begun = 0;
 				if (streamed) {
 					StreamScope scope(ctx, ctx->stream);
-					begun = schnorr_msm_dev_locked(ctx, cv, n, S[24], S[25], S[26], S[27], r_fmt, seed, 0, d_verdicts, nullptr, nullptr, ctx->stream, 0, &step);
+					begun = schnorr_msm_dev_locked(ctx, cv, n, S[BW_S], S[BW_NE], S[BW_KEYS], S[BW_R], r_fmt, seed, 0, d_verdicts, nullptr, nullptr, ctx->stream, 0, &step);
 				}
-				int rc = begun ? -1 : host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &,
-										     hipStream_t s, const std::function<int()> &) {
+				int rc = begun ? -1 : host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &,
+										     hipStream_t s, const Between &) {
 					if (first) {
 						HIPCHK(hipMemsetAsync(d_flag, 0, 4, s));
 						HIPCHK(hipMemsetAsync(d_verdicts, 1, pieces, s));
@@ -5654,28 +5749,28 @@ extern "C" int ec_schnorr_verify_msg_all_batch(ecamd_ctx *ctx, const ecamd_curve
 					}
 					const uint8_t *d_aff = ip[0], *d_kst = nullptr;
 					if (key_fmt == ECAMD_PT_PROJECTIVE) {
-						if (ensure(&ctx->stage[20], &ctx->stage_bytes[20], (size_t)m * 2 * cl) || ensure(&ctx->stage[21], &ctx->stage_bytes[21], m)) {
+						if (stage_need(ctx, SI_PRJ_AFF, (size_t)m * 2 * cl) || stage_need(ctx, SI_PRJ_ST, m)) {
 							return -1;
 						}
 						EcamdPrjInArgs I;
 						I.in = ip[0];
-						I.aff = S[20];
-						I.pre = S[21];
+						I.aff = S[SI_PRJ_AFF];
+						I.pre = S[SI_PRJ_ST];
 						I.n = m;
 						I.clen = (uint32_t)cl;
 						I.for_mul = 0;
 						I.slot = cv->slot;
 						HIPCHK(launch_prj_import(cv, I, s));
-						d_aff = S[20];
-						d_kst = S[21];
+						d_aff = S[SI_PRJ_AFF];
+						d_kst = S[SI_PRJ_ST];
 					}
 					P.keys_aff = d_aff;
 					P.kst = d_kst;
 					P.sigs = ip[1];
 					P.slots = const_cast<uint8_t *>(ip[2]);   // the staged copy of the caller's slots
-					P.keys_out = S[26] + (size_t)done * 2 * cl;
-					P.s_out = S[24] + (size_t)done * ql;
-					P.r_out = S[27] + (size_t)done * rl;
+					P.keys_out = S[BW_KEYS] + (size_t)done * 2 * cl;
+					P.s_out = S[BW_S] + (size_t)done * ql;
+					P.r_out = S[BW_R] + (size_t)done * rl;
 					P.flag = d_flag;
 					P.n = m;
 					P.clen = (uint32_t)cl;
@@ -5688,8 +5783,8 @@ extern "C" int ec_schnorr_verify_msg_all_batch(ecamd_ctx *ctx, const ecamd_curve
 					if (ecdsa_hash_stage(ctx, hash_type, m, ip[2], stride, (uint32_t)hl, s)) {
 						return -1;
 					}
-					N.dig = S[17];
-					N.ne = S[25] + (size_t)done * ql;
+					N.dig = S[ST_DIGESTS];
+					N.ne = S[BW_NE] + (size_t)done * ql;
 					N.n = m;
 					N.hlen = (uint32_t)hl;
 					N.qlen = (uint32_t)ql;
@@ -5698,7 +5793,7 @@ extern "C" int ec_schnorr_verify_msg_all_batch(ecamd_ctx *ctx, const ecamd_curve
 						step.mode = 2;
 						step.first = done;
 						step.count = m;
-						if (schnorr_msm_dev_locked(ctx, cv, n, S[24], S[25], S[26], S[27], r_fmt, seed, 0, d_verdicts, nullptr, nullptr, s, 0, &step)) {
+						if (schnorr_msm_dev_locked(ctx, cv, n, S[BW_S], S[BW_NE], S[BW_KEYS], S[BW_R], r_fmt, seed, 0, d_verdicts, nullptr, nullptr, s, 0, &step)) {
 							return -1;
 						}
 					}
@@ -5711,12 +5806,12 @@ extern "C" int ec_schnorr_verify_msg_all_batch(ecamd_ctx *ctx, const ecamd_curve
 					uint32_t pc = 0;
 					if (streamed) {
 						step.mode = 3;
-						rc = schnorr_msm_dev_locked(ctx, cv, n, S[24], S[25], S[26], S[27], r_fmt, seed, 0, d_verdicts, nullptr, nullptr, s, 0, &step);
+						rc = schnorr_msm_dev_locked(ctx, cv, n, S[BW_S], S[BW_NE], S[BW_KEYS], S[BW_R], r_fmt, seed, 0, d_verdicts, nullptr, nullptr, s, 0, &step);
 					}
 					for (uint32_t off = 0; off < n && !rc && !streamed; off += ctx->max_chunk, pc++) {
 						const uint32_t m = (n - off) < ctx->max_chunk ? (n - off) : ctx->max_chunk;
-						rc = schnorr_msm_dev_locked(ctx, cv, m, S[24] + (size_t)off * ql, S[25] + (size_t)off * ql, S[26] + (size_t)off * 2 * cl,
-									    S[27] + (size_t)off * rl, r_fmt, seed, pc, d_verdicts + pc, nullptr, nullptr, s);
+						rc = schnorr_msm_dev_locked(ctx, cv, m, S[BW_S] + (size_t)off * ql, S[BW_NE] + (size_t)off * ql, S[BW_KEYS] + (size_t)off * 2 * cl,
+									    S[BW_R] + (size_t)off * rl, r_fmt, seed, pc, d_verdicts + pc, nullptr, nullptr, s);
 					}
 					std::vector<uint8_t> v(pieces, 1);
 					uint32_t flag = 1;
@@ -5767,7 +5862,6 @@ extern "C" int ecamd_debug_schnorr_msm(ecamd_ctx *ctx, const ecamd_curve *cv, ui
 	return schnorr_msm_host_locked(ctx, cv, n, s, ne, keys_aff, r, r_fmt, seed, accept, z_out, sum_out);
 }
 
-static void msm_seed_discard(ecamd_ctx *ctx);
 static int eddsa_verify_all_batch_dev_impl(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const void *d_pubkeys,
 					     const void *d_sigs, const void *d_hram, uint32_t hram_len, void *d_verdict,
 					     void *hip_stream);
@@ -5786,7 +5880,7 @@ static int eddsa_verify_all_batch_dev_impl(ecamd_ctx *ctx, const ecamd_curve *cv
 	if (!ctx) {
 		return fail("ec_eddsa_verify_all_batch_dev: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	if (eddsa_args_ok("ec_eddsa_verify_all_batch_dev", ctx, cv_in, n, d_pubkeys, d_sigs, d_hram, d_verdict, hram_len)) {
 		return -1;
 	}
@@ -5830,7 +5924,7 @@ extern "C" int ecamd_debug_eddsa_msm(ecamd_ctx *ctx, const ecamd_curve *cv_in, u
 	if (!ctx || !accept || !seed) {
 		return fail("ecamd_debug_eddsa_msm: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	uint8_t dummy = 0;
 	if (eddsa_args_ok("ecamd_debug_eddsa_msm", ctx, cv_in, n, pubkeys, sigs, hram, &dummy, 64)) {
 		return -1;
@@ -5847,18 +5941,6 @@ extern "C" int ecamd_debug_eddsa_msm(ecamd_ctx *ctx, const ecamd_curve *cv_in, u
 // batch when one random linear combination of the cofactored equations vanishes, which holds when every signature verifies
 // and fails otherwise except with probability ~2^-128 over its random z_i.  Here every item is verified (the batch is the
 // parallel dimension already), so the bit is the exact conjunction and the first rejected index comes for free.
-// the seed of ecamd_ctx_set_msm_seed keys ONE whole-batch call: whichever path that call took (Ed448, a batch below msm_min,
-// mode 0, an error), it is gone afterwards (ADVICE round 3)
-static void msm_seed_discard(ecamd_ctx *ctx)
-{
-	if (ctx) {
-		std::lock_guard<std::mutex> lk(ctx->mu);
-		if (ctx->msm_seed_valid) {
-			memset(ctx->msm_seed_bytes, 0, sizeof(ctx->msm_seed_bytes));
-			ctx->msm_seed_valid = false;
-		}
-	}
-}
 static int eddsa_verify_all_batch_impl(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *pubkeys,
 				       const uint8_t *sigs, const uint8_t *hram, uint32_t hram_len, int *all_valid,
 				       uint32_t *first_rejected);
@@ -5977,7 +6059,7 @@ static int eddsa_sign_setup(const char *fn, ecamd_ctx *ctx, const ecamd_curve *c
 	return 0;
 }
 
-// stage: 3 r big-endian, 4 [r]G, 5 its status
+// SR_: r big-endian, [r]G and its status
 static int eddsa_sign_R_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEdSignArgs &T, uint32_t n,
 				   const uint8_t *d_rhash, uint8_t *d_Renc, uint8_t *d_status, hipStream_t s)
 {
@@ -5992,21 +6074,21 @@ static int eddsa_sign_R_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, const 
 		return 0;
 	}
 	const uint32_t cl = (uint32_t)cv->clen;   // 32 / 56
-	if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], (size_t)n * cl) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], (size_t)n * 2 * cl) ||
-	    ensure(&ctx->stage[5], &ctx->stage_bytes[5], n)) {
+	if (stage_need(ctx, SR_R, (size_t)n * cl) || stage_need(ctx, SR_RW, (size_t)n * 2 * cl) ||
+	    stage_need(ctx, SR_STR, n)) {
 		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	EcamdEdSignArgs A = T;
 	A.n = n;
 	A.r_hash = d_rhash;
-	A.r_be = S[3];
+	A.r_be = S[SR_R];
 	HIPCHK(ecamd_launch_ed_sign_r(A, s));
-	if (smul_dev_locked(ctx, cv, n, S[3], cl, nullptr, S[4], S[5], s)) {   // prj_pt_mul(r, G) (:1776; Ed448: r / 4, :1746)
+	if (smul_dev_locked(ctx, cv, n, S[SR_R], cl, nullptr, S[SR_RW], S[SR_STR], s)) {   // prj_pt_mul(r, G) (:1776; Ed448: r / 4, :1746)
 		return -1;
 	}
-	A.Rw = S[4];
-	A.stR = S[5];
+	A.Rw = S[SR_RW];
+	A.stR = S[SR_STR];
 	A.out = d_Renc;
 	A.status = d_status;
 	HIPCHK(launch_ed_sign_enc(cv, A, s));
@@ -6019,7 +6101,7 @@ extern "C" int ec_eddsa_sign_R_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint
 	if (!ctx) {
 		return fail("ec_eddsa_sign_R_batch: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	EcamdEdSignArgs T;
 	if (eddsa_sign_setup("ec_eddsa_sign_R_batch", ctx, cv, n, r_hash, R_enc, status, &T)) {
 		return -1;
@@ -6029,8 +6111,7 @@ extern "C" int ec_eddsa_sign_R_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint
 	}
 	HIPCHK(hipSetDevice(ctx->device));
 	const std::vector<HostArr> arrs = {{r_hash, nullptr, (size_t)(T.is448 ? 114 : 64)}, {nullptr, R_enc, (size_t)(T.is448 ? 57 : 32)}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return eddsa_sign_R_dev_locked(ctx, cv, T, m, ip[0], op[1], op[2], s);
 	});
 }
@@ -6045,7 +6126,7 @@ extern "C" int ec_eddsa_encode_point_batch(ecamd_ctx *ctx, const ecamd_curve *cv
 	if (!ctx) {
 		return fail("ec_eddsa_encode_point_batch: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	EcamdEdSignArgs T;
 	if (eddsa_sign_setup("ec_eddsa_encode_point_batch", ctx, cv, n, points_prj, enc, status, &T)) {
 		return -1;
@@ -6056,16 +6137,15 @@ extern "C" int ec_eddsa_encode_point_batch(ecamd_ctx *ctx, const ecamd_curve *cv
 	HIPCHK(hipSetDevice(ctx->device));
 	const size_t cl = (size_t)cv->clen, kl = T.is448 ? 57 : 32;
 	const std::vector<HostArr> arrs = {{points_prj, nullptr, 3 * cl}, {nullptr, enc, kl}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
-		// stage: 3 affine points, 4 import status (0 / 1 error / 2 infinity: the encode kernel's convention)
-		if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], (size_t)m * 2 * cl) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], m)) {
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		// import status: 0 / 1 error / 2 infinity, the encode kernel's convention
+		if (stage_need(ctx, EN_AFF, (size_t)m * 2 * cl) || stage_need(ctx, EN_PRE, m)) {
 			return -1;
 		}
 		EcamdPrjInArgs I;
 		I.in = ip[0];
-		I.aff = ctx->stage[3];
-		I.pre = ctx->stage[4];
+		I.aff = ctx->stage[EN_AFF];
+		I.pre = ctx->stage[EN_PRE];
 		I.n = m;
 		I.clen = (uint32_t)cl;
 		I.for_mul = 0;
@@ -6073,8 +6153,8 @@ extern "C" int ec_eddsa_encode_point_batch(ecamd_ctx *ctx, const ecamd_curve *cv
 		HIPCHK(launch_prj_import(cv, I, s));
 		EcamdEdSignArgs A = T;
 		A.n = m;
-		A.Rw = ctx->stage[3];
-		A.stR = ctx->stage[4];
+		A.Rw = ctx->stage[EN_AFF];
+		A.stR = ctx->stage[EN_PRE];
 		A.out = op[1];
 		A.status = op[2];
 		HIPCHK(launch_ed_sign_enc(cv, A, s));
@@ -6088,7 +6168,7 @@ extern "C" int ec_eddsa_sign_S_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint
 	if (!ctx || (n && !S_out)) {
 		return fail("ec_eddsa_sign_S_batch: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	EcamdEdSignArgs T;
 	if (eddsa_sign_setup("ec_eddsa_sign_S_batch", ctx, cv, n, r_hash, hram, a_scalars, &T)) {
 		return -1;
@@ -6099,8 +6179,7 @@ extern "C" int ec_eddsa_sign_S_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint
 	HIPCHK(hipSetDevice(ctx->device));
 	const size_t hl = T.is448 ? 114 : 64, kl = T.is448 ? 57 : 32;
 	const std::vector<HostArr> arrs = {{r_hash, nullptr, hl}, {hram, nullptr, hl}, {a_scalars, nullptr, kl}, {nullptr, S_out, kl}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		EcamdEdSignArgs A = T;
 		A.n = m;
 		A.r_hash = ip[0];
@@ -6116,14 +6195,14 @@ extern "C" int ec_eddsa_sign_S_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint
 // one-call EdDSA signing (include/libecc_amd.h: ec_eddsa_sign_msg_batch, ec_eddsa_pub_key_batch): eddsa_import_key_pair_from_priv_key_buf
 // (sig/eddsa.c:1028) + _eddsa_sign (:1554-1870) per item with every hash on the device (ecamd_eddsa_sign.hip).  Per chunk of at
 // most max_chunk items:
-//   k_eddsa_expand_r        h = H(sk), clamp, PH(M), r_hash: a into stage 30, r_hash into 31, a zero-extended into 32 (keys derived
+//   k_eddsa_expand_r        h = H(sk), clamp, PH(M), r_hash: a into ES_A, r_hash into ES_RHASH, a zero-extended into ES_AWIDE (keys derived
 //                           here), PH(M) into 40, the slot check into 36.  30 - 32 are secret: ensure() wipes what it frees,
 //                           ecamd_ctx_wipe_scratch the rest
-//   eddsa_sign_R_dev_locked pubkeys == NULL: A = encode([a]B) from stage 32 (Ed448: a / 4 and the isogeny, as eddsa_init_pub_key :840
-//                           does with a >> 2) into pub_out or stage 39, its status into 38
-//   eddsa_sign_R_dev_locked R = encode([r]B) into stage 34, its status into 37
-//   k_eddsa_hram            H(dom || R || A || M-or-PH(M)) into stage 33, R into the signature
-//   k_ed_sign_S             S = r + hram a mod q into stage 35
+//   eddsa_sign_R_dev_locked pubkeys == NULL: A = encode([a]B) from ES_AWIDE (Ed448: a / 4 and the isogeny, as eddsa_init_pub_key :840
+//                           does with a >> 2) into pub_out or ES_AENC, its status into ES_STA
+//   eddsa_sign_R_dev_locked R = encode([r]B) into ES_R, its status into ES_STR
+//   k_eddsa_hram            H(dom || R || A || M-or-PH(M)) into ES_HRAM, R into the signature
+//   k_ed_sign_S             S = r + hram a mod q into ES_S
 //   k_eddsa_sign_fin        S into the signature; status; zero bytes where the slot was bad
 // Only enqueues.
 // ------------------------------------------------------------------------------------------
@@ -6142,12 +6221,10 @@ static int eddsa_sign_msg_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, cons
 	const size_t kl = T.is448 ? 57 : 32, hl = 2 * kl;
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
 	const bool derive = d_pub == nullptr, ph = eced::alg_is_ph(alg);
-	const size_t need[11] = {chunk * kl, chunk * hl, derive ? chunk * hl : 0, chunk * hl, chunk * kl, chunk * kl, chunk, chunk, derive ? chunk : 0,
-				 derive && !d_pub_out ? chunk * kl : 0, ph ? (size_t)chunk * eced::PH_LEN : 0};
-	for (int i = 0; i < 11; i++) {
-		if (need[i] && ensure(&ctx->stage[30 + i], &ctx->stage_bytes[30 + i], need[i])) {
-			return -1;
-		}
+	if (stage_need(ctx, {{ES_A, chunk * kl}, {ES_RHASH, chunk * hl}, {ES_AWIDE, derive ? chunk * hl : 0}, {ES_HRAM, chunk * hl}, {ES_R, chunk * kl},
+			     {ES_S, chunk * kl}, {ES_BAD, chunk}, {ES_STR, chunk}, {ES_STA, derive ? chunk : 0},
+			     {ES_AENC, derive && !d_pub_out ? chunk * kl : 0}, {ES_PH, ph ? (size_t)chunk * eced::PH_LEN : 0}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	for (uint32_t off = 0; off < n; off += chunk) {
@@ -6158,53 +6235,53 @@ static int eddsa_sign_msg_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, cons
 		E.sk = d_sk + off * kl;
 		E.slots = d_slots + (size_t)off * stride;
 		E.stride = stride;
-		E.a = S[30];
-		E.r_hash = S[31];
-		E.a_wide = derive ? S[32] : nullptr;
-		E.hram = S[33];
-		E.bad = S[36];
-		E.ph = ph ? S[40] : nullptr;
+		E.a = S[ES_A];
+		E.r_hash = S[ES_RHASH];
+		E.a_wide = derive ? S[ES_AWIDE] : nullptr;
+		E.hram = S[ES_HRAM];
+		E.bad = S[ES_BAD];
+		E.ph = ph ? S[ES_PH] : nullptr;
 		HIPCHK(ecamd_launch_eddsa_expand(alg, E, s));
 		const uint8_t *A_enc = derive ? nullptr : d_pub + off * kl;
 		if (derive) {
-			uint8_t *dst = d_pub_out ? d_pub_out + off * kl : S[39];
-			if (eddsa_sign_R_dev_locked(ctx, cv, T, m, S[32], dst, S[38], s)) {
+			uint8_t *dst = d_pub_out ? d_pub_out + off * kl : S[ES_AENC];
+			if (eddsa_sign_R_dev_locked(ctx, cv, T, m, S[ES_AWIDE], dst, S[ES_STA], s)) {
 				return -1;
 			}
 			A_enc = dst;
 		} else if (d_pub_out) {
 			HIPCHK(hipMemcpyAsync(d_pub_out + off * kl, A_enc, m * kl, hipMemcpyDeviceToDevice, s));
 		}
-		if (eddsa_sign_R_dev_locked(ctx, cv, T, m, S[31], S[34], S[37], s)) {
+		if (eddsa_sign_R_dev_locked(ctx, cv, T, m, S[ES_RHASH], S[ES_R], S[ES_STR], s)) {
 			return -1;
 		}
-		E.R = S[34];
+		E.R = S[ES_R];
 		E.A = A_enc;
 		E.sigs = d_sigs + off * 2 * kl;
 		HIPCHK(ecamd_launch_eddsa_hram(alg, E, s));
 		EcamdEdSignArgs G = T;
 		G.n = m;
-		G.r_hash = S[31];
-		G.hram = S[33];
-		G.a = S[30];
-		G.out = S[35];
+		G.r_hash = S[ES_RHASH];
+		G.hram = S[ES_HRAM];
+		G.a = S[ES_A];
+		G.out = S[ES_S];
 		HIPCHK(ecamd_launch_ed_sign_S(G, s));
-		E.S = S[35];
-		E.stR = S[37];
-		E.stA = derive ? S[38] : nullptr;
+		E.S = S[ES_S];
+		E.stR = S[ES_STR];
+		E.stA = derive ? S[ES_STA] : nullptr;
 		E.status = d_status + off;
 		HIPCHK(ecamd_launch_eddsa_sign_fin(alg, E, s));
 	}
 	return 0;
 }
 
-// stage: 30 a, 32 a zero-extended (both secret)
+// ES_A, ES_AWIDE: a, and a zero-extended (both secret)
 static int eddsa_pub_key_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEdSignArgs &T, uint32_t n, const uint8_t *d_sk,
 				    uint8_t *d_pub_out, uint8_t *d_status, hipStream_t s)
 {
 	const size_t kl = T.is448 ? 57 : 32, hl = 2 * kl;
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (ensure(&ctx->stage[30], &ctx->stage_bytes[30], chunk * kl) || ensure(&ctx->stage[32], &ctx->stage_bytes[32], chunk * hl)) {
+	if (stage_need(ctx, ES_A, chunk * kl) || stage_need(ctx, ES_AWIDE, chunk * hl)) {
 		return -1;
 	}
 	const int alg = T.is448 ? eced::EDDSA448 : eced::EDDSA25519;   // the key expansion is the family's (sig/eddsa.c:650-671)
@@ -6216,10 +6293,10 @@ static int eddsa_pub_key_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, const
 		eddsa_front_args(&E, dom);
 		E.n = m;
 		E.sk = d_sk + off * kl;
-		E.a = ctx->stage[30];
-		E.a_wide = ctx->stage[32];
+		E.a = ctx->stage[ES_A];
+		E.a_wide = ctx->stage[ES_AWIDE];
 		HIPCHK(ecamd_launch_eddsa_expand(alg, E, s));
-		if (eddsa_sign_R_dev_locked(ctx, cv, T, m, ctx->stage[32], d_pub_out + off * kl, d_status + off, s)) {
+		if (eddsa_sign_R_dev_locked(ctx, cv, T, m, ctx->stage[ES_AWIDE], d_pub_out + off * kl, d_status + off, s)) {
 			return -1;
 		}
 	}
@@ -6268,7 +6345,7 @@ extern "C" int ec_eddsa_sign_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv
 	if (!ctx) {
 		return fail("ec_eddsa_sign_msg_batch_dev: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	EcamdEdSignArgs T;
 	eced::Dom dom;
 	if (eddsa_msg_args_ok("ec_eddsa_sign_msg_batch_dev", ctx, cv, alg, n, d_secret_keys, adata, adata_len, d_msg_slots, msg_stride, d_sigs, d_status,
@@ -6292,7 +6369,7 @@ extern "C" int ec_eddsa_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, in
 	if (!ctx) {
 		return fail("ec_eddsa_sign_msg_batch: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	EcamdEdSignArgs T;
 	eced::Dom dom;
 	if (eddsa_msg_args_ok("ec_eddsa_sign_msg_batch", ctx, cv, alg, n, secret_keys, adata, adata_len, msg_slots, msg_stride, sigs, status, &T, &dom)) {
@@ -6306,8 +6383,7 @@ extern "C" int ec_eddsa_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, in
 	// the optional arrays keep their places: an array with neither pointer is neither copied nor read
 	const std::vector<HostArr> arrs = {{secret_keys, nullptr, kl}, {pubkeys, nullptr, pubkeys ? kl : 0}, {msg_slots, nullptr, msg_stride},
 					   {nullptr, sigs, 2 * kl},    {nullptr, pub_out, pub_out ? kl : 0}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-						       hipStream_t s, const std::function<int()> &) {
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return eddsa_sign_msg_dev_locked(ctx, cv, T, alg, dom, m, ip[0], ip[1], ip[2], msg_stride, op[3], op[4], op[5], s);
 	});
 }
@@ -6318,7 +6394,7 @@ extern "C" int ec_eddsa_pub_key_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv,
 	if (!ctx) {
 		return fail("ec_eddsa_pub_key_batch_dev: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	EcamdEdSignArgs T;
 	if (eddsa_sign_setup("ec_eddsa_pub_key_batch_dev", ctx, cv, n, d_secret_keys, d_pub_out, d_status, &T)) {
 		return -1;
@@ -6338,7 +6414,7 @@ extern "C" int ec_eddsa_pub_key_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uin
 	if (!ctx) {
 		return fail("ec_eddsa_pub_key_batch: bad argument");
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: the checks run the curve's one-time setup, under the lock
 	EcamdEdSignArgs T;
 	if (eddsa_sign_setup("ec_eddsa_pub_key_batch", ctx, cv, n, secret_keys, pub_out, status, &T)) {
 		return -1;
@@ -6349,8 +6425,7 @@ extern "C" int ec_eddsa_pub_key_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uin
 	HIPCHK(hipSetDevice(ctx->device));
 	const size_t kl = T.is448 ? 57 : 32;
 	const std::vector<HostArr> arrs = {{secret_keys, nullptr, kl}, {nullptr, pub_out, kl}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-						       hipStream_t s, const std::function<int()> &) {
+	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return eddsa_pub_key_dev_locked(ctx, cv, T, m, ip[0], op[1], op[2], s);
 	});
 }
@@ -6374,57 +6449,54 @@ static int pt_fmt_batch(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, u
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: stages by hand on the context's stream, and sizes its slots before the scope opens
 	HIPCHK(hipSetDevice(ctx->device));
 	const size_t clen = (size_t)cv->clen, alen = 2 * clen;
 	const size_t ilen = (in_fmt ? 3 : 2) * clen, olen = (out_fmt ? 3 : 2) * clen;
-	// stage: 0 scalars, 1 points as given, 2 affine inputs, 3 import status, 4 affine results, 5 their status,
-	//        6 output, 7 output status
-	const size_t need[8] = {mul ? (size_t)n * slen : 0, points ? n * ilen : 0, n * alen, n, n * alen, n, n * olen, n};
-	for (int i = 0; i < 8; i++) {
-		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	// the points as given, their affine form and import status, the affine results and their status, the output in out_fmt
+	if (stage_need(ctx, {{PF_SCALARS, mul ? (size_t)n * slen : 0}, {PF_IN, points ? n * ilen : 0}, {PF_AFF, n * alen}, {PF_PRE, n},
+			     {PF_RES, n * alen}, {PF_RST, n}, {PF_OUT, n * olen}, {PF_OST, n}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	hipStream_t s = ctx->stream;
 	StreamScope scope(ctx, s);
 	if (mul) {
-		HIPCHK(hipMemcpyAsync(S[0], scalars, (size_t)n * slen, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(S[PF_SCALARS], scalars, (size_t)n * slen, hipMemcpyHostToDevice, s));
 	}
 	if (points) {
-		HIPCHK(hipMemcpyAsync(S[1], points, n * ilen, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(S[PF_IN], points, n * ilen, hipMemcpyHostToDevice, s));
 	}
-	const uint8_t *d_aff = points ? S[1] : nullptr;  // affine inputs of the scalar multiplication (NULL: generator)
+	const uint8_t *d_aff = points ? S[PF_IN] : nullptr;  // affine inputs of the scalar multiplication (NULL: generator)
 	const uint8_t *d_pre = nullptr;
 	if (points && in_fmt == 1) {
 		EcamdPrjInArgs I;
-		I.in = S[1];
-		I.aff = S[2];
-		I.pre = S[3];
+		I.in = S[PF_IN];
+		I.aff = S[PF_AFF];
+		I.pre = S[PF_PRE];
 		I.n = n;
 		I.clen = (uint32_t)clen;
 		I.for_mul = mul ? 1 : 0;
 		I.slot = cv->slot;
 		HIPCHK(launch_prj_import(cv, I, s));
-		d_aff = S[2];
-		d_pre = S[3];
+		d_aff = S[PF_AFF];
+		d_pre = S[PF_PRE];
 	}
 	const uint8_t *d_res = d_aff, *d_st = nullptr;
 	if (mul) {
-		if (smul_dev_locked(ctx, cv, n, S[0], slen, d_aff, S[4], S[5], s)) {
+		if (smul_dev_locked(ctx, cv, n, S[PF_SCALARS], slen, d_aff, S[PF_RES], S[PF_RST], s)) {
 			return -1;
 		}
-		d_res = S[4];
-		d_st = S[5];
+		d_res = S[PF_RES];
+		d_st = S[PF_RST];
 	} else if (in_fmt == 0) {
 		// affine in, no multiplication: validation only, through the group-law kernel's import checks
 		// (P + P is computed and dropped; its status carries the import result)
 		EcamdPtArgs A;
-		A.p1 = S[1];
+		A.p1 = S[PF_IN];
 		A.p2 = nullptr;
-		A.out = S[4];
-		A.status = S[5];
+		A.out = S[PF_RES];
+		A.status = S[PF_RST];
 		A.n = n;
 		A.clen = (uint32_t)clen;
 		A.dbl = 1;
@@ -6432,27 +6504,27 @@ static int pt_fmt_batch(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, u
 		HIPCHK(ecamd_launch_pt(cv->nw, A, s));
 		// a valid point may double to infinity (order 2): only the import error matters here
 		std::vector<uint8_t> st(n);
-		HIPCHK(hipMemcpyAsync(st.data(), S[5], n, hipMemcpyDeviceToHost, s));
+		HIPCHK(hipMemcpyAsync(st.data(), S[PF_RST], n, hipMemcpyDeviceToHost, s));
 		HIPCHK(hipStreamSynchronize(s));
 		for (uint32_t i = 0; i < n; i++) {
 			st[i] = st[i] == 1 ? 1 : 0;
 		}
-		HIPCHK(hipMemcpyAsync(S[5], st.data(), n, hipMemcpyHostToDevice, s));
+		HIPCHK(hipMemcpyAsync(S[PF_RST], st.data(), n, hipMemcpyHostToDevice, s));
 		HIPCHK(hipStreamSynchronize(s));
-		d_st = S[5];
+		d_st = S[PF_RST];
 	}
 	EcamdPrjOutArgs O;
 	O.aff = d_res;
 	O.st = d_st;
 	O.pre = d_pre;
-	O.out = S[6];
-	O.status = S[7];
+	O.out = S[PF_OUT];
+	O.status = S[PF_OST];
 	O.n = n;
 	O.clen = (uint32_t)clen;
 	O.out_prj = out_fmt;
 	HIPCHK(ecamd_launch_prj_export(O, s));
-	HIPCHK(hipMemcpyAsync(out, S[6], n * olen, hipMemcpyDeviceToHost, s));
-	HIPCHK(hipMemcpyAsync(status, S[7], n, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(out, S[PF_OUT], n * olen, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(status, S[PF_OST], n, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	return 0;
 }
@@ -6544,37 +6616,35 @@ static int y_from_x_common(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
+	std::lock_guard<std::mutex> lk(ctx->mu);   // own head: stages by hand on the context's stream, and sizes its slots before the scope opens
 	HIPCHK(hipSetDevice(ctx->device));
 	if (sqrt_setup(cv)) {
 		return -1;
 	}
 	const size_t cl = (size_t)cv->clen;
-	const size_t need[4] = {(size_t)n * in_stride, (size_t)n * cl * (mode ? 2 : 1), (size_t)n * cl, n};
-	for (int i = 0; i < 4; i++) {
-		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	const size_t in_bytes = (size_t)n * in_stride, y1_bytes = (size_t)n * cl * (mode ? 2 : 1), y2_bytes = (size_t)n * cl;
+	if (stage_need(ctx, {{YX_IN, in_bytes}, {YX_Y1, y1_bytes}, {YX_Y2, y2_bytes}, {YX_ST, n}})) {
+		return -1;
 	}
 	hipStream_t s = ctx->stream;
 	StreamScope scope(ctx, s);
 	uint8_t **S = ctx->stage;
-	HIPCHK(hipMemcpyAsync(S[0], in, need[0], hipMemcpyHostToDevice, s));
+	HIPCHK(hipMemcpyAsync(S[YX_IN], in, in_bytes, hipMemcpyHostToDevice, s));
 	EcamdYfromXArgs A = cv->sqrt_tmpl;
-	A.x = S[0];
+	A.x = S[YX_IN];
 	A.xstride = in_stride;
-	A.y1 = S[1];
-	A.y2 = S[2];
-	A.aff = S[1];
-	A.status = S[3];
+	A.y1 = S[YX_Y1];
+	A.y2 = S[YX_Y2];
+	A.aff = S[YX_Y1];
+	A.status = S[YX_ST];
 	A.n = n;
 	A.mode = mode;
 	HIPCHK(ecamd_launch_y_from_x(cv->nw, A, s));
-	HIPCHK(hipMemcpyAsync(o1, S[1], need[1], hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(o1, S[YX_Y1], y1_bytes, hipMemcpyDeviceToHost, s));
 	if (mode == 0) {
-		HIPCHK(hipMemcpyAsync(o2, S[2], need[2], hipMemcpyDeviceToHost, s));
+		HIPCHK(hipMemcpyAsync(o2, S[YX_Y2], y2_bytes, hipMemcpyDeviceToHost, s));
 	}
-	HIPCHK(hipMemcpyAsync(status, S[3], n, hipMemcpyDeviceToHost, s));
+	HIPCHK(hipMemcpyAsync(status, S[YX_ST], n, hipMemcpyDeviceToHost, s));
 	HIPCHK(hipStreamSynchronize(s));
 	return 0;
 }
@@ -6605,7 +6675,7 @@ extern "C" int ec_point_decompress_batch(ecamd_ctx *ctx, const ecamd_curve *cv, 
 //   k_recover_fin     Y1 = A + B, Y2 = A - B, two chords with the denominator x_B - x_A, inverted together for eight items
 //   k_recover_redo    the items with A or B at infinity or x_A = x_B, on the complete formulas (nothing marked: a near-empty launch)
 // Every multiplier is a function of the signature and the digest: public, whatever ecamd_ctx_set_secret_scalars says.
-// stage: 3 u, 4 v, 5 A, 6 B, 7 stA, 8 stB, 9 flags, 10 status of k_y_from_x, 11 x, 12 y1, 13 y2, 14 R.  Only enqueues.
+// R is no key: no [q]R pass.  Frame: ST_U .. ST_FLAGS and RC_.  Only enqueues.
 static int ecdsa_recover_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const uint8_t *d_sig, const uint8_t *d_dig,
 				    uint32_t hlen, uint8_t *d_pub1, uint8_t *d_pub2, uint8_t *d_st1, uint8_t *d_st2, hipStream_t s)
 {
@@ -6616,12 +6686,9 @@ static int ecdsa_recover_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv_in, ui
 	PublicScalars pub_scope(ctx);
 	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	const size_t need[15] = {0, 0, 0, chunk * ql, chunk * ql, chunk * plen, chunk * plen, chunk, chunk, chunk, chunk,
-				 chunk * cl, chunk * cl, chunk * cl, chunk * plen};
-	for (int i = 3; i < 15; i++) {
-		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	if (two_mul_need(ctx, cv, chunk) ||
+	    stage_need(ctx, {{RC_YST, chunk}, {RC_X, chunk * cl}, {RC_Y1, chunk * cl}, {RC_Y2, chunk * cl}, {RC_R, chunk * plen}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	for (uint32_t off = 0; off < n; off += chunk) {
@@ -6630,10 +6697,10 @@ static int ecdsa_recover_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv_in, ui
 		memset(&P, 0, sizeof(P));
 		P.sigs = d_sig + (size_t)off * 2 * ql;
 		P.digests = d_dig + (size_t)off * hlen;
-		P.u = S[3];
-		P.v = S[4];
-		P.x = S[11];
-		P.flags = S[9];
+		P.u = S[ST_U];
+		P.v = S[ST_V];
+		P.x = S[RC_X];
+		P.flags = S[ST_FLAGS];
 		P.n = m;
 		P.qlen = (uint32_t)ql;
 		P.clen = (uint32_t)cl;
@@ -6643,44 +6710,29 @@ static int ecdsa_recover_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv_in, ui
 		big_to_be(P.p_be, (int)cl, cv->p);
 		HIPCHK(ecamd_launch_recover_prep(cv->qnw, P, s));
 		EcamdYfromXArgs Y = cv->sqrt_tmpl;
-		Y.x = S[11];
+		Y.x = S[RC_X];
 		Y.xstride = (uint32_t)cl;
-		Y.y1 = S[12];
-		Y.y2 = S[13];
-		Y.aff = S[12];
-		Y.status = S[10];
+		Y.y1 = S[RC_Y1];
+		Y.y2 = S[RC_Y2];
+		Y.aff = S[RC_Y1];
+		Y.status = S[RC_YST];
 		Y.n = m;
 		Y.mode = 0;
 		HIPCHK(ecamd_launch_y_from_x(cv->nw, Y, s));
 		EcamdRecoverPointArgs R;
-		R.x = S[11];
-		R.y1 = S[12];
-		R.flags = S[9];
-		R.yst = S[10];
-		R.R = S[14];
+		R.x = S[RC_X];
+		R.y1 = S[RC_Y1];
+		R.flags = S[ST_FLAGS];
+		R.yst = S[RC_YST];
+		R.R = S[RC_R];
 		R.n = m;
 		R.clen = (uint32_t)cl;
 		HIPCHK(ecamd_launch_recover_point(R, s));
-		if (smul_dev_locked(ctx, cv, m, S[3], (uint32_t)ql, nullptr, S[5], S[7], s) ||   // A = [u]G (:988)
-		    smul_dev_locked(ctx, cv, m, S[4], (uint32_t)ql, S[14], S[6], S[8], s)) {     // B = [v](x, y1) (:990)
+		// A = [u]G (:988), B = [v](x, y1) (:990), Y1 = A + B and Y2 = A - B straight into the caller's arrays
+		if (two_mul_sum_dev(ctx, cv, m, S[RC_R], false, S[RC_YST], d_pub1 + (size_t)off * plen, d_pub2 + (size_t)off * plen, d_st1 + off,
+				    d_st2 + off, s)) {
 			return -1;
 		}
-		EcamdRecoverFinArgs F;
-		F.A = S[5];
-		F.stA = S[7];
-		F.B = S[6];
-		F.stB = S[8];
-		F.flags = S[9];
-		F.yst = S[10];
-		F.out1 = d_pub1 + (size_t)off * plen;
-		F.out2 = d_pub2 + (size_t)off * plen;
-		F.st1 = d_st1 + off;
-		F.st2 = d_st2 + off;
-		F.n = m;
-		F.clen = (uint32_t)cl;
-		F.slot = cv->slot;
-		HIPCHK(ecamd_launch_recover_fin(cv->nw, F, s));
-		HIPCHK(ecamd_launch_recover_redo(cv->nw, F, s));
 	}
 	return 0;
 }
@@ -6709,12 +6761,10 @@ extern "C" int ec_ecdsa_recover_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv,
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return ecdsa_recover_dev_locked(ctx, cv, n, (const uint8_t *)d_sigs, (const uint8_t *)d_digests, hlen, (uint8_t *)d_pub1_aff,
-					(uint8_t *)d_pub2_aff, (uint8_t *)d_status1, (uint8_t *)d_status2, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return ecdsa_recover_dev_locked(ctx, cv, n, (const uint8_t *)d_sigs, (const uint8_t *)d_digests, hlen, (uint8_t *)d_pub1_aff,
+						(uint8_t *)d_pub2_aff, (uint8_t *)d_status1, (uint8_t *)d_status2, s);
+	});
 }
 
 extern "C" int ec_ecdsa_recover_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *sigs, const uint8_t *digests,
@@ -6726,13 +6776,10 @@ extern "C" int ec_ecdsa_recover_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uin
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t plen = (size_t)2 * cv->clen;
 	const std::vector<HostArr> arrs = {{sigs, nullptr, (size_t)2 * cv->qlen}, {digests, nullptr, hlen}, {nullptr, pub1_aff, plen},
 					   {nullptr, pub2_aff, plen}, {nullptr, status1, 1}, {nullptr, status2, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-						       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return ecdsa_recover_dev_locked(ctx, cv, m, ip[0], ip[1], hlen, op[2], op[3], op[4], op[5], s);
 	});
 }
@@ -6748,8 +6795,7 @@ extern "C" int ec_ecdsa_recover_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uin
 //   k_sha2_slots      the digest
 //   k_hsig_cmp        the digest against r
 // and signing is [k]G (secret-scalar mode as the context says), k_hsig_fill, k_sha2_slots, k_hsig_sign.
-// stage: 3 u / [k]G, 4 v / status of [k]G, 5 A, 6 B, 7 stA, 8 stB, 9 flags, 10 subgroup status, 11 [q]Y, 12 W', 13 A - B (a sink: k_recover_fin's second sum, not used here),
-// 14 status of W', 15 status of A - B, 16 staged slots, 17 digests.  Only enqueues.
+// Frames: ST_ with ST_SLOTS and ST_DIGESTS; signing SG_.  Only enqueues.
 // ------------------------------------------------------------------------------------------
 static uint32_t hsig_staged_stride(const ecamd_curve *cv, int alg, uint32_t stride)
 {
@@ -6768,12 +6814,12 @@ static int hsig_stage_hash(ecamd_ctx *ctx, int hash_type, uint32_t m, EcamdHsigA
 	uint8_t **S = ctx->stage;
 	if (H.alg != ECAMD_SIG_ECKCDSA) {
 		// the caller's array is not modified: the coordinates go into a copy
-		HIPCHK(hipMemcpyAsync(S[16], d_in, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
+		HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
 	}
-	H.slots = S[16];
-	H.dg = S[17];
+	H.slots = S[ST_SLOTS];
+	H.dg = S[ST_DIGESTS];
 	HIPCHK(ecamd_launch_hsig_fill(H, s));
-	HIPCHK(ecamd_launch_sha2_slots(hash_type, S[16], H.sstride, m, S[17], H.hsize, s));
+	HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], H.sstride, m, S[ST_DIGESTS], H.hsize, s));
 	return 0;
 }
 
@@ -6790,12 +6836,8 @@ static int hsig_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg
 	const size_t siglen = (size_t)echsig::r_len(alg, (int)hsize, (int)ql) + ql;
 	const uint32_t sstride = hsig_staged_stride(cv, alg, stride);
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	const size_t need[18] = {0, 0, 0, chunk * ql, chunk * ql, chunk * plen, chunk * plen, chunk, chunk, chunk, chunk, chunk * plen + 256,
-				 chunk * plen, chunk * plen, chunk, chunk, (size_t)chunk * sstride, (size_t)chunk * hsize};
-	for (int i = 3; i < 18; i++) {
-		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	if (verify_sum_need(ctx, cv, chunk) || stage_need(ctx, {{ST_SLOTS, (size_t)chunk * sstride}, {ST_DIGESTS, (size_t)chunk * hsize}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	for (uint32_t off = 0; off < n; off += chunk) {
@@ -6805,11 +6847,11 @@ static int hsig_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg
 		memset(&H, 0, sizeof(H));
 		H.sigs = d_sig + (size_t)off * siglen;
 		H.inputs = in;
-		H.u = S[3];
-		H.v = S[4];
-		H.flags = S[9];
-		H.W = S[12];
-		H.stW = S[14];
+		H.u = S[ST_U];
+		H.v = S[ST_V];
+		H.flags = S[ST_FLAGS];
+		H.W = S[ST_W];
+		H.stW = S[ST_STW];
 		H.out = d_res + off;
 		H.n = m;
 		H.qlen = (uint32_t)ql;
@@ -6819,34 +6861,7 @@ static int hsig_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg
 		H.qslot = cv->qslot;
 		H.alg = alg;
 		HIPCHK(ecamd_launch_hsig_prep(cv->qnw, H, s));
-		if (smul_dev_locked(ctx, cv, m, S[3], (uint32_t)ql, nullptr, S[5], S[7], s) ||
-		    smul_dev_locked(ctx, cv, m, S[4], (uint32_t)ql, pub, S[6], S[8], s)) {
-			return -1;
-		}
-		if (big_cmp(cv->order, cv->q) != 0) {
-			// cofactor != 1: ec_pub_key_import_from_aff_buf also requires [q]Y == infinity (sig/ec_key.c:199-205), as in ecdsa_two_smul_dev
-			if (smul_dev_locked(ctx, cv, m, cv->d_gen + plen, (uint32_t)ql, pub, S[11], S[10], s, 0)) {
-				return -1;
-			}
-			HIPCHK(ecamd_launch_status_require(S[8], S[10], 2, m, s));
-		}
-		EcamdRecoverFinArgs F;
-		F.A = S[5];
-		F.stA = S[7];
-		F.B = S[6];
-		F.stB = S[8];
-		F.flags = S[9];
-		F.yst = S[9];
-		F.out1 = S[12];
-		F.out2 = S[13];   // sinks: the recovery kernels also write A - B and its status, which this path never reads
-		F.st1 = S[14];
-		F.st2 = S[15];
-		F.n = m;
-		F.clen = (uint32_t)cl;
-		F.slot = cv->slot;
-		HIPCHK(ecamd_launch_recover_fin(cv->nw, F, s));
-		HIPCHK(ecamd_launch_recover_redo(cv->nw, F, s));
-		if (hsig_stage_hash(ctx, hash_type, m, H, in, stride, s)) {
+		if (verify_sum_dev(ctx, cv, m, pub, s) || hsig_stage_hash(ctx, hash_type, m, H, in, stride, s)) {
 			return -1;
 		}
 		HIPCHK(ecamd_launch_hsig_cmp(H, s));
@@ -6867,16 +6882,16 @@ static int hsig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, 
 		return 0;
 	}
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], chunk * plen) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], chunk) ||
-	    ensure(&ctx->stage[9], &ctx->stage_bytes[9], chunk) || ensure(&ctx->stage[16], &ctx->stage_bytes[16], (size_t)chunk * sstride) ||
-	    ensure(&ctx->stage[17], &ctx->stage_bytes[17], (size_t)chunk * hsize)) {
+	if (stage_need(ctx, SG_KG, chunk * plen) || stage_need(ctx, SG_STKG, chunk) ||
+	    stage_need(ctx, ST_FLAGS, chunk) || stage_need(ctx, ST_SLOTS, (size_t)chunk * sstride) ||
+	    stage_need(ctx, ST_DIGESTS, (size_t)chunk * hsize)) {
 		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	for (uint32_t off = 0; off < n; off += chunk) {
 		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
 		const uint8_t *in = d_in + (size_t)off * stride;
-		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[3], S[4], s)) {   // W = [k]G
+		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {   // W = [k]G
 			return -1;
 		}
 		EcamdHsigArgs H;
@@ -6884,9 +6899,9 @@ static int hsig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, 
 		H.inputs = in;
 		H.privs = d_privs + off * ql;
 		H.nonces = d_nonces + off * ql;
-		H.flags = S[9];
-		H.W = S[3];
-		H.stW = S[4];
+		H.flags = S[ST_FLAGS];
+		H.W = S[SG_KG];
+		H.stW = S[SG_STKG];
 		H.out = d_sigs + (size_t)off * siglen;
 		H.status = d_status + off;
 		H.n = m;
@@ -6939,12 +6954,10 @@ extern "C" int ec_sig_hashed_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve 
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return hsig_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_inputs, stride,
-				      (uint8_t *)d_result, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return hsig_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_inputs, stride,
+					      (uint8_t *)d_result, s);
+	});
 }
 
 extern "C" int ec_sig_hashed_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
@@ -6956,12 +6969,9 @@ extern "C" int ec_sig_hashed_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv,
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t siglen = (size_t)echsig::r_len(alg, echsig::hash_size(hash_type), cv->qlen) + cv->qlen;
 	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, siglen}, {inputs, nullptr, stride}, {nullptr, result, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return hsig_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], s);
 	});
 }
@@ -6975,12 +6985,10 @@ extern "C" int ec_sig_hashed_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *c
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return hsig_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_inputs, stride,
-				    (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return hsig_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_inputs, stride,
+					    (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
 }
 
 extern "C" int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
@@ -6992,13 +7000,10 @@ extern "C" int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, i
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t ql = (size_t)cv->qlen;
 	const size_t siglen = (size_t)echsig::r_len(alg, echsig::hash_size(hash_type), cv->qlen) + ql;
 	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {inputs, nullptr, stride}, {nullptr, sigs, siglen}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-					       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return hsig_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], op[4], s);
 	});
 }
@@ -7015,7 +7020,7 @@ extern "C" int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, i
 //   k_belt_slots      t
 //   k_bign_cmp        t against s0
 // and signing is [k]G (secret-scalar mode as the context says), k_bign_fill, k_belt_slots, k_bign_sign.
-// stage: as hsig_verify_dev_locked up to 15; 16 belt-hash's slots, 17 the digests of the messages, 18 the BelT digests.  Only enqueues.
+// Frames: ST_ with ST_SLOTS (belt-hash's slots), ST_DIGESTS (the digests of the messages) and ST_BELT; signing SG_.  Only enqueues.
 // ------------------------------------------------------------------------------------------
 static int bign_message_digests(ecamd_ctx *ctx, int hash_type, uint32_t m, const uint8_t *d_in, uint32_t stride, EcamdBignArgs &B, hipStream_t s)
 {
@@ -7026,11 +7031,11 @@ static int bign_message_digests(ecamd_ctx *ctx, int hash_type, uint32_t m, const
 	}
 	uint8_t **S = ctx->stage;
 	if (hash_type == ecbign::HASH_BELT) {
-		HIPCHK(ecamd_launch_belt_slots(d_in, stride, m, S[17], B.hsize, s));
+		HIPCHK(ecamd_launch_belt_slots(d_in, stride, m, S[ST_DIGESTS], B.hsize, s));
 	} else {
-		HIPCHK(ecamd_launch_sha2_slots(hash_type, d_in, stride, m, S[17], B.hsize, s));
+		HIPCHK(ecamd_launch_sha2_slots(hash_type, d_in, stride, m, S[ST_DIGESTS], B.hsize, s));
 	}
-	B.dg = S[17];
+	B.dg = S[ST_DIGESTS];
 	B.mslots = d_in;
 	B.mstride = stride;
 	return 0;
@@ -7054,10 +7059,10 @@ static void bign_args(EcamdBignArgs &B, const ecamd_curve *cv, int hash_type, ui
 static int bign_stage_belt(ecamd_ctx *ctx, EcamdBignArgs &B, hipStream_t s)
 {
 	uint8_t **S = ctx->stage;
-	B.slots = S[16];
-	B.bt = S[18];
+	B.slots = S[ST_SLOTS];
+	B.bt = S[ST_BELT];
 	HIPCHK(ecamd_launch_bign_fill(B, s));
-	HIPCHK(ecamd_launch_belt_slots(S[16], B.bstride, B.n, S[18], ecbign::DIGEST_BT, s));
+	HIPCHK(ecamd_launch_belt_slots(S[ST_SLOTS], B.bstride, B.n, S[ST_BELT], ecbign::DIGEST_BT, s));
 	return 0;
 }
 
@@ -7065,17 +7070,14 @@ static int bign_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int has
 				  const uint8_t *d_in, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *d_res, hipStream_t s)
 {
 	PublicScalars pub_scope(ctx);   // u, v and the group order are public
-	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen, siglen = (size_t)ecbign::sig_len(cv->qlen);
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, siglen = (size_t)ecbign::sig_len(cv->qlen);
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
 	EcamdBignArgs B;
 	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
-	const size_t need[19] = {0, 0, 0, chunk * ql, chunk * ql, chunk * plen, chunk * plen, chunk, chunk, chunk, chunk, chunk * plen + 256,
-				 chunk * plen, chunk * plen, chunk, chunk, (size_t)chunk * B.bstride, hash_type ? (size_t)chunk * B.hsize : 0,
-				 (size_t)chunk * ecbign::DIGEST_BT};
-	for (int i = 3; i < 19; i++) {
-		if (ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	if (verify_sum_need(ctx, cv, chunk) ||
+	    stage_need(ctx, {{ST_SLOTS, (size_t)chunk * B.bstride}, {ST_DIGESTS, hash_type ? (size_t)chunk * B.hsize : 0},
+			     {ST_BELT, (size_t)chunk * ecbign::DIGEST_BT}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	for (uint32_t off = 0; off < n; off += chunk) {
@@ -7083,44 +7085,17 @@ static int bign_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int has
 		const uint8_t *pub = d_pub + (size_t)off * plen;
 		B.n = m;
 		B.sigs = d_sig + (size_t)off * siglen;
-		B.u = S[3];
-		B.v = S[4];
-		B.flags = S[9];
-		B.W = S[12];
-		B.stW = S[14];
+		B.u = S[ST_U];
+		B.v = S[ST_V];
+		B.flags = S[ST_FLAGS];
+		B.W = S[ST_W];
+		B.stW = S[ST_STW];
 		B.out = d_res + off;
 		if (bign_message_digests(ctx, hash_type, m, d_in + (size_t)off * stride, stride, B, s)) {
 			return -1;
 		}
 		HIPCHK(ecamd_launch_bign_prep(cv->qnw, B, s));
-		if (smul_dev_locked(ctx, cv, m, S[3], (uint32_t)ql, nullptr, S[5], S[7], s) ||
-		    smul_dev_locked(ctx, cv, m, S[4], (uint32_t)ql, pub, S[6], S[8], s)) {
-			return -1;
-		}
-		if (big_cmp(cv->order, cv->q) != 0) {
-			// cofactor != 1: ec_pub_key_import_from_aff_buf also requires [q]Y == infinity (sig/ec_key.c:199-205), as in hsig_verify_dev_locked
-			if (smul_dev_locked(ctx, cv, m, cv->d_gen + plen, (uint32_t)ql, pub, S[11], S[10], s, 0)) {
-				return -1;
-			}
-			HIPCHK(ecamd_launch_status_require(S[8], S[10], 2, m, s));
-		}
-		EcamdRecoverFinArgs F;
-		F.A = S[5];
-		F.stA = S[7];
-		F.B = S[6];
-		F.stB = S[8];
-		F.flags = S[9];
-		F.yst = S[9];
-		F.out1 = S[12];
-		F.out2 = S[13];   // sinks, as in hsig_verify_dev_locked
-		F.st1 = S[14];
-		F.st2 = S[15];
-		F.n = m;
-		F.clen = (uint32_t)cl;
-		F.slot = cv->slot;
-		HIPCHK(ecamd_launch_recover_fin(cv->nw, F, s));
-		HIPCHK(ecamd_launch_recover_redo(cv->nw, F, s));
-		if (bign_stage_belt(ctx, B, s)) {
+		if (verify_sum_dev(ctx, cv, m, pub, s) || bign_stage_belt(ctx, B, s)) {
 			return -1;
 		}
 		HIPCHK(ecamd_launch_bign_cmp(B, s));
@@ -7136,23 +7111,23 @@ static int bign_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
 	EcamdBignArgs B;
 	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
-	if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], chunk * plen) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], chunk) ||
-	    ensure(&ctx->stage[16], &ctx->stage_bytes[16], (size_t)chunk * B.bstride) ||
-	    ensure(&ctx->stage[17], &ctx->stage_bytes[17], hash_type ? (size_t)chunk * B.hsize : 0) ||
-	    ensure(&ctx->stage[18], &ctx->stage_bytes[18], (size_t)chunk * ecbign::DIGEST_BT)) {
+	if (stage_need(ctx, SG_KG, chunk * plen) || stage_need(ctx, SG_STKG, chunk) ||
+	    stage_need(ctx, ST_SLOTS, (size_t)chunk * B.bstride) ||
+	    stage_need(ctx, ST_DIGESTS, hash_type ? (size_t)chunk * B.hsize : 0) ||
+	    stage_need(ctx, ST_BELT, (size_t)chunk * ecbign::DIGEST_BT)) {
 		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	for (uint32_t off = 0; off < n; off += chunk) {
 		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[3], S[4], s)) {   // W = [k]G
+		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {   // W = [k]G
 			return -1;
 		}
 		B.n = m;
 		B.privs = d_privs + off * ql;
 		B.nonces = d_nonces + off * ql;
-		B.W = S[3];
-		B.stW = S[4];
+		B.W = S[SG_KG];
+		B.stW = S[SG_STKG];
 		B.out = d_sigs + (size_t)off * siglen;
 		B.status = d_status + off;
 		B.sign = 1;
@@ -7202,12 +7177,10 @@ extern "C" int ec_bign_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, i
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return bign_verify_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_inputs, stride, oid,
-				      oid_len, (uint8_t *)d_result, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return bign_verify_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_inputs, stride, oid,
+					      oid_len, (uint8_t *)d_result, s);
+	});
 }
 
 extern "C" int ec_bign_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
@@ -7219,12 +7192,9 @@ extern "C" int ec_bign_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int a
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, (size_t)ecbign::sig_len(cv->qlen)},
 					   {inputs, nullptr, stride}, {nullptr, result, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-						       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return bign_verify_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], ip[2], stride, oid, oid_len, op[3], s);
 	});
 }
@@ -7239,12 +7209,10 @@ extern "C" int ec_bign_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return bign_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_inputs, stride, oid,
-				    oid_len, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return bign_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_inputs, stride, oid,
+					    oid_len, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
 }
 
 extern "C" int ec_bign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
@@ -7257,13 +7225,10 @@ extern "C" int ec_bign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t ql = (size_t)cv->qlen;
 	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {inputs, nullptr, stride},
 					   {nullptr, sigs, (size_t)ecbign::sig_len(cv->qlen)}, {nullptr, status, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-						       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return bign_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], ip[2], stride, oid, oid_len, op[3], op[4], s);
 	});
 }
@@ -7281,9 +7246,7 @@ extern "C" int ec_bign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg
 //   k_schnorr_item_cmp     BIP0340: finite, y even, x = r; ECFSDSA: finite, x || y = r
 // and signing is [k]G (secret-scalar mode as the context says), BIP0340: Y = [x]G (the same) or the caller's key through k_ptf (op 2),
 // k_schnorr_item_fill, k_sha2_slots, k_schnorr_item_sign.
-// stage: 3 s / [k]G, 4 q - e / status of [k]G, 5 A / Y, 6 B, 7 stA / status of Y, 8 stB, 9 flags, 10 subgroup status, 11 [q]Y, 12 W',
-// 13 A - B (a sink), 14 status of W', 15 status of A - B, 16 staged slots, 17 digests, 18 the key as the equation uses it,
-// 20 / 21 the projective import's keys and status, 22 / 23 ECFSDSA's W and its on-curve status.  Only enqueues.
+// Frames: ST_ (ST_U holds s, ST_V q - e) with ST_SLOTS, ST_DIGESTS and SI_; signing SG_.  Only enqueues.
 // ------------------------------------------------------------------------------------------
 static bool schnorr_item_no_room(const ecamd_curve *cv, int alg, uint32_t hsize, uint32_t stride)
 {
@@ -7316,13 +7279,10 @@ static int schnorr_item_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv,
 	const bool fs = alg == ECAMD_SIG_ECFSDSA, prj = key_fmt == ECAMD_PT_PROJECTIVE;
 	const size_t siglen = (size_t)ecschnorr::r_len(alg, (int)cl) + ql, kw = (prj ? 3 : 2) * cl;
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	const size_t need[24] = {0, 0, 0, chunk * ql, chunk * ql, chunk * plen, chunk * plen, chunk, chunk, chunk, chunk, chunk * plen + 256,
-				 chunk * plen, chunk * plen, chunk, chunk, (size_t)chunk * stride, (size_t)chunk * hsize, chunk * plen, 0,
-				 prj ? chunk * plen : 0, prj ? chunk : 0, fs ? chunk * plen : 0, fs ? chunk : 0};
-	for (int i = 3; i < 24; i++) {
-		if (need[i] && ensure(&ctx->stage[i], &ctx->stage_bytes[i], need[i])) {
-			return -1;
-		}
+	if (verify_sum_need(ctx, cv, chunk) ||
+	    stage_need(ctx, {{ST_SLOTS, (size_t)chunk * stride}, {ST_DIGESTS, (size_t)chunk * hsize}, {SI_KEY, chunk * plen},
+			     {SI_PRJ_AFF, prj ? chunk * plen : 0}, {SI_PRJ_ST, prj ? chunk : 0}, {SI_WPT, fs ? chunk * plen : 0}, {SI_WST, fs ? chunk : 0}})) {
+		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	EcamdSchnorrNeArgs N;
@@ -7336,86 +7296,62 @@ static int schnorr_item_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv,
 		if (prj) {
 			EcamdPrjInArgs I;
 			I.in = keys;
-			I.aff = S[20];
-			I.pre = S[21];
+			I.aff = S[SI_PRJ_AFF];
+			I.pre = S[SI_PRJ_ST];
 			I.n = m;
 			I.clen = (uint32_t)cl;
 			I.for_mul = fs ? 1 : 0;   // (0 : 0 : 0): ECFSDSA multiplies the key as it is, BIP0340 takes its unique representative
 			I.slot = cv->slot;
 			HIPCHK(launch_prj_import(cv, I, s));
-			keys = S[20];
-			kst = S[21];
+			keys = S[SI_PRJ_AFF];
+			kst = S[SI_PRJ_ST];
 		}
 		// the caller's array is not modified: the patches go into a copy
-		HIPCHK(hipMemcpyAsync(S[16], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
+		HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
 		EcamdSchnorrItemArgs H;
 		schnorr_item_args(H, cv, alg, hsize, stride, m);
 		H.keys = keys;
 		H.kst = kst;
 		H.gen = cv->d_gen;
 		H.sigs = d_sig + (size_t)off * siglen;
-		H.slots = S[16];
-		H.key_out = S[18];
-		H.s_out = S[3];
-		H.w_out = fs ? S[22] : nullptr;
-		H.flags = S[9];
-		H.wst = fs ? S[23] : nullptr;
-		H.A = S[5];
-		H.stA = S[7];
-		H.W = S[12];
-		H.stW = S[14];
+		H.slots = S[ST_SLOTS];
+		H.key_out = S[SI_KEY];
+		H.s_out = S[ST_U];
+		H.w_out = fs ? S[SI_WPT] : nullptr;
+		H.flags = S[ST_FLAGS];
+		H.wst = fs ? S[SI_WST] : nullptr;
+		H.A = S[ST_A];
+		H.stA = S[ST_STA];
+		H.W = S[ST_W];
+		H.stW = S[ST_STW];
 		H.out = d_res + off;
 		HIPCHK(ecamd_launch_schnorr_item_prep(cv->qnw, H, s));
 		if (fs) {
 			// "Reject the signature if r is not a valid point on the curve" (ecfsdsa.c:449-460): the on-curve test the point calls use
 			EcamdPtfArgs T;
 			memset(&T, 0, sizeof(T));
-			T.p1 = S[22];
-			T.p2 = S[22];
-			T.out = S[22];   // untouched by op 2
-			T.status = S[23];
+			T.p1 = S[SI_WPT];
+			T.p2 = S[SI_WPT];
+			T.out = S[SI_WPT];   // untouched by op 2
+			T.status = S[SI_WST];
 			T.n = m;
 			T.clen = (uint32_t)cl;
 			T.op = 2;
 			T.slot = cv->slot;
 			HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
 		}
-		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[16], stride, m, S[17], hsize, s));
-		N.dig = S[17];
-		N.ne = S[4];
+		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], stride, m, S[ST_DIGESTS], hsize, s));
+		N.dig = S[ST_DIGESTS];
+		N.ne = S[ST_V];
 		N.n = m;
 		N.hlen = hsize;
 		N.qlen = (uint32_t)ql;
 		HIPCHK(ecamd_launch_schnorr_ne(cv->qnw, N, s));
-		if (smul_dev_locked(ctx, cv, m, S[3], (uint32_t)ql, nullptr, S[5], S[7], s) ||
-		    smul_dev_locked(ctx, cv, m, S[4], (uint32_t)ql, S[18], S[6], S[8], s)) {
-			return -1;
-		}
-		if (big_cmp(cv->order, cv->q) != 0) {
-			// cofactor != 1: the key import also requires [q]Y == infinity (sig/ec_key.c:199-205), as in hsig_verify_dev_locked
-			if (smul_dev_locked(ctx, cv, m, cv->d_gen + plen, (uint32_t)ql, S[18], S[11], S[10], s, 0)) {
-				return -1;
-			}
-			HIPCHK(ecamd_launch_status_require(S[8], S[10], 2, m, s));
-		}
-		EcamdRecoverFinArgs F;
-		F.A = S[5];
-		F.stA = S[7];
-		F.B = S[6];
-		F.stB = S[8];
 		// k_recover_fin takes ANY non-zero flag as "no sum for this item": that holds for flag 2 too (ECFSDSA, the key at infinity),
 		// whose verdict k_schnorr_item_cmp reads from A = [s]G and stA, not from W'
-		F.flags = S[9];
-		F.yst = S[9];
-		F.out1 = S[12];
-		F.out2 = S[13];   // sinks, as in hsig_verify_dev_locked
-		F.st1 = S[14];
-		F.st2 = S[15];
-		F.n = m;
-		F.clen = (uint32_t)cl;
-		F.slot = cv->slot;
-		HIPCHK(ecamd_launch_recover_fin(cv->nw, F, s));
-		HIPCHK(ecamd_launch_recover_redo(cv->nw, F, s));
+		if (verify_sum_dev(ctx, cv, m, S[SI_KEY], s)) {
+			return -1;
+		}
 		HIPCHK(ecamd_launch_schnorr_item_cmp(H, s));
 	}
 	return 0;
@@ -7435,16 +7371,16 @@ static int schnorr_item_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, i
 	}
 	const bool bip = alg == ECAMD_SIG_BIP0340;
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (ensure(&ctx->stage[3], &ctx->stage_bytes[3], chunk * plen) || ensure(&ctx->stage[4], &ctx->stage_bytes[4], chunk) ||
-	    ensure(&ctx->stage[9], &ctx->stage_bytes[9], chunk) || ensure(&ctx->stage[16], &ctx->stage_bytes[16], (size_t)chunk * stride) ||
-	    ensure(&ctx->stage[17], &ctx->stage_bytes[17], (size_t)chunk * hsize) ||
-	    (bip && (ensure(&ctx->stage[5], &ctx->stage_bytes[5], chunk * plen) || ensure(&ctx->stage[7], &ctx->stage_bytes[7], chunk)))) {
+	if (stage_need(ctx, SG_KG, chunk * plen) || stage_need(ctx, SG_STKG, chunk) ||
+	    stage_need(ctx, ST_FLAGS, chunk) || stage_need(ctx, ST_SLOTS, (size_t)chunk * stride) ||
+	    stage_need(ctx, ST_DIGESTS, (size_t)chunk * hsize) ||
+	    (bip && (stage_need(ctx, SG_Y, chunk * plen) || stage_need(ctx, SG_STY, chunk)))) {
 		return -1;
 	}
 	uint8_t **S = ctx->stage;
 	for (uint32_t off = 0; off < n; off += chunk) {
 		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[3], S[4], s)) {   // R = [k]G
+		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {   // R = [k]G
 			return -1;
 		}
 		EcamdSchnorrItemArgs H;
@@ -7455,8 +7391,8 @@ static int schnorr_item_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, i
 			memset(&T, 0, sizeof(T));
 			T.p1 = d_pubs + off * plen;
 			T.p2 = T.p1;
-			T.out = S[5];   // untouched by op 2
-			T.status = S[7];
+			T.out = S[SG_Y];   // untouched by op 2
+			T.status = S[SG_STY];
 			T.n = m;
 			T.clen = (uint32_t)cl;
 			T.op = 2;
@@ -7464,24 +7400,24 @@ static int schnorr_item_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, i
 			HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
 			H.keys = d_pubs + off * plen;
 		} else if (bip) {
-			if (smul_dev_locked(ctx, cv, m, d_privs + off * ql, (uint32_t)ql, nullptr, S[5], S[7], s)) {   // Y = [x]G
+			if (smul_dev_locked(ctx, cv, m, d_privs + off * ql, (uint32_t)ql, nullptr, S[SG_Y], S[SG_STY], s)) {   // Y = [x]G
 				return -1;
 			}
-			H.keys = S[5];
+			H.keys = S[SG_Y];
 		}
-		H.kst = bip ? S[7] : nullptr;
+		H.kst = bip ? S[SG_STY] : nullptr;
 		H.privs = d_privs + off * ql;
 		H.nonces = d_nonces + off * ql;
-		H.slots = S[16];
-		H.flags = S[9];
-		H.W = S[3];
-		H.stW = S[4];
-		H.dg = S[17];
+		H.slots = S[ST_SLOTS];
+		H.flags = S[ST_FLAGS];
+		H.W = S[SG_KG];
+		H.stW = S[SG_STKG];
+		H.dg = S[ST_DIGESTS];
 		H.out = d_sigs + (size_t)off * siglen;
 		H.status = d_status + off;
-		HIPCHK(hipMemcpyAsync(S[16], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
+		HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
 		HIPCHK(ecamd_launch_schnorr_item_fill(H, s));
-		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[16], stride, m, S[17], hsize, s));
+		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], stride, m, S[ST_DIGESTS], hsize, s));
 		HIPCHK(ecamd_launch_schnorr_item_sign(cv->qnw, H, s));
 	}
 	return 0;
@@ -7527,12 +7463,10 @@ extern "C" int ec_schnorr_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return schnorr_item_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_keys, key_fmt, (const uint8_t *)d_sigs,
-					      (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_result, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return schnorr_item_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_keys, key_fmt, (const uint8_t *)d_sigs,
+						      (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_result, s);
+	});
 }
 
 extern "C" int ec_schnorr_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *keys, int key_fmt,
@@ -7545,13 +7479,10 @@ extern "C" int ec_schnorr_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, in
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t cl = (size_t)cv->clen, siglen = (size_t)ecschnorr::r_len(alg, cv->clen) + cv->qlen;
 	const std::vector<HostArr> arrs = {{keys, nullptr, (key_fmt == ECAMD_PT_PROJECTIVE ? 3 : 2) * cl}, {sigs, nullptr, siglen},
 					   {hash_slots, nullptr, stride}, {nullptr, result, 1}};
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-						       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return schnorr_item_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], key_fmt, ip[1], ip[2], stride, op[3], s);
 	});
 }
@@ -7566,12 +7497,10 @@ extern "C" int ec_schnorr_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, 
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return schnorr_item_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff,
-					    (const uint8_t *)d_nonces, (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return schnorr_item_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff,
+						    (const uint8_t *)d_nonces, (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
 }
 
 extern "C" int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
@@ -7584,8 +7513,6 @@ extern "C" int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int 
 	if (n == 0) {
 		return 0;
 	}
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
 	const size_t ql = (size_t)cv->qlen, plen = (size_t)2 * cv->clen;
 	const size_t siglen = (size_t)ecschnorr::r_len(alg, cv->clen) + ql;
 	const bool with_pub = alg == ECAMD_SIG_BIP0340 && pubkeys_aff != nullptr;   // ECFSDSA ignores it
@@ -7594,8 +7521,7 @@ extern "C" int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int 
 	if (with_pub) {
 		arrs.push_back({pubkeys_aff, nullptr, plen});
 	}
-	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const std::vector<const uint8_t *> &ip, const std::vector<uint8_t *> &op,
-						       hipStream_t s, const std::function<int()> &) {
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return schnorr_item_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], with_pub ? ip[5] : nullptr, ip[1], ip[2], stride, op[3], op[4], s);
 	});
 }
