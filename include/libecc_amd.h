@@ -360,8 +360,8 @@ int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, 
  *
  * Signing is _ec_sign with the nonce supplied by the caller, as for every other signing call here.
  *   nonces  n x qlen: the value k the scheme multiplies G by, k in [1, q - 1], otherwise status 1.  For BIP0340 that is the reference's
- *           H_nonce(...) mod q (sig/bip0340.c:237-294): the "BIP0340/aux" and "BIP0340/nonce" tagged hashes STAY WITH THE CALLER (unlike RFC 6979
- *           for ECDSA: ec_decdsa_sign_batch).
+ *           H_nonce(...) mod q (sig/bip0340.c:237-294); THIS call takes it from the caller.  ec_bip0340_sign_batch below derives it on
+ *           the device from the aux value (the "BIP0340/aux" and "BIP0340/nonce" tagged hashes), as ec_decdsa_sign_batch does for ECDSA.
  *   privs   n x qlen: x itself.  BIP0340: 0 < x < q, ECFSDSA: x < q (the reference signs with x = 0: s = k), otherwise status 1.
  *   pubkeys_aff  BIP0340: the key pair's public half, n x 2*clen -- its x is hashed and the parity of its y decides d <-> q - d.  NULL:
  *           the device derives Y = [x]G (fixed-base, honours secret-scalar mode).  Non-NULL: imported (coordinates < p, on the curve,
@@ -382,7 +382,8 @@ int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int
 			  uint8_t *status);
 /* BIGN and DBIGN (STB 34.101.45; sig/bign_common.c): the scheme that hashes its commitment with belt-hash (STB 34.101.31),
  * whatever hash the message had.  alg: libecc's ec_alg_type numbers 18 / 19 -- the two verify and sign identically here; they differ
- * in where the nonce comes from, and DBIGN's generator (__bign_determinitic_nonce) STAYS WITH THE CALLER (unlike RFC 6979 for ECDSA: ec_decdsa_sign_batch).
+ * in where the nonce comes from: THESE calls take it from the caller under either alg.  ec_dbign_sign_batch below runs DBIGN's generator
+ * (__bign_determinitic_nonce) on the device, as ec_decdsa_sign_batch does for ECDSA.
  * Any other alg is a call-level error (-1, ecamd_last_error()).
  *   lengths  qlen = ceil(|q| / 8), l = qlen / 2 (integer division).  sigs: n x (l + qlen), s0 (l bytes) then s1 (qlen bytes),
  *            both LITTLE-ENDIAN, as the reference writes them (the digest read as a number and W's coordinates in the hash input
@@ -450,6 +451,50 @@ int ec_rfc6979_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_ty
 			   const uint8_t *digests, uint8_t *nonces, uint8_t *status);
 int ec_decdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *in,
 			 uint32_t in_stride, int in_is_digest, uint8_t *sigs, uint8_t *status);
+/* Deterministic BIGN (DBIGN, libecc's ec_alg_type 19) with the nonce of STB 34.101.45 section 6.3.3 derived ON THE DEVICE, as the
+ * reference's __bign_determinitic_nonce runs it (sig/bign_common.c:200-342), its non-standard choices included.
+ *   ec_dbign_nonce_batch   privs n x qlen big-endian, digests n x digest_len (H(m), digest_len in 1 .. 128); nonces n x qlen big-endian.
+ *            theta = belt-hash(oid || the first 2 l octets of the key written to qlen octets and byte-reversed || t), l = qlen / 2 (an odd
+ *            qlen -- 29, 66 -- drops the key's top octet); r = the digest, zero-padded; n = digest_len / 16, raised to 2 when it is 0 or 1;
+ *            i = 1, 2, ..: s = r_1 ^ .. ^ r_(n-1), the first n - 2 blocks move left, r_(n-1) = F_theta(s) ^ r_n ^ <i>_128, r_n = s; the
+ *            candidate is the first qlen octets of r, little-endian, cut to the bits of q when qlen < 16 n, and the first 16 n octets
+ *            otherwise; accepted when i >= 2 n and 0 < k < q.  status[i] = 0; 1 with a zero nonce only after 1000 candidates rejected at
+ *            i >= 2 n (the reference goes on until i wraps; the worst libecc order rejects 15 in 16).  The nonces are SECRET: the caller
+ *            owns their wiping.
+ *   ec_dbign_sign_batch    ec_key_pair_import_from_priv_key_buf + _ec_sign(DBIGN) per item.  hash_type, inputs, stride and oid follow
+ *            ec_bign_sign_batch's rules.  t: STB's optional additional data, the same for all items, a HOST pointer in the _dev form too;
+ *            t_len in 0 .. 64, otherwise (or t NULL with t_len > 0) a call-level error.  Per chunk: the digests, the nonces into a scratch
+ *            buffer that never leaves the device (wiped when freed and by ecamd_ctx_wipe_scratch), then ec_bign_sign_batch's core:
+ *            bytes and status are those of ec_bign_sign_batch fed with the derived k; its key rules too (x < q, x = 0 signs).
+ * UNLIKE everything else BelT does here, the generator's substitution indices depend on the private key.  In the default mode the
+ * kernel gathers from a table in LDS; after ecamd_ctx_set_secret_scalars(ctx, 1) every look-up reads the whole table at addresses that
+ * do not depend on the index.  Both give the same bytes.  n = 0, NULL arguments, a handle of another context, a bad hash_type or
+ * stride and chunking behave as for ec_decdsa_sign_batch.  Orders of at most 528 bits (qlen <= 66). */
+int ec_dbign_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const uint8_t *privs, const uint8_t *digests,
+			 uint32_t digest_len, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *nonces,
+			 uint8_t *status);
+int ec_dbign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *inputs,
+			uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *sigs,
+			uint8_t *status);
+/* BIP0340 signing with the semi-deterministic nonce derived ON THE DEVICE, as _bip0340_sign runs it (sig/bip0340.c:213-294).  hash_type
+ * 1 .. 4 (the reference does not fix BIP0340 to SHA-256) is the hash of both tagged hashes and of the challenge.  privs, pubkeys_aff
+ * (NULL: Y = [x]G on the device), hash_slots and stride are exactly ec_schnorr_sign_batch's for BIP0340.
+ *   aux      n x qlen big-endian, REQUIRED: the value libecc draws below 2^(8 qlen) through its `rand` hook.  All-zero is legal.
+ *   nonce    d = x, or q - x when Y.y is odd; mask = H(H(tag_aux) || H(tag_aux) || aux); t = d ^ mask over max(qlen, hsize) octets (the
+ *            reference's two length cases); k = OS2I(H(H(tag_nonce) || H(tag_nonce) || t || Y.x || m)) mod q over the whole digest, m being
+ *            the slot's bytes behind its fixed fields.  status 1 with a zero nonce: x = 0 or x >= q, a key that does not import, k = 0,
+ *            a slot that does not hold the fixed fields or does not fit the stride.
+ *   ec_bip0340_nonce_batch   hands the SECRET nonces (n x qlen big-endian) to the caller, who owns their wiping.
+ *   ec_bip0340_sign_batch    Y, then the nonce into a scratch buffer that never leaves the device, then ec_schnorr_sign_batch's core:
+ *            signature bytes (clen + qlen) and status are those of ec_schnorr_sign_batch fed with that k.
+ * The generator looks nothing up by a secret; [k]G and [x]G honour ecamd_ctx_set_secret_scalars.  n = 0, NULL arguments (aux
+ * included), a handle of another context, a bad hash_type or stride and chunking behave as for ec_decdsa_sign_batch. */
+int ec_bip0340_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs,
+			   const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *nonces,
+			   uint8_t *status);
+int ec_bip0340_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs,
+			  const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+			  uint8_t *status);
 /* ec_key_pair_gen's generic rule (sig/ec_key.c:594-610): x = nn_get_random_mod(q) from the item's 2*qlen random bytes, Y = [x]G.
  * priv_out: n x qlen big-endian; pub_out: n x 2*clen affine X || Y; status as ec_prj_pt_mul_batch.  (Secret scalars: see
  * ecamd_ctx_set_secret_scalars; the private keys cross the bus on their way back, as supplied ones do on their way in.) */
@@ -755,6 +800,23 @@ int ec_rfc6979_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int has
 			       const void *d_digests, void *d_nonces, void *d_status, void *hip_stream);
 int ec_decdsa_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs, const void *d_in,
 			     uint32_t in_stride, int in_is_digest, void *d_sigs, void *d_status, void *hip_stream);
+/* ec_dbign_nonce_batch / ec_dbign_sign_batch / ec_bip0340_nonce_batch / ec_bip0340_sign_batch with device pointers: enqueue only (oid and
+ * t stay host pointers: they are copied into the kernel arguments before the call returns).  Scratch of the signing calls: per item of
+ * a chunk the nonce (qlen bytes, secret) and what ec_bign_sign_batch_dev / ec_schnorr_sign_batch_dev take; the BIP0340 calls also Y and
+ * its status.  Message slots must be 4-byte aligned (the length word is read as one aligned word); keys, aux values and digests are
+ * read by octets.  d_pubkeys_aff may be NULL.  d_nonces of the nonce calls is the caller's buffer: secret, and the caller's to wipe. */
+int ec_dbign_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const void *d_privs, const void *d_digests,
+			     uint32_t digest_len, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, void *d_nonces,
+			     void *d_status, void *hip_stream);
+int ec_dbign_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs, const void *d_inputs,
+			    uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, void *d_sigs,
+			    void *d_status, void *hip_stream);
+int ec_bip0340_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs,
+			       const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_nonces,
+			       void *d_status, void *hip_stream);
+int ec_bip0340_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs,
+			      const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+			      void *d_status, void *hip_stream);
 /* ec_eddsa_sign_msg_batch / ec_eddsa_pub_key_batch with device pointers: enqueue only (sig/eddsa.c:611-688 and :1554-1870 on the
  * device).  adata stays host memory: it is copied into the kernel arguments before the call returns.  d_pubkeys and d_pub_out may be
  * NULL.  d_msg_slots must be 4-byte aligned (the length word is read as one aligned word); keys and encodings need no alignment.

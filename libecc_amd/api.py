@@ -35,6 +35,8 @@ EXPORTED_SYMBOLS = [
     "ec_bign_verify_batch", "ec_bign_verify_batch_dev", "ec_bign_sign_batch", "ec_bign_sign_batch_dev",
     "ec_rfc6979_nonce_batch", "ec_rfc6979_nonce_batch_dev", "ec_decdsa_sign_batch", "ec_decdsa_sign_batch_dev",
     "ec_eddsa_sign_msg_batch", "ec_eddsa_sign_msg_batch_dev", "ec_eddsa_pub_key_batch", "ec_eddsa_pub_key_batch_dev",
+    "ec_dbign_nonce_batch", "ec_dbign_nonce_batch_dev", "ec_dbign_sign_batch", "ec_dbign_sign_batch_dev",
+    "ec_bip0340_nonce_batch", "ec_bip0340_nonce_batch_dev", "ec_bip0340_sign_batch", "ec_bip0340_sign_batch_dev",
 ]
 
 # libecc's ec_alg_type numbers of the EdDSA variants ec_eddsa_sign_msg_batch serves (lib_ecc_types.h:49-55)
@@ -152,6 +154,14 @@ def load_library():
         L.ec_rfc6979_nonce_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, vp, vp]
         L.ec_decdsa_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u32, C.c_int, u8p, u8p]
         L.ec_decdsa_sign_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u32, C.c_int, vp, vp, vp]
+        L.ec_dbign_nonce_batch.argtypes = [vp, vp, u32, u8p, u8p, u32, u8p, u32, u8p, u32, u8p, u8p]
+        L.ec_dbign_nonce_batch_dev.argtypes = [vp, vp, u32, vp, vp, u32, u8p, u32, u8p, u32, vp, vp, vp]
+        L.ec_dbign_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u32, u8p, u32, u8p, u32, u8p, u8p]
+        L.ec_dbign_sign_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u32, u8p, u32, u8p, u32, vp, vp, vp]
+        L.ec_bip0340_nonce_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u8p, u32, u8p, u8p]
+        L.ec_bip0340_nonce_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, vp, u32, vp, vp, vp]
+        L.ec_bip0340_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u8p, u32, u8p, u8p]
+        L.ec_bip0340_sign_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, vp, u32, vp, vp, vp]
         L.ec_eddsa_sign_msg_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u32, u8p, u8p, u8p]
         L.ec_eddsa_sign_msg_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u8p, u32, vp, u32, vp, vp, vp, vp]
         L.ec_eddsa_pub_key_batch.argtypes = [vp, vp, u32, u8p, u8p, u8p]
@@ -532,6 +542,43 @@ class Curve:
              "ec_decdsa_sign_batch")
         return sigs.raw[:2 * self.qlen * n], st.raw[:n]
 
+    def dbign_nonce(self, privs, digests, digest_len, oid, t=b""):
+        """the nonces of deterministic BIGN (STB 34.101.45 section 6.3.3) derived on the device from the digests of the messages
+        (digest_len octets each), the OID of their hash and the optional additional data t: (n x qlen big-endian, status)"""
+        n = len(privs) // self.qlen
+        out, st = C.create_string_buffer(max(1, self.qlen * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_dbign_nonce_batch(self.ctx.h, self.h, n, privs, digests, digest_len, oid, len(oid), t, len(t), out, st),
+             "ec_dbign_nonce_batch")
+        return out.raw[:self.qlen * n], st.raw[:n]
+
+    def dbign_sign(self, hash_type, privs, inputs, stride, oid, t=b""):
+        """deterministic BIGN signatures (s0 || s1, little-endian) and a status byte per item, the nonce derived on the device;
+        hash_type, inputs, stride and oid as for bign_sign"""
+        n = len(privs) // self.qlen
+        sl = self.bign_siglen()
+        sigs, st = C.create_string_buffer(max(1, sl * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_dbign_sign_batch(self.ctx.h, self.h, hash_type, n, privs, inputs, stride, oid, len(oid), t, len(t), sigs, st),
+             "ec_dbign_sign_batch")
+        return sigs.raw[:sl * n], st.raw[:n]
+
+    def bip0340_nonce(self, hash_type, privs, pubs, aux, slots, stride):
+        """BIP0340's nonces derived on the device from the keys, the aux values (n x qlen big-endian) and the signing slots of
+        schnorr_sign; pubs: X || Y per item, or None (Y = [x]G on the device): (n x qlen big-endian, status)"""
+        n = len(privs) // self.qlen
+        out, st = C.create_string_buffer(max(1, self.qlen * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_bip0340_nonce_batch(self.ctx.h, self.h, hash_type, n, privs, pubs, aux, slots, stride, out, st),
+             "ec_bip0340_nonce_batch")
+        return out.raw[:self.qlen * n], st.raw[:n]
+
+    def bip0340_sign(self, hash_type, privs, pubs, aux, slots, stride):
+        """BIP0340 signatures (r || s) and a status byte per item, the nonce derived on the device from the aux values"""
+        n = len(privs) // self.qlen
+        sl = self.clen + self.qlen
+        sigs, st = C.create_string_buffer(max(1, sl * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_bip0340_sign_batch(self.ctx.h, self.h, hash_type, n, privs, pubs, aux, slots, stride, sigs, st),
+             "ec_bip0340_sign_batch")
+        return sigs.raw[:sl * n], st.raw[:n]
+
     def key_pair_gen_raw(self, raw):
         """x = nn_get_random_mod value of the item's 2 * qlen random bytes, Y = [x]G: (privs, pubs affine, status)"""
         n = len(raw) // (2 * self.qlen)
@@ -748,6 +795,22 @@ class Curve:
     def decdsa_sign_dev(self, hash_type, n, d_privs, d_in, stride, is_digest, d_sigs, d_status, stream=None):
         _chk(self.L, self.L.ec_decdsa_sign_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_in, stride, 1 if is_digest else 0, d_sigs,
                                                       d_status, stream), "ec_decdsa_sign_batch_dev")
+
+    def dbign_nonce_dev(self, n, d_privs, d_digests, digest_len, oid, t, d_nonces, d_status, stream=None):
+        _chk(self.L, self.L.ec_dbign_nonce_batch_dev(self.ctx.h, self.h, n, d_privs, d_digests, digest_len, oid, len(oid), t, len(t), d_nonces,
+                                                      d_status, stream), "ec_dbign_nonce_batch_dev")
+
+    def dbign_sign_dev(self, hash_type, n, d_privs, d_inputs, stride, oid, t, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_dbign_sign_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_inputs, stride, oid, len(oid), t, len(t), d_sigs,
+                                                     d_status, stream), "ec_dbign_sign_batch_dev")
+
+    def bip0340_nonce_dev(self, hash_type, n, d_privs, d_pubs, d_aux, d_slots, stride, d_nonces, d_status, stream=None):
+        _chk(self.L, self.L.ec_bip0340_nonce_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_pubs, d_aux, d_slots, stride, d_nonces,
+                                                        d_status, stream), "ec_bip0340_nonce_batch_dev")
+
+    def bip0340_sign_dev(self, hash_type, n, d_privs, d_pubs, d_aux, d_slots, stride, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_bip0340_sign_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_pubs, d_aux, d_slots, stride, d_sigs,
+                                                       d_status, stream), "ec_bip0340_sign_batch_dev")
 
     def ecccdh_dev(self, n, d_privs, d_peers, d_secrets, d_status, stream=None):
         _chk(self.L, self.L.ec_ecccdh_derive_batch_dev(self.ctx.h, self.h, n, d_privs, d_peers, d_secrets, d_status,

@@ -17,10 +17,15 @@
 // The table is reached through a template parameter `Tab` (anything indexable by an octet): the kernel passes a pointer into
 // LDS, the host build (tests/bign_host_shim.cpp) a plain array.
 //
-// SECRET-SCALAR MODE: everything BelT touches in this library is public.  BIGN hashes the OID, the coordinates of the commitment
-// W -- which every verifier recomputes from the signature -- and the digest of the message; the message hash of hash_type 16 is
-// over the message.  No look-up index depends on a private key or a nonce, so the table look-ups are not masked in secret-scalar
-// mode either.
+// SECRET DATA: what BIGN's verification and signing hash is public -- the OID, the coordinates of the commitment W, which every
+// verifier recomputes from the signature, and the digest of the message (the message itself for hash_type 16) -- so k_belt_slots
+// and the host shims pass a plain table and the look-ups are indexed by public octets.  DBIGN's nonce generator (ecamd_dbign_nonce.h,
+// k_dbign_nonce) is different: its belt-hash runs over the private key and its block cipher is keyed by the result, so there EVERY
+// substitution index depends on the private key.  In the library's default mode that kernel gathers from the LDS table like the
+// others (the default mode allows secret-dependent addresses: the comb does the same); in secret-scalar mode
+// (ecamd_ctx_set_secret_scalars) it passes ScanTab below, whose look-up reads all 64 dwords of the table at addresses that do not
+// depend on the index and keeps the wanted octet with compares and shifts.  A Tab whose g() is overloaded (ScanTab) also gets the
+// rolled form of the cipher, encrypt_rolled: the scan is long, and eight unrolled rounds of it would not fit the instruction cache.
 //
 // LDS layout: the table is kept as 256 OCTETS (64 dwords).  For ds_read_u8 the bank of byte address a is (a / 4) mod 32 within a
 // 32-lane group and equal dwords broadcast, so a gather meets at most 2 distinct dwords per bank (2 LDS cycles per group at worst);
@@ -65,6 +70,81 @@ template <class Tab> ECB_FN uint32_t g(const Tab &H, uint32_t u, int r)
 	return (t << r) | (t >> (32 - r));
 }
 
+// The table behind a look-up that forms no address from its index: w points at the 256 octets as 64 dwords (octet i in bits
+// 8 (i mod 4) of dword i / 4); every look-up reads all of them in order -- on the device at wave-uniform LDS addresses, which
+// broadcast -- and keeps the one wanted with a compare.
+struct ScanTab {
+	const uint32_t *w;
+	ECB_FN uint8_t operator[](uint32_t i) const
+	{
+		uint32_t t = 0;
+#pragma unroll 16
+		for (uint32_t j = 0; j < 64u; j++) {
+			const uint32_t T = w[j];
+			t = (i >> 2) == j ? T : t;
+		}
+		return (uint8_t)(t >> (8u * (i & 3u)));
+	}
+};
+
+// G_r(u) over ScanTab: one scan serves the four octets
+ECB_FN uint32_t g(const ScanTab &H, uint32_t u, int r)
+{
+	const uint32_t i0 = u & 0xffu, i1 = (u >> 8) & 0xffu, i2 = (u >> 16) & 0xffu, i3 = u >> 24;
+	uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0;
+#pragma unroll 16
+	for (uint32_t j = 0; j < 64u; j++) {
+		const uint32_t T = H.w[j];
+		t0 = (i0 >> 2) == j ? T : t0;
+		t1 = (i1 >> 2) == j ? T : t1;
+		t2 = (i2 >> 2) == j ? T : t2;
+		t3 = (i3 >> 2) == j ? T : t3;
+	}
+	const uint32_t t = ((t0 >> (8u * (i0 & 3u))) & 0xffu) | (((t1 >> (8u * (i1 & 3u))) & 0xffu) << 8) |
+			   (((t2 >> (8u * (i2 & 3u))) & 0xffu) << 16) | (((t3 >> (8u * (i3 & 3u))) & 0xffu) << 24);
+	return (t << r) | (t >> (32 - r));
+}
+
+// x <- F_key(x) with the eight rounds as a loop: the round keys K_(7i-6) .. K_(7i) are key[0 .. 6] of a copy that is rotated by
+// seven places (= back by one) after each round, so every index is still a constant.  The same bytes as encrypt below.
+template <class Tab> ECB_FN void encrypt_rolled(const Tab &H, const uint32_t (&key)[8], uint32_t (&x)[4])
+{
+	uint32_t a = x[0], b = x[1], c = x[2], d = x[3];
+	uint32_t k0 = key[0], k1 = key[1], k2 = key[2], k3 = key[3], k4 = key[4], k5 = key[5], k6 = key[6], k7 = key[7];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+#endif
+	for (uint32_t i = 1; i <= 8; i++) {
+		b ^= g(H, a + k0, 5);
+		c ^= g(H, d + k1, 21);
+		a -= g(H, b + k2, 13);
+		const uint32_t e = g(H, b + c + k3, 21) ^ i;
+		b += e;
+		c -= e;
+		d += g(H, c + k4, 13);
+		b ^= g(H, a + k5, 21);
+		c ^= g(H, d + k6, 5);
+		const uint32_t na = b, nb = d, nc = a, nd = c;
+		a = na;
+		b = nb;
+		c = nc;
+		d = nd;
+		const uint32_t last = k7;
+		k7 = k6;
+		k6 = k5;
+		k5 = k4;
+		k4 = k3;
+		k3 = k2;
+		k2 = k1;
+		k1 = k0;
+		k0 = last;
+	}
+	x[0] = b;
+	x[1] = d;
+	x[2] = a;
+	x[3] = c;
+}
+
 // x <- F_key(x).  Fully unrolled, so that every index into key[] is a constant (the arrays stay in registers).
 template <class Tab> ECB_FN void encrypt(const Tab &H, const uint32_t (&key)[8], uint32_t (&x)[4])
 {
@@ -93,6 +173,8 @@ template <class Tab> ECB_FN void encrypt(const Tab &H, const uint32_t (&key)[8],
 	x[2] = a;
 	x[3] = c;
 }
+
+ECB_FN void encrypt(const ScanTab &H, const uint32_t (&key)[8], uint32_t (&x)[4]) { encrypt_rolled(H, key, x); }
 
 // One step of the iteration on a 256-bit block X: t = sigma1(X || h) is XORed into s, and h <- sigma2(X || h).
 template <class Tab> ECB_FN void step(const Tab &H, const uint32_t (&X)[8], uint32_t (&s)[4], uint32_t (&h)[8])

@@ -9,7 +9,7 @@
 //            t = the first min(l, 32) bytes of belt-hash(OID || first 2l bytes of LE(W.x) || LE(W.y) || digest), zero-padded
 //            to l bytes; accept iff t = s0 over all l bytes (l = 33 on a 521-bit order: byte 32 of s0 must be 0)
 //   sign:    x < q; W = [k]G; s0 = t as above; s1 = k - hbar - (s0 + 2^(8l)) x.  No restart, no test of s1.
-// BIGN and DBIGN differ in where the nonce comes from only, and that stays with the caller.
+// BIGN and DBIGN differ in where the nonce comes from only: these steps take it as given (DBIGN's generator is ecamd_dbign_nonce.h).
 //
 // Written against the `Ops` policy of ecamd_sigfam.h, so the same text runs in the kernels (ecamd_bign_kernels.h) and on the host
 // in tests/bign_host_shim.cpp.

@@ -25,6 +25,8 @@
 #include "ecamd_schnorr.h"
 #include "ecamd_bign.h"
 #include "ecamd_rfc6979.h"
+#include "ecamd_dbign_nonce.h"
+#include "ecamd_bip0340_nonce.h"
 #include "ecamd_eddsa_sign.h"
 
 // ------------------------------------------------------------------------------------------
@@ -232,7 +234,7 @@ static const CurveRow g_curve_rows[] = {
 //   VP_  secp256r1 loop       3..5, 7       ecdsa_verify_dev_locked (ST_U, ST_V and VP_*); its redo pass is the ST_ frame, after it   ST_TARGET, EF_
 //   RC_  recovery             10..14        ecdsa_recover_dev_locked, on top of ST_U .. ST_FLAGS (it has no [q]Y pass and no W' of its own)
 //   SG_  signing              3..5, 7, 20   ecdsa_ / sig_ / hsig_ / bign_ / schnorr_item_sign_dev_locked, ec_ecdsa_sign_msg_batch,
-//                                           decdsa_sign_dev_locked (SG_NONCES)                     ST_FLAGS, ST_SLOTS, ST_DIGESTS, ST_BELT
+//                                           decdsa_sign_ / dbign_sign_ / bip0340_dev_locked (SG_NONCES)   ST_FLAGS, ST_SLOTS, ST_DIGESTS, ST_BELT
 //   EV_  EdDSA verification   3..15, 18, 19 eddsa_verify_dev_locked, eddsa448_verify_dev_locked, eddsa448_msm_dev_locked   ST_DIGESTS (h), EP_, EB_, MH_
 //   SR_  EdDSA [r]B           3..5          eddsa_sign_R_dev_locked                                ES_ (it runs inside the one-call signing)
 //   EN_  EdDSA point encoding 3, 4          ec_eddsa_encode_point_batch                            nothing
@@ -7524,6 +7526,372 @@ extern "C" int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int 
 	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return schnorr_item_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], with_pub ? ip[5] : nullptr, ip[1], ip[2], stride, op[3], op[4], s);
 	});
+}
+
+// ------------------------------------------------------------------------------------------
+// DBIGN and BIP0340 with the nonce derived ON THE DEVICE (include/libecc_amd.h: ec_dbign_nonce_batch, ec_dbign_sign_batch,
+// ec_bip0340_nonce_batch, ec_bip0340_sign_batch): the two generators of ecamd_detnonce.hip in front of the signing cores above.
+// Per chunk of at most max_chunk items
+//   DBIGN    k_sha2_slots / k_belt_slots (hash_type != 0), k_dbign_nonce into SG_NONCES (the table scanned in secret-scalar mode),
+//            bign_sign_dev_locked on the chunk (it hashes the chunk's messages again for its own frame: a compression or two per item)
+//   BIP0340  Y = [x]G into SG_Y (or the on-curve test of the caller's keys), k_bip0340_nonce into SG_NONCES,
+//            schnorr_item_sign_dev_locked on the chunk with Y as its supplied key (so [x]G is computed once)
+// Every slot the cores size is sized here first, for the whole chunk, so no buffer moves between the generator and the core.
+// SG_NONCES is secret: ensure() wipes what it frees, ecamd_ctx_wipe_scratch the rest.  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static const uint32_t h_sha256_k[64] = {ECAMD_SHA256_K};
+static const uint64_t h_sha512_k[80] = {ECAMD_SHA512_K};
+
+static int det_order_ok(const char *fn, const ecamd_curve *cv)
+{
+	if (cv->qslot < 0 || big_bitlen(cv->q) < 2 || cv->q.size() > 17 || cv->qlen > ecrfc::MAX_QLEN ||
+	    (uint32_t)cv->qlen != ((uint32_t)cv->qbits + 7) / 8 || cv->clen > ecbip::MAX_CLEN) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	return 0;
+}
+
+static int dbign_nonce_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_privs, const uint8_t *d_digests, uint32_t hlen,
+				  const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *d_nonces, uint8_t *d_status,
+				  hipStream_t s)
+{
+	EcamdDbignNonceArgs D;
+	memset(&D, 0, sizeof(D));
+	D.privs = d_privs;
+	D.digests = d_digests;
+	D.nonces = d_nonces;
+	D.status = d_status;
+	D.n = n;
+	D.qlen = (uint32_t)cv->qlen;
+	D.qbits = (uint32_t)cv->qbits;
+	D.hlen = hlen;
+	D.oid_len = oid_len;
+	D.t_len = t_len;
+	D.scan = ctx->secret_scalars ? 1 : 0;
+	for (int w = 0; w < 17; w++) {
+		D.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
+	}
+	if (oid_len) {
+		memcpy(D.oid, oid, oid_len);
+	}
+	if (t_len) {
+		memcpy(D.t, t, t_len);
+	}
+	HIPCHK(ecamd_launch_dbign_nonce(D, s));
+	return 0;
+}
+
+static int dbign_common_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, const uint8_t *oid, uint32_t oid_len, const uint8_t *t,
+			   uint32_t t_len)
+{
+	if (oid_len > (uint32_t)ecdbign::MAX_OID || (oid_len && !oid)) {
+		return fail(std::string(fn) + ": oid_len must be 0 .. 64, and oid non-NULL when it is not 0");
+	}
+	if (t_len > (uint32_t)ecdbign::MAX_T || (t_len && !t)) {
+		return fail(std::string(fn) + ": t_len must be 0 .. 64, and t non-NULL when it is not 0");
+	}
+	if (!ctx || !cv || cv->ctx != ctx) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	return det_order_ok(fn, cv);
+}
+
+static int dbign_nonce_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const void *a, const void *b, uint32_t digest_len,
+			       const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, const void *c, const void *d)
+{
+	if (digest_len < 1 || digest_len > (uint32_t)ecdbign::MAX_DIGEST) {
+		return fail(std::string(fn) + ": digest_len must be 1 .. 128");
+	}
+	if (dbign_common_ok(fn, ctx, cv, oid, oid_len, t, t_len)) {
+		return -1;
+	}
+	if (n && (!a || !b || !c || !d)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	return 0;
+}
+
+extern "C" int ec_dbign_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const void *d_privs, const void *d_digests,
+					uint32_t digest_len, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, void *d_nonces,
+					void *d_status, void *hip_stream)
+{
+	if (dbign_nonce_args_ok("ec_dbign_nonce_batch_dev", ctx, cv, n, d_privs, d_digests, digest_len, oid, oid_len, t, t_len, d_nonces, d_status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return dbign_nonce_dev_locked(ctx, cv, n, (const uint8_t *)d_privs, (const uint8_t *)d_digests, digest_len, oid, oid_len, t, t_len,
+					      (uint8_t *)d_nonces, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_dbign_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *privs, const uint8_t *digests,
+				    uint32_t digest_len, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *nonces,
+				    uint8_t *status)
+{
+	if (dbign_nonce_args_ok("ec_dbign_nonce_batch", ctx, cv, n, privs, digests, digest_len, oid, oid_len, t, t_len, nonces, status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {digests, nullptr, digest_len}, {nullptr, nonces, ql}, {nullptr, status, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return dbign_nonce_dev_locked(ctx, cv, m, ip[0], ip[1], digest_len, oid, oid_len, t, t_len, op[2], op[3], s);
+	});
+}
+
+static int dbign_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_in,
+				 uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *d_sigs,
+				 uint8_t *d_status, hipStream_t s)
+{
+	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen, siglen = (size_t)ecbign::sig_len(cv->qlen);
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	EcamdBignArgs B;
+	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
+	if (stage_need(ctx, {{SG_NONCES, (size_t)chunk * ql}, {SG_KG, chunk * plen}, {SG_STKG, chunk}, {ST_SLOTS, (size_t)chunk * B.bstride},
+			     {ST_DIGESTS, hash_type ? (size_t)chunk * B.hsize : 0}, {ST_BELT, (size_t)chunk * ecbign::DIGEST_BT}})) {
+		return -1;
+	}
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		const uint8_t *in = d_in + (size_t)off * stride;
+		B.n = m;
+		if (bign_message_digests(ctx, hash_type, m, in, stride, B, s)) {
+			return -1;
+		}
+		// (the generator's status lands in the caller's status bytes and is replaced by the signing core's: a zero nonce is status 1 there)
+		if (dbign_nonce_dev_locked(ctx, cv, m, d_privs + off * ql, B.dg, B.hsize, oid, oid_len, t, t_len, ctx->stage[SG_NONCES], d_status + off, s) ||
+		    bign_sign_dev_locked(ctx, cv, hash_type, m, d_privs + off * ql, ctx->stage[SG_NONCES], in, stride, oid, oid_len,
+					 d_sigs + (size_t)off * siglen, d_status + off, s)) {
+			return -1;
+		}
+	}
+	return 0;
+}
+
+static int dbign_sign_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *a, const void *b,
+			      uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, const void *c, const void *d)
+{
+	if (bign_args_ok(fn, ctx, cv, ECAMD_SIG_DBIGN, hash_type, n, a, b, b, c, d, stride, oid, oid_len)) {
+		return -1;
+	}
+	return dbign_common_ok(fn, ctx, cv, oid, oid_len, t, t_len);
+}
+
+extern "C" int ec_dbign_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs, const void *d_inputs,
+				       uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, void *d_sigs,
+				       void *d_status, void *hip_stream)
+{
+	if (dbign_sign_args_ok("ec_dbign_sign_batch_dev", ctx, cv, hash_type, n, d_privs, d_inputs, stride, oid, oid_len, t, t_len, d_sigs, d_status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return dbign_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_inputs, stride, oid, oid_len, t, t_len,
+					     (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_dbign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *inputs,
+				   uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *sigs,
+				   uint8_t *status)
+{
+	if (dbign_sign_args_ok("ec_dbign_sign_batch", ctx, cv, hash_type, n, privs, inputs, stride, oid, oid_len, t, t_len, sigs, status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {inputs, nullptr, stride}, {nullptr, sigs, (size_t)ecbign::sig_len(cv->qlen)},
+					   {nullptr, status, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return dbign_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], stride, oid, oid_len, t, t_len, op[2], op[3], s);
+	});
+}
+
+// the two tag hashes of the call's hash, as its words
+template <int ALG, typename KT> static void bip0340_tags_of(EcamdBip0340NonceArgs &N, KT Kt)
+{
+	typename ecrfc::Alg<ALG>::W w[8];
+	ecbip::tag_hash<ALG>("BIP0340/aux", 11, w, Kt);
+	for (int t = 0; t < 8; t++) {
+		N.tag_aux[t] = (uint64_t)w[t];
+	}
+	ecbip::tag_hash<ALG>("BIP0340/nonce", 13, w, Kt);
+	for (int t = 0; t < 8; t++) {
+		N.tag_nonce[t] = (uint64_t)w[t];
+	}
+}
+
+static void bip0340_nonce_args(EcamdBip0340NonceArgs &N, const ecamd_curve *cv, int hash_type, uint32_t stride)
+{
+	memset(&N, 0, sizeof(N));
+	N.qlen = (uint32_t)cv->qlen;
+	N.qbits = (uint32_t)cv->qbits;
+	N.clen = (uint32_t)cv->clen;
+	N.stride = stride;
+	for (int w = 0; w < 17; w++) {
+		N.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
+	}
+	switch (hash_type) {
+	case 1: bip0340_tags_of<224>(N, h_sha256_k); break;
+	case 2: bip0340_tags_of<256>(N, h_sha256_k); break;
+	case 3: bip0340_tags_of<384>(N, h_sha512_k); break;
+	default: bip0340_tags_of<512>(N, h_sha512_k); break;
+	}
+}
+
+// Y of one chunk: [x]G into SG_Y, or the caller's keys with their on-curve test; either way SG_STY holds the status.  *keys: where Y lies.
+static int bip0340_keys_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, const uint8_t *d_privs, const uint8_t *d_pubs, const uint8_t **keys,
+			    hipStream_t s)
+{
+	uint8_t **S = ctx->stage;
+	if (d_pubs) {
+		EcamdPtfArgs T;
+		memset(&T, 0, sizeof(T));
+		T.p1 = d_pubs;
+		T.p2 = d_pubs;
+		T.out = S[SG_Y];   // untouched by op 2
+		T.status = S[SG_STY];
+		T.n = m;
+		T.clen = (uint32_t)cv->clen;
+		T.op = 2;
+		T.slot = cv->slot;
+		HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
+		*keys = d_pubs;
+		return 0;
+	}
+	*keys = S[SG_Y];
+	return smul_dev_locked(ctx, cv, m, d_privs, (uint32_t)cv->qlen, nullptr, S[SG_Y], S[SG_STY], s);
+}
+
+// sign = false: the nonces go to d_out (n x qlen); true: into SG_NONCES, and the signatures (n x (clen + qlen)) to d_out
+static int bip0340_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_pubs,
+			      const uint8_t *d_aux, const uint8_t *d_in, uint32_t stride, uint8_t *d_out, uint8_t *d_status, bool sign, hipStream_t s)
+{
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen, siglen = cl + ql;
+	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	if (sign && schnorr_item_no_room(cv, ECAMD_SIG_BIP0340, hsize, stride)) {
+		HIPCHK(hipMemsetAsync(d_out, 0, n * siglen, s));
+		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
+		return 0;
+	}
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	if (stage_need(ctx, {{SG_Y, chunk * plen}, {SG_STY, chunk}}) ||
+	    (sign && stage_need(ctx, {{SG_NONCES, (size_t)chunk * ql}, {SG_KG, chunk * plen}, {SG_STKG, chunk}, {ST_FLAGS, chunk},
+				      {ST_SLOTS, (size_t)chunk * stride}, {ST_DIGESTS, (size_t)chunk * hsize}}))) {
+		return -1;
+	}
+	EcamdBip0340NonceArgs N;
+	bip0340_nonce_args(N, cv, hash_type, stride);
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		const uint8_t *in = d_in + (size_t)off * stride;
+		if (bip0340_keys_dev(ctx, cv, m, d_privs + off * ql, d_pubs ? d_pubs + off * plen : nullptr, &N.keys, s)) {
+			return -1;
+		}
+		N.n = m;
+		N.privs = d_privs + off * ql;
+		N.kst = ctx->stage[SG_STY];
+		N.aux = d_aux + off * ql;
+		N.slots = in;
+		N.nonces = sign ? ctx->stage[SG_NONCES] : d_out + off * ql;
+		N.status = d_status + off;   // signing: replaced by the core's, where a zero nonce is status 1
+		HIPCHK(ecamd_launch_bip0340_nonce(hash_type, N, s));
+		// the core takes Y as a supplied key ([x]G is computed once): derived here, it fails the core's on-curve test only as the point at infinity
+		if (sign && schnorr_item_sign_dev_locked(ctx, cv, ECAMD_SIG_BIP0340, hash_type, m, N.privs, N.keys, N.nonces, in, stride,
+							 d_out + (size_t)off * siglen, d_status + off, s)) {
+			return -1;
+		}
+	}
+	return 0;
+}
+
+static int bip0340_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *privs, const void *aux,
+			   const void *slots, const void *out, const void *status, uint32_t stride)
+{
+	if (schnorr_item_args_ok(fn, ctx, cv, ECAMD_SIG_BIP0340, hash_type, n, privs, aux, slots, out, status, stride)) {
+		return -1;
+	}
+	return det_order_ok(fn, cv);
+}
+
+extern "C" int ec_bip0340_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
+					  const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_nonces,
+					  void *d_status, void *hip_stream)
+{
+	if (bip0340_args_ok("ec_bip0340_nonce_batch_dev", ctx, cv, hash_type, n, d_privs, d_aux, d_hash_slots, d_nonces, d_status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return bip0340_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff, (const uint8_t *)d_aux,
+					  (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_nonces, (uint8_t *)d_status, false, s);
+	});
+}
+
+extern "C" int ec_bip0340_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
+					 const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+					 void *d_status, void *hip_stream)
+{
+	if (bip0340_args_ok("ec_bip0340_sign_batch_dev", ctx, cv, hash_type, n, d_privs, d_aux, d_hash_slots, d_sigs, d_status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return bip0340_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff, (const uint8_t *)d_aux,
+					  (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_sigs, (uint8_t *)d_status, true, s);
+	});
+}
+
+static int bip0340_host(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *pubkeys_aff,
+			const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *out, size_t outlen, uint8_t *status, bool sign)
+{
+	const size_t ql = (size_t)cv->qlen, plen = (size_t)2 * cv->clen;
+	std::vector<HostArr> arrs = {{privs, nullptr, ql}, {aux, nullptr, ql}, {hash_slots, nullptr, stride}, {nullptr, out, outlen}, {nullptr, status, 1}};
+	if (pubkeys_aff) {
+		arrs.push_back({pubkeys_aff, nullptr, plen});
+	}
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return bip0340_dev_locked(ctx, cv, hash_type, m, ip[0], pubkeys_aff ? ip[5] : nullptr, ip[1], ip[2], stride, op[3], op[4], sign, s);
+	});
+}
+
+extern "C" int ec_bip0340_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+				      const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *nonces,
+				      uint8_t *status)
+{
+	if (bip0340_args_ok("ec_bip0340_nonce_batch", ctx, cv, hash_type, n, privs, aux, hash_slots, nonces, status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return bip0340_host(ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, nonces, (size_t)cv->qlen, status, false);
+}
+
+extern "C" int ec_bip0340_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+				     const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+				     uint8_t *status)
+{
+	if (bip0340_args_ok("ec_bip0340_sign_batch", ctx, cv, hash_type, n, privs, aux, hash_slots, sigs, status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return bip0340_host(ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, sigs, (size_t)cv->clen + cv->qlen, status, true);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -695,6 +695,32 @@ struct EcamdRfc6979Args {
 	uint32_t q[17];          // the generator's order, little-endian words
 };
 hipError_t ecamd_launch_rfc6979_nonce(int hash_type, const EcamdRfc6979Args &a, hipStream_t s);
+// the nonce of deterministic BIGN (STB 34.101.45 section 6.3.3, ecamd_dbign_nonce.h / ecamd_detnonce.hip: k_dbign_nonce)
+struct EcamdDbignNonceArgs {
+	const uint8_t *privs;    // n x qlen big-endian
+	const uint8_t *digests;  // n x hlen: the digests of the messages
+	uint8_t *nonces;         // n x qlen big-endian (secret)
+	uint8_t *status;         // n: 0, or 1 with a zero nonce
+	uint32_t n, qlen, qbits, hlen, oid_len, t_len;
+	int scan;                // secret-scalar mode: the substitution table is scanned, not gathered from
+	uint32_t q[17];          // the generator's order, little-endian words
+	uint8_t oid[64], t[64];  // the OID of the message's hash and STB's optional additional data, the same for every item
+};
+hipError_t ecamd_launch_dbign_nonce(const EcamdDbignNonceArgs &a, hipStream_t s);
+// the nonce of BIP0340 signing (sig/bip0340.c:213-294, ecamd_bip0340_nonce.h / ecamd_detnonce.hip: k_bip0340_nonce<ALG>); hash_type 1 .. 4
+struct EcamdBip0340NonceArgs {
+	const uint8_t *privs;    // n x qlen big-endian
+	const uint8_t *keys;     // n x 2*clen: the public keys, affine
+	const uint8_t *kst;      // n: a non-zero byte fails the item (the key did not import, or [x]G is the point at infinity)
+	const uint8_t *aux;      // n x qlen big-endian
+	const uint8_t *slots;    // n x stride: BIP0340 signing slots (u32 length, the fixed fields, the message)
+	uint8_t *nonces;         // n x qlen big-endian (secret)
+	uint8_t *status;         // n: 0, or 1 with a zero nonce
+	uint32_t n, qlen, qbits, clen, stride;
+	uint32_t q[17];          // the generator's order, little-endian words
+	uint64_t tag_aux[8], tag_nonce[8];   // H("BIP0340/aux"), H("BIP0340/nonce") as the hash's words (a 32-bit word in the low half)
+};
+hipError_t ecamd_launch_bip0340_nonce(int hash_type, const EcamdBip0340NonceArgs &a, hipStream_t s);
 // the hashing front end of one-call EdDSA signing (ecamd_eddsa_sign.h / ecamd_eddsa_sign.hip); alg: libecc's ec_alg_type 9 .. 13,
 // klen = 32 / 57, hlen = 64 / 114.  Three steps share the structure:
 //   expand  (k_eddsa_expand_r)  sk, slots -> a, r_hash, a_wide (unless NULL), ph (PH variants), bad; slots == NULL: the key

@@ -6,7 +6,7 @@ torch.distributed.run, weak scaling, contiguous shards, one RCCL all-gather of t
 bytes per step); not the driver's headline bench.  --workload ecdsa_recover is the exception: one GPU, recovery beside the
 verification of the same signatures in alternating windows (recover_row).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..4 --curve C]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..4 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -672,6 +672,128 @@ def decdsa_row(a, ctx, dev, stream, rng, B):
     ctx.close()
 
 
+def det_sign_row(a, ctx, dev, stream, rng, B):
+    """DBIGN (--workload dbign_sign: ec_dbign_sign_batch_dev on 32-byte digests, bign256v1 unless --curve says otherwise) or BIP0340
+    (--workload bip0340_sign: ec_bip0340_sign_batch_dev on 32-byte messages with SHA-256, Y derived on the device) with the nonce
+    derived on the device, beside the supplied-nonce twin (ec_bign_sign_batch_dev / ec_schnorr_sign_batch_dev) on the same
+    device-resident items, in the same run, in alternating windows of a.steps calls; and the generator by itself
+    (ec_dbign_nonce_batch_dev / ec_bip0340_nonce_batch_dev; the latter includes Y = [x]G) between HIP events.  --secret: the context in
+    secret-scalar mode (DBIGN's generator scans its substitution table).  Gates: the nonces are the Python restatement's on
+    min(--ref-items, 256) random items, and all signatures equal those of the twin fed with the derived nonces.  One GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload %s measures one GPU: run it with --gpus 1, outside torch.distributed.run" % a.workload)
+    import oracles as O
+    import bign_ref as BR
+    import schnorr_ref as SR
+    import det_sign_ref as D
+    dbign = a.workload == "dbign_sign"
+    curve = a.curve if a.curve != "SECP256R1" else ("BIGN256V1" if dbign else "SECP256K1")
+    cv = ctx.curve(curve)
+    ctx.set_secret_scalars(bool(a.secret))
+    q, ql, cl = O.CURVES[curve]["q"], O.qlen(curve), O.clen(curve)
+    raw = rng.integers(0, 256, size=(B, ql + 8), dtype=np.uint8)
+    privs = b"".join(((int.from_bytes(raw[i].tobytes(), "big") % (q - 1)) + 1).to_bytes(ql, "big") for i in range(B))
+    oid, tdata = BR.OID_BELT, D.T_SAMPLE
+
+    def t(b):
+        return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+    sp = stream.cuda_stream
+    d_x = t(privs)
+    d_k = torch.empty(B * ql, dtype=torch.uint8, device=dev)
+    d_st, d_st2 = (torch.empty(B, dtype=torch.uint8, device=dev) for _ in range(2))
+    if dbign:
+        hl, sl = 32, BR.sig_len(curve)
+        inp = rng.integers(0, 256, size=B * hl, dtype=np.uint8).tobytes()
+        d_in = t(inp)
+
+        def nonces():
+            cv.dbign_nonce_dev(B, d_x.data_ptr(), d_in.data_ptr(), hl, oid, tdata, d_k.data_ptr(), d_st.data_ptr(), sp)
+
+        def derived():
+            cv.dbign_sign_dev(0, B, d_x.data_ptr(), d_in.data_ptr(), hl, oid, tdata, d_sig.data_ptr(), d_st.data_ptr(), sp)
+
+        def supplied():
+            cv.bign_sign_dev(BR.DBIGN, 0, B, d_x.data_ptr(), d_k.data_ptr(), d_in.data_ptr(), hl, oid, d_sig2.data_ptr(), d_st2.data_ptr(), sp)
+
+        def restated(i):
+            return D.dbign_nonce_from_digest(curve, privs[ql * i:ql * (i + 1)], inp[hl * i:hl * (i + 1)], oid, tdata)[1]
+    else:
+        hname, ht, ml, sl = "SHA256", 2, 32, cl + ql
+        stride = D.bip_stride(curve, hname, ml)
+        slots = np.zeros((B, stride), dtype=np.uint8)
+        head = np.frombuffer(D.bip_slot(curve, hname, bytes(ml), stride), dtype=np.uint8)
+        slots[:] = head
+        msgs = rng.integers(0, 256, size=(B, ml), dtype=np.uint8)
+        off = 4 + 2 * 32 + 2 * cl
+        slots[:, off:off + ml] = msgs
+        aux = rng.integers(0, 256, size=B * ql, dtype=np.uint8).tobytes()
+        d_in, d_aux = t(slots.tobytes()), t(aux)
+
+        def nonces():
+            cv.bip0340_nonce_dev(ht, B, d_x.data_ptr(), None, d_aux.data_ptr(), d_in.data_ptr(), stride, d_k.data_ptr(), d_st.data_ptr(), sp)
+
+        def derived():
+            cv.bip0340_sign_dev(ht, B, d_x.data_ptr(), None, d_aux.data_ptr(), d_in.data_ptr(), stride, d_sig.data_ptr(), d_st.data_ptr(), sp)
+
+        def supplied():
+            cv.schnorr_sign_dev(SR.BIP0340, ht, B, d_x.data_ptr(), None, d_k.data_ptr(), d_in.data_ptr(), stride, d_sig2.data_ptr(), d_st2.data_ptr(), sp)
+
+        def restated(i):
+            return D.bip_nonce(curve, hname, int.from_bytes(privs[ql * i:ql * (i + 1)], "big"), int.from_bytes(aux[ql * i:ql * (i + 1)], "big"),
+                               msgs[i].tobytes())[1]
+    d_sig, d_sig2 = (torch.empty(B * sl, dtype=torch.uint8, device=dev) for _ in range(2))
+    # ---- gates ----
+    nonces()
+    torch.cuda.synchronize()
+    ks = bytes(d_k.cpu().numpy())
+    if bytes(d_st.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: a nonce was not derived")
+    idx = [int(i) for i in np.sort(np.random.default_rng(2).choice(B, size=min(B, 256, max(1, a.ref_items)), replace=False))]
+    for i in idx:
+        if restated(i).to_bytes(ql, "big") != ks[ql * i:ql * (i + 1)]:
+            raise SystemExit("PARITY FAILURE: item %d's nonce is not the restatement's" % i)
+    derived()
+    supplied()
+    torch.cuda.synchronize()
+    if bytes(d_sig.cpu().numpy()) != bytes(d_sig2.cpu().numpy()) or bytes(d_st.cpu().numpy()) != bytes(B) or bytes(d_st2.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: the one-call form does not sign what the supplied-nonce call signs with its nonces")
+    gate = "%d nonces as the Python restatement derives them; all 2^%d signatures equal those of the supplied-nonce call" % (len(idx), a.batch_log2)
+    # ---- timing: alternating windows; the generator between events ----
+    for _ in range(a.warmup):
+        supplied()
+        derived()
+        nonces()
+    torch.cuda.synchronize()
+    ts, td, tn = [], [], []
+    for _ in range(3):
+        for fn, acc in ((supplied, ts), (derived, td)):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            acc.append((time.perf_counter() - t0) / a.steps)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(a.steps):
+            nonces()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        tn.append(e0.elapsed_time(e1) / 1e3 / a.steps)
+    ms, md, mn = float(np.median(ts)), float(np.median(td)), float(np.median(tn))
+    what = "DBIGN signatures/sec (%s, 32-byte digests supplied" % curve.lower() if dbign else "BIP0340 signatures/sec (%s, SHA-256, 32-byte messages, Y derived" % curve.lower()
+    print(json.dumps({"metric": "%s, nonces derived on the device, %s mode, batch=2^%d, device-resident)"
+                                % (what, "secret-scalar" if a.secret else "default", a.batch_log2),
+                      "value": B / md, "unit": "signatures/s", "derived_ms": [1e3 * x for x in td],
+                      "supplied_nonces_same_run": {"value": B / ms, "unit": "signatures/s", "ms": [1e3 * x for x in ts]},
+                      "derived_over_supplied": ms / md,
+                      "nonce_call": {"ms": [1e3 * x for x in tn], "ns_per_item": 1e9 * mn / B, "items_per_s": B / mn},
+                      "gate": gate,
+                      "config": {"workload": a.workload, "curve": curve, "secret": bool(a.secret), "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+    ctx.set_secret_scalars(False)
+    cv.free()
+    ctx.close()
+
+
 def eddsa_sign_row(a, ctx, dev, stream, rng, B):
     """One-call EdDSA signing (ec_eddsa_sign_msg_batch_dev: key expansion, PH(M), r_hash and hram hashed on the device) on 32-byte
     messages, device-resident, with the public keys supplied or (--derive-pub) derived on the device; beside it, in the same run and in
@@ -773,13 +895,14 @@ def eddsa_sign_row(a, ctx, dev, stream, rng, B):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
     ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa",
                                                     "ed25519", "ed25519ctx", "ed25519ph", "ed448", "ed448ph"],
                     help="eddsa_sign: ed25519, ed25519ctx, ed25519ph, ed448, ed448ph; sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
     ap.add_argument("--hash", type=int, default=None, choices=[0, 1, 2, 3, 4, 16],
                     help="bign_verify / bign_sign: 0 the caller hashed (SHA-256 digests supplied), 16 (default) belt-hash of message slots on the device; "
                          "decdsa_sign: 1 .. 4, SHA-224 / 256 (default) / 384 / 512")
+    ap.add_argument("--secret", action="store_true", help="dbign_sign / bip0340_sign: the context in secret-scalar mode")
     ap.add_argument("--derive-pub", action="store_true", help="eddsa_sign: pubkeys = NULL, A = encode([a]B) derived on the device (a second comb multiplication per item)")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
@@ -844,6 +967,8 @@ def main():
         return bign_row(a, ctx, dev, stream, rng, B)
     if a.workload == "decdsa_sign":
         return decdsa_row(a, ctx, dev, stream, rng, B)
+    if a.workload in ("dbign_sign", "bip0340_sign"):
+        return det_sign_row(a, ctx, dev, stream, rng, B)
     if a.workload == "eddsa_sign":
         if not a.alg.startswith("ed"):
             raise SystemExit("--workload eddsa_sign: --alg ed25519 | ed25519ctx | ed25519ph | ed448 | ed448ph")
