@@ -296,6 +296,47 @@ int ec_sig_verify_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint3
 int ec_sig_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const uint8_t *privs,
 		      const uint8_t *nonces, const uint8_t *digests, uint32_t digest_len, uint8_t *sigs, uint8_t *status);
 /*
+ * The same three schemes from MESSAGES: the hashes they are deployed with run on the device, SM2's Z too, in front of the
+ * digest-level cores above, for the reason given at ec_ecdsa_verify_msg_batch_fmt (a portable-C Streebog or SM3 on the host costs
+ * more per item than everything else).  Verdicts, signature bytes and status are those of ec_sig_verify_batch / ec_sig_sign_batch
+ * fed with libecc's digests.
+ *   hash_type  libecc's hash_alg_type numbers: 1 .. 4 (SHA-224 / 256 / 384 / 512), 11 (SM3), 13, 14 (Streebog-256 / -512; octet
+ *              order of message and digest as libecc's hash/streebog.c).  SM2's Z is computed with SM3 or SHA-2: SM2 with 13 or 14,
+ *              and any other alg or hash_type, is a call-level error (-1, ecamd_last_error()).
+ *   msg_slots  the slots of ec_ecdsa_verify_msg_batch_fmt: a little-endian u32 length, then the bytes; stride a multiple of 4 in
+ *              4 .. 4096.  For SM2 the hash input is <blank> || m: the caller leaves hsize octets empty in front of the message and
+ *              counts them in the length, as for ECSDSA; the device writes Z into a staged copy.  The caller's array is never
+ *              modified.  A slot that does not fit its stride (4 + length > stride), or for SM2 is shorter than the blank, is
+ *              result / status 1 (signing: with zero signature bytes).
+ *   id, id_len SM2 only (ignored otherwise): the signer's ID of Z, ONE HOST pointer per call, in the _dev forms too (as DBIGN's t);
+ *              0 .. 1024 octets (libecc: SM2_MAX_ID_LEN 8191).  id == NULL with id_len > 0, or a longer id, is a call-level error.
+ *              Z takes xY || yY as the octets of the affine key; ENTL || ID || a || b || xG || yG is absorbed once per call on the
+ *              host and the kernel starts from its midstate.
+ *   pubkeys_aff of signing: SM2 only (ignored otherwise), for Z: n x 2 clen, or NULL -- then Y = [x]G is computed on the device with the
+ *              fixed-base multiplication, which honours ecamd_ctx_set_secret_scalars.  An SM2 item whose key does not import (off the
+ *              curve, a coordinate >= p, Y at infinity) or whose x the digest-level rules refuse is status 1 with zero bytes.
+ * ec_hash_slots_batch is the bare hash: n x hsize digests of the slots (for 11, 13, 14 a slot that does not fit its stride gets
+ * an all-zero digest; 1 .. 4 run the kernel of ec_ecdsa_verify_msg_batch_fmt, which hashes what fits).
+ * Key rules, n = 0, NULL arguments, foreign handles, chunking by ecamd_ctx_set_max_chunk as ec_decdsa_sign_batch; ecamd_ctx_wipe_scratch
+ * covers the staged slots.  Not here: SHA-3, SHA-512/t, RIPEMD-160 and BASH on the device, the ecamd_multi_* wrappers, the
+ * libecc-typed boundary (libsign_amd), and ECKCDSA's z prefix.
+ */
+int ec_sig_verify_msg_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys_aff,
+			    const uint8_t *sigs, const uint8_t *msg_slots, uint32_t stride, const uint8_t *id, uint32_t id_len,
+			    uint8_t *result);
+int ec_sig_verify_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_pubkeys_aff,
+				const void *d_sigs, const void *d_msg_slots, uint32_t stride, const uint8_t *id, uint32_t id_len,
+				void *d_result, void *hip_stream);
+int ec_sig_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+			  const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *msg_slots, uint32_t stride, const uint8_t *id,
+			  uint32_t id_len, uint8_t *sigs, uint8_t *status);
+int ec_sig_sign_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_privs,
+			      const void *d_pubkeys_aff, const void *d_nonces, const void *d_msg_slots, uint32_t stride, const uint8_t *id,
+			      uint32_t id_len, void *d_sigs, void *d_status, void *hip_stream);
+int ec_hash_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *msg_slots, uint32_t stride, uint8_t *digests);
+int ec_hash_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_msg_slots, uint32_t stride, void *d_digests,
+			    void *hip_stream);
+/*
  * ECSDSA, ECOSDSA and ECKCDSA: the schemes of libecc's table that hash AFTER the multiplication.  The verifier computes
  * W' = [u]G + [v]Y, hashes its affine coordinates on the device and compares the digest with the signature's r byte for byte; the
  * signer hashes W = [k]G and derives e = digest mod q.  alg: libecc's ec_alg_type numbers; hash_type: libecc's hash_alg_type

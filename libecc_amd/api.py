@@ -30,6 +30,8 @@ EXPORTED_SYMBOLS = [
     "ec_schnorr_verify_all_batch", "ec_schnorr_verify_all_batch_dev", "ec_schnorr_verify_msg_all_batch", "ec_eddsa_verify_msg_prj_all_batch", "ecamd_multi_eddsa_verify_msg_prj_all_batch", "ecamd_multi_schnorr_verify_msg_all_batch", "ec_schnorr_verify_all_available", "ecamd_multi_schnorr_verify_all_batch", "ecamd_debug_schnorr_msm", "ecamd_debug_schnorr_msm_words",
     "ec_ecdsa_recover_batch", "ec_ecdsa_recover_batch_dev",
     "ec_sig_verify_batch", "ec_sig_verify_batch_dev", "ec_sig_sign_batch", "ec_sig_sign_batch_dev",
+    "ec_sig_verify_msg_batch", "ec_sig_verify_msg_batch_dev", "ec_sig_sign_msg_batch", "ec_sig_sign_msg_batch_dev",
+    "ec_hash_slots_batch", "ec_hash_slots_batch_dev",
     "ec_sig_hashed_verify_batch", "ec_sig_hashed_verify_batch_dev", "ec_sig_hashed_sign_batch", "ec_sig_hashed_sign_batch_dev",
     "ec_schnorr_verify_batch", "ec_schnorr_verify_batch_dev", "ec_schnorr_sign_batch", "ec_schnorr_sign_batch_dev",
     "ec_bign_verify_batch", "ec_bign_verify_batch_dev", "ec_bign_sign_batch", "ec_bign_sign_batch_dev",
@@ -53,6 +55,8 @@ SIG_ECFSDSA, SIG_BIP0340 = 5, 20
 SIG_BIGN, SIG_DBIGN = 18, 19
 HASH_BELT = 16
 HASH_SIZES = {1: 28, 2: 32, 3: 48, 4: 64}          # libecc's hash_alg_type numbers of SHA-224 / 256 / 384 / 512
+HASH_SM3, HASH_STREEBOG256, HASH_STREEBOG512 = 11, 13, 14
+HASH_SLOT_SIZES = {**HASH_SIZES, 11: 32, 13: 32, 14: 64}   # what ec_hash_slots_batch and the message-level ec_sig_* calls hash with
 
 
 class EcamdError(RuntimeError):
@@ -132,6 +136,12 @@ def load_library():
         L.ec_sig_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u8p]
         L.ec_sig_verify_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, u32, vp, vp]
         L.ec_sig_sign_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, u32, vp, vp, vp]
+        L.ec_sig_verify_msg_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u32, u8p]
+        L.ec_sig_verify_msg_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, u8p, u32, vp, vp]
+        L.ec_sig_sign_msg_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u8p, u32, u8p, u32, u8p, u8p]
+        L.ec_sig_sign_msg_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, vp, u32, u8p, u32, vp, vp, vp]
+        L.ec_hash_slots_batch.argtypes = [vp, C.c_int, u32, u8p, u32, u8p]
+        L.ec_hash_slots_batch_dev.argtypes = [vp, C.c_int, u32, vp, u32, vp, vp]
         L.ec_sig_hashed_verify_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p]
         L.ec_sig_hashed_sign_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u8p]
         L.ec_sig_hashed_verify_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, vp, vp]
@@ -222,6 +232,17 @@ class Context:
 
     def set_max_chunk(self, n):
         _chk(self.L, self.L.ecamd_ctx_set_max_chunk(self.h, n), "ecamd_ctx_set_max_chunk")
+
+    def hash_slots(self, hash_type, slots, stride):
+        """the bare device hash of message slots (1 .. 4 SHA-2, 11 SM3, 13 / 14 Streebog-256 / -512): n x digest size bytes"""
+        n = len(slots) // stride
+        hl = HASH_SLOT_SIZES.get(hash_type, 0)
+        out = C.create_string_buffer(max(1, n * hl))
+        _chk(self.L, self.L.ec_hash_slots_batch(self.h, hash_type, n, slots, stride, out), "ec_hash_slots_batch")
+        return out.raw[:n * hl]
+
+    def hash_slots_dev(self, hash_type, n, d_slots, stride, d_digests, stream=None):
+        _chk(self.L, self.L.ec_hash_slots_batch_dev(self.h, hash_type, n, d_slots, stride, d_digests, stream), "ec_hash_slots_batch_dev")
 
     def set_secret_scalars(self, on=True):
         _chk(self.L, self.L.ecamd_ctx_set_secret_scalars(self.h, 1 if on else 0), "ecamd_ctx_set_secret_scalars")
@@ -430,6 +451,24 @@ class Curve:
         sigs = C.create_string_buffer(max(1, 2 * self.qlen * n))
         st = C.create_string_buffer(max(1, n))
         _chk(self.L, self.L.ec_sig_sign_batch(self.ctx.h, self.h, alg, n, privs, nonces, digests, hlen, sigs, st), "ec_sig_sign_batch")
+        return sigs.raw[:2 * self.qlen * n], st.raw[:n]
+
+    def sig_verify_msg(self, alg, hash_type, pubs, sigs, slots, stride, ident=None):
+        """ECGDSA / ECRDSA / SM2 verification from message slots, hashed on the device (hash_type 1 .. 4, 11 SM3, 13 / 14 Streebog);
+        SM2: `ident` is the signer's id of Z and every slot starts with a blank of the digest size"""
+        n = len(pubs) // (2 * self.clen)
+        res = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_sig_verify_msg_batch(self.ctx.h, self.h, alg, hash_type, n, pubs, sigs, slots, stride, ident,
+                                                    len(ident) if ident else 0, res), "ec_sig_verify_msg_batch")
+        return res.raw[:n]
+
+    def sig_sign_msg(self, alg, hash_type, privs, nonces, slots, stride, ident=None, pubs=None):
+        """ECGDSA / ECRDSA / SM2 signatures from message slots; SM2: pubs (for Z) may be None, then Y = [x]G on the device"""
+        n = len(privs) // self.qlen
+        sigs = C.create_string_buffer(max(1, 2 * self.qlen * n))
+        st = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_sig_sign_msg_batch(self.ctx.h, self.h, alg, hash_type, n, privs, pubs, nonces, slots, stride, ident,
+                                                  len(ident) if ident else 0, sigs, st), "ec_sig_sign_msg_batch")
         return sigs.raw[:2 * self.qlen * n], st.raw[:n]
 
     def sig_hashed_rlen(self, alg, hash_type):
@@ -737,6 +776,14 @@ class Curve:
     def sig_verify_dev(self, alg, n, d_pubs, d_sigs, d_digests, hlen, d_result, stream=None):
         _chk(self.L, self.L.ec_sig_verify_batch_dev(self.ctx.h, self.h, alg, n, d_pubs, d_sigs, d_digests, hlen, d_result, stream),
              "ec_sig_verify_batch_dev")
+
+    def sig_verify_msg_dev(self, alg, hash_type, n, d_pubs, d_sigs, d_slots, stride, ident, d_result, stream=None):
+        _chk(self.L, self.L.ec_sig_verify_msg_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_pubs, d_sigs, d_slots, stride, ident,
+                                                        len(ident) if ident else 0, d_result, stream), "ec_sig_verify_msg_batch_dev")
+
+    def sig_sign_msg_dev(self, alg, hash_type, n, d_privs, d_pubs, d_nonces, d_slots, stride, ident, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_sig_sign_msg_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_privs, d_pubs, d_nonces, d_slots, stride, ident,
+                                                      len(ident) if ident else 0, d_sigs, d_status, stream), "ec_sig_sign_msg_batch_dev")
 
     def sig_sign_dev(self, alg, n, d_privs, d_nonces, d_digests, hlen, d_sigs, d_status, stream=None):
         _chk(self.L, self.L.ec_sig_sign_batch_dev(self.ctx.h, self.h, alg, n, d_privs, d_nonces, d_digests, hlen, d_sigs, d_status,

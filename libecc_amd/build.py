@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libecc_amd.so")
-SOURCES = ["ecamd_kernels.hip", "ecamd_p256_kernel.hip", "ecamd_hash.hip", "ecamd_rfc6979.hip", "ecamd_detnonce.hip", "ecamd_eddsa_sign.hip", "ecamd_host.cpp", "ecamd_multi.cpp"]
+SOURCES = ["ecamd_kernels.hip", "ecamd_p256_kernel.hip", "ecamd_hash.hip", "ecamd_hash2.hip", "ecamd_rfc6979.hip", "ecamd_detnonce.hip", "ecamd_eddsa_sign.hip", "ecamd_host.cpp", "ecamd_multi.cpp"]
 DEPS = ["ecamd_madchain.h", "ecamd_field.h", "ecamd_point.h", "ecamd_u29.h", "ecamd_p256.h", "ecamd_u29g.h", "ecamd_jacg.h",
         "ecamd_internal.h", "ecamd_lattice.h", "ecamd_randmod.h", "ecamd_recover.h", "ecamd_recover_kernels.h",
         "ecamd_sigfam.h", "ecamd_sigfam_kernels.h", "ecamd_sighash.h", "ecamd_sighash_kernels.h",
@@ -19,7 +19,8 @@ DEPS = ["ecamd_madchain.h", "ecamd_field.h", "ecamd_point.h", "ecamd_u29.h", "ec
 # headers that only some translation units include
 SOURCE_DEPS = {"ecamd_kernels.hip": ["ecamd_schnorr.h", "ecamd_schnorr_kernels.h", "ecamd_bign.h", "ecamd_bign_kernels.h"],
                "ecamd_host.cpp": ["ecamd_schnorr.h", "ecamd_bign.h", "ecamd_rfc6979.h", "ecamd_eddsa_sign.h", "ecamd_belt.h", "ecamd_dbign_nonce.h",
-                                  "ecamd_bip0340_nonce.h"], "ecamd_hash.hip": ["ecamd_belt.h"],
+                                  "ecamd_bip0340_nonce.h", "ecamd_sm3.h", "ecamd_sm2z.h"], "ecamd_hash.hip": ["ecamd_belt.h"],
+               "ecamd_hash2.hip": ["ecamd_sm3.h", "ecamd_streebog.h", "ecamd_sm2z.h", "ecamd_rfc6979.h"],
                "ecamd_rfc6979.hip": ["ecamd_rfc6979.h"],
                "ecamd_detnonce.hip": ["ecamd_rfc6979.h", "ecamd_belt.h", "ecamd_dbign_nonce.h", "ecamd_bip0340_nonce.h"],
                "ecamd_eddsa_sign.hip": ["ecamd_rfc6979.h", "ecamd_eddsa_sign.h"]}

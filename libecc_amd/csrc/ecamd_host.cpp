@@ -27,6 +27,7 @@
 #include "ecamd_rfc6979.h"
 #include "ecamd_dbign_nonce.h"
 #include "ecamd_bip0340_nonce.h"
+#include "ecamd_sm2z.h"
 #include "ecamd_eddsa_sign.h"
 
 // ------------------------------------------------------------------------------------------
@@ -248,6 +249,7 @@ static const CurveRow g_curve_rows[] = {
 //   EB_  EdDSA batch-wide     24..27        eddsa_verify_msg_prj_impl, the same way                EP_, EV_, ST_DIGESTS
 //        sig_target           29            ST_TARGET: the comparison target of ECGDSA / ECRDSA / SM2, beside ST_ and VP_
 //   ES_  one-call EdDSA sign  30..40        eddsa_sign_msg_dev_locked, eddsa_pub_key_dev_locked    SR_
+//   SM_  sig from messages    41, 42        sig_msg_verify_ / sig_msg_sign_dev_locked, which outlive the digest-level core they call   ST_, VP_, SG_, ST_SLOTS, ST_DIGESTS, ST_TARGET
 //
 // smul_dev_locked itself takes no slot (ctx->tbl, ctx->tbl_fast); host_pipeline stages in ctx->hbuf.
 // ------------------------------------------------------------------------------------------
@@ -281,9 +283,10 @@ enum StageSlot {
 	EB_KEYS = 24, EB_SIGS = 25, EB_HRAM = 26, EB_MARKS = 27,
 	ST_TARGET = 29,
 	ES_A = 30, ES_RHASH = 31, ES_AWIDE = 32, ES_HRAM = 33, ES_R = 34, ES_S = 35, ES_BAD = 36, ES_STR = 37, ES_STA = 38, ES_AENC = 39, ES_PH = 40,
+	SM_BAD = 41, SM_Z = 42,   // the items a message-level ECGDSA / ECRDSA / SM2 call rejects itself; SM2's Z
 	ECAMD_NSTAGE
 };
-static_assert(ECAMD_NSTAGE == ES_PH + 1, "ECAMD_NSTAGE counts the slots: the last frame ends the array");
+static_assert(ECAMD_NSTAGE == SM_Z + 1, "ECAMD_NSTAGE counts the slots: the last frame ends the array");
 
 struct ecamd_ctx {
 	int device;
@@ -7892,6 +7895,303 @@ extern "C" int ec_bip0340_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int 
 		return 0;
 	}
 	return bip0340_host(ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, sigs, (size_t)cv->clen + cv->qlen, status, true);
+}
+
+// ------------------------------------------------------------------------------------------
+// ECGDSA / ECRDSA / SM2 from messages (include/libecc_amd.h: ec_sig_verify_msg_batch, ec_sig_sign_msg_batch, ec_hash_slots_batch): the
+// hashes of ecamd_hash.hip / ecamd_hash2.hip in front of the digest-level cores ecdsa_verify_dev_locked(.., alg) / sig_sign_dev_locked,
+// which run unchanged.  Per chunk of at most max_chunk items:
+//   (signing, SM2)     Y: the caller's keys through the on-curve test, or [x]G (bip0340_keys_dev: SG_Y, SG_STY)
+//   k_sig_msg_bad      SM_BAD: the slot does not fit its stride, is shorter than SM2's blank, or the key did not import
+//   (SM2) k_sm2_z      Z from the prefix midstate into SM_Z; a copy of the slots in ST_SLOTS; k_slot_patch puts Z into the blank
+//   k_*_slots          the digests into ST_DIGESTS
+//   the core           verdicts / signatures and status as for the digest-level call
+//   k_reject_where / k_sig_msg_reject_sign   SM_BAD's items: result 1 / status 1 with zero bytes
+// Frames: SM_ with ST_SLOTS and ST_DIGESTS around the core's own (ST_ / VP_ / SG_).  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static int sig_msg_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t stride, const uint8_t *id,
+			   uint32_t id_len)
+{
+	if (sig_alg_ok(fn, alg)) {
+		return -1;
+	}
+	if (ecamd_hash_digest_len(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224 / 256 / 384 / 512), 11 (SM3), 13 or 14 (Streebog-256 / -512)");
+	}
+	if (stride < 4 || (stride & 3u) || stride > 4096) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	if (!ctx || !cv || cv->ctx != ctx) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	if (alg == ECAMD_SIG_SM2) {
+		if (ecsm2z::hash_size(hash_type) == 0) {
+			return fail(std::string(fn) + ": SM2's Z is computed with SM3 or SHA-2 (hash_type 11 or 1 .. 4)");
+		}
+		if (id_len > (uint32_t)ecsm2z::MAX_ID) {
+			return fail(std::string(fn) + ": id_len must be at most 1024");
+		}
+		if (id_len && !id) {
+			return fail(std::string(fn) + ": id is NULL with a positive id_len");
+		}
+		if (cv->clen > ecsm2z::MAX_CLEN) {
+			return fail(std::string(fn) + ": field not supported");
+		}
+	}
+	return 0;
+}
+
+// the prefix of the call's Z (SM2 only; otherwise left alone)
+static int sig_msg_prefix(const ecamd_curve *cv, int alg, int hash_type, const uint8_t *id, uint32_t id_len, ecsm2z::Prefix &P)
+{
+	if (alg != ECAMD_SIG_SM2) {
+		return 0;
+	}
+	uint8_t a[ecsm2z::MAX_CLEN], b[ecsm2z::MAX_CLEN], gx[ecsm2z::MAX_CLEN], gy[ecsm2z::MAX_CLEN];
+	big_to_be(a, cv->clen, cv->a);
+	big_to_be(b, cv->clen, cv->b);
+	big_to_be(gx, cv->clen, cv->gx);
+	big_to_be(gy, cv->clen, cv->gy);
+	if (ecsm2z::prefix_init(P, hash_type, id, id_len, a, b, gx, gy, (uint32_t)cv->clen, h_sha256_k, h_sha512_k)) {
+		return fail("internal: Z prefix");
+	}
+	return 0;
+}
+
+// SM2: Z of the chunk's keys into the blank of a staged copy of its slots; *hin: the slots to hash
+static int sig_msg_stage_z(ecamd_ctx *ctx, const ecsm2z::Prefix &P, uint32_t m, const uint8_t *d_keys, uint32_t plen, const uint8_t *d_in,
+			   uint32_t stride, uint32_t hl, const uint8_t **hin, hipStream_t s)
+{
+	uint8_t **S = ctx->stage;
+	HIPCHK(ecamd_launch_sm2_z(P, d_keys, plen, S[SM_Z], hl, m, s));
+	HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in, (size_t)m * stride, hipMemcpyDeviceToDevice, s));   // the caller's array is not modified
+	HIPCHK(ecamd_launch_slot_patch(S[ST_SLOTS], stride, 0, S[SM_Z], hl, S[SM_BAD], m, s));
+	*hin = S[ST_SLOTS];
+	return 0;
+}
+
+static int sig_msg_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_pub,
+				     const uint8_t *d_sig, const uint8_t *d_in, uint32_t stride, const ecsm2z::Prefix &P, uint8_t *d_res, hipStream_t s,
+				     const Between *between = nullptr)
+{
+	const size_t plen = (size_t)2 * cv->clen, sl = (size_t)2 * cv->qlen;
+	const uint32_t hl = (uint32_t)ecamd_hash_digest_len(hash_type), blank = alg == ECAMD_SIG_SM2 ? hl : 0u;
+	const bool sm2 = alg == ECAMD_SIG_SM2;
+	if (stride < 4u + blank) {   // no slot can hold the blank: every item is rejected
+		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
+		return 0;
+	}
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	if (stage_need(ctx, {{ST_DIGESTS, (size_t)chunk * hl}, {SM_BAD, chunk}, {ST_SLOTS, sm2 ? (size_t)chunk * stride : 0}, {SM_Z, sm2 ? (size_t)chunk * hl : 0}})) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		const uint8_t *pub = d_pub + (size_t)off * plen, *in = d_in + (size_t)off * stride, *hin = in;
+		HIPCHK(ecamd_launch_sig_msg_bad(in, stride, blank, nullptr, S[SM_BAD], m, s));
+		if (sm2 && sig_msg_stage_z(ctx, P, m, pub, (uint32_t)plen, in, stride, hl, &hin, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_hash_slots(hash_type, hin, stride, m, S[ST_DIGESTS], hl, s));
+		if (ecdsa_verify_dev_locked(ctx, cv, m, pub, d_sig + (size_t)off * sl, S[ST_DIGESTS], hl, d_res + off, s,
+					    off + m == n ? between : nullptr, alg)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_reject_where(d_res + off, S[SM_BAD], m, s));
+	}
+	return 0;
+}
+
+static int sig_msg_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_privs,
+				   const uint8_t *d_pubs, const uint8_t *d_nonces, const uint8_t *d_in, uint32_t stride, const ecsm2z::Prefix &P,
+				   uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
+{
+	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen, sl = 2 * ql;
+	const uint32_t hl = (uint32_t)ecamd_hash_digest_len(hash_type), blank = alg == ECAMD_SIG_SM2 ? hl : 0u;
+	const bool sm2 = alg == ECAMD_SIG_SM2;
+	if (stride < 4u + blank) {
+		HIPCHK(hipMemsetAsync(d_sigs, 0, n * sl, s));
+		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
+		return 0;
+	}
+	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	if (stage_need(ctx, {{ST_DIGESTS, (size_t)chunk * hl}, {SM_BAD, chunk}, {ST_SLOTS, sm2 ? (size_t)chunk * stride : 0}, {SM_Z, sm2 ? (size_t)chunk * hl : 0},
+			     {SG_Y, sm2 ? chunk * plen : 0}, {SG_STY, sm2 ? chunk : 0}})) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		const uint8_t *in = d_in + (size_t)off * stride, *hin = in, *keys = nullptr;
+		// SM2: Y for Z, supplied (with its on-curve test) or [x]G by the fixed-base multiplication in the context's secret-scalar mode
+		if (sm2 && bip0340_keys_dev(ctx, cv, m, d_privs + off * ql, d_pubs ? d_pubs + off * plen : nullptr, &keys, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_sig_msg_bad(in, stride, blank, sm2 ? S[SG_STY] : nullptr, S[SM_BAD], m, s));
+		if (sm2 && sig_msg_stage_z(ctx, P, m, keys, (uint32_t)plen, in, stride, hl, &hin, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_hash_slots(hash_type, hin, stride, m, S[ST_DIGESTS], hl, s));
+		if (sig_sign_dev_locked(ctx, cv, alg, m, d_privs + off * ql, d_nonces + off * ql, S[ST_DIGESTS], hl, d_sigs + off * sl, d_status + off, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_sig_msg_reject_sign(d_sigs + off * sl, (uint32_t)sl, d_status + off, S[SM_BAD], m, s));
+	}
+	return 0;
+}
+
+extern "C" int ec_sig_verify_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
+					   const void *d_sigs, const void *d_msg_slots, uint32_t stride, const uint8_t *id, uint32_t id_len,
+					   void *d_result, void *hip_stream)
+{
+	ecsm2z::Prefix P;
+	if (sig_msg_args_ok("ec_sig_verify_msg_batch_dev", ctx, cv, alg, hash_type, stride, id, id_len)) {
+		return -1;
+	}
+	if (n && (!d_pubkeys || !d_sigs || !d_msg_slots || !d_result)) {
+		return fail("ec_sig_verify_msg_batch_dev: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
+		return -1;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return sig_msg_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_msg_slots,
+						 stride, P, (uint8_t *)d_result, s);
+	});
+}
+
+extern "C" int ec_sig_verify_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
+				       const uint8_t *sigs, const uint8_t *msg_slots, uint32_t stride, const uint8_t *id, uint32_t id_len,
+				       uint8_t *result)
+{
+	ecsm2z::Prefix P;
+	if (sig_msg_args_ok("ec_sig_verify_msg_batch", ctx, cv, alg, hash_type, stride, id, id_len)) {
+		return -1;
+	}
+	if (n && (!pubkeys || !sigs || !msg_slots || !result)) {
+		return fail("ec_sig_verify_msg_batch: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
+		return -1;
+	}
+	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, (size_t)2 * cv->qlen}, {msg_slots, nullptr, stride},
+					   {nullptr, result, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &between) {
+		return sig_msg_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, P, op[3], s, &between);
+	});
+}
+
+extern "C" int ec_sig_sign_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+					 const void *d_pubkeys, const void *d_nonces, const void *d_msg_slots, uint32_t stride, const uint8_t *id,
+					 uint32_t id_len, void *d_sigs, void *d_status, void *hip_stream)
+{
+	ecsm2z::Prefix P;
+	if (sig_msg_args_ok("ec_sig_sign_msg_batch_dev", ctx, cv, alg, hash_type, stride, id, id_len)) {
+		return -1;
+	}
+	if (n && (!d_privs || !d_nonces || !d_msg_slots || !d_sigs || !d_status)) {
+		return fail("ec_sig_sign_msg_batch_dev: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
+		return -1;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return sig_msg_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, alg == ECAMD_SIG_SM2 ? (const uint8_t *)d_pubkeys : nullptr,
+					       (const uint8_t *)d_nonces, (const uint8_t *)d_msg_slots, stride, P, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_sig_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+				     const uint8_t *pubkeys, const uint8_t *nonces, const uint8_t *msg_slots, uint32_t stride, const uint8_t *id,
+				     uint32_t id_len, uint8_t *sigs, uint8_t *status)
+{
+	ecsm2z::Prefix P;
+	if (sig_msg_args_ok("ec_sig_sign_msg_batch", ctx, cv, alg, hash_type, stride, id, id_len)) {
+		return -1;
+	}
+	if (n && (!privs || !nonces || !msg_slots || !sigs || !status)) {
+		return fail("ec_sig_sign_msg_batch: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
+		return -1;
+	}
+	const size_t ql = (size_t)cv->qlen;
+	const bool with_keys = alg == ECAMD_SIG_SM2 && pubkeys;
+	std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {msg_slots, nullptr, stride}, {nullptr, sigs, 2 * ql}, {nullptr, status, 1}};
+	if (with_keys) {
+		arrs.push_back({pubkeys, nullptr, (size_t)2 * cv->clen});
+	}
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return sig_msg_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], with_keys ? ip[5] : nullptr, ip[1], ip[2], stride, P, op[3], op[4], s);
+	});
+}
+
+static int hash_slots_args_ok(const char *fn, ecamd_ctx *ctx, int hash_type, uint32_t n, const void *slots, uint32_t stride, const void *out)
+{
+	if (ecamd_hash_digest_len(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224 / 256 / 384 / 512), 11 (SM3), 13 or 14 (Streebog-256 / -512)");
+	}
+	if (stride < 4 || (stride & 3u) || stride > 4096) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	if (!ctx || (n && (!slots || !out))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	return 0;
+}
+
+static int hash_slots_dev_locked(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *d_slots, uint32_t stride, uint8_t *d_out, hipStream_t s)
+{
+	const uint32_t hl = (uint32_t)ecamd_hash_digest_len(hash_type), chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
+	for (uint32_t off = 0; off < n; off += chunk) {
+		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
+		HIPCHK(ecamd_launch_hash_slots(hash_type, d_slots + (size_t)off * stride, stride, m, d_out + (size_t)off * hl, hl, s));
+	}
+	return 0;
+}
+
+extern "C" int ec_hash_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_msg_slots, uint32_t stride, void *d_digests,
+				       void *hip_stream)
+{
+	if (hash_slots_args_ok("ec_hash_slots_batch_dev", ctx, hash_type, n, d_msg_slots, stride, d_digests)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return hash_slots_dev_locked(ctx, hash_type, n, (const uint8_t *)d_msg_slots, stride, (uint8_t *)d_digests, s);
+	});
+}
+
+extern "C" int ec_hash_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *msg_slots, uint32_t stride, uint8_t *digests)
+{
+	if (hash_slots_args_ok("ec_hash_slots_batch", ctx, hash_type, n, msg_slots, stride, digests)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const std::vector<HostArr> arrs = {{msg_slots, nullptr, stride}, {nullptr, digests, (size_t)ecamd_hash_digest_len(hash_type)}};
+	return host_call(ctx, 256, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return hash_slots_dev_locked(ctx, hash_type, m, ip[0], stride, op[1], s);
+	});
 }
 
 // ------------------------------------------------------------------------------------------

@@ -807,6 +807,20 @@ hipError_t ecamd_launch_shake256_slots(const uint8_t *slots, uint32_t stride, ui
 hipError_t ecamd_launch_sha2_slots(int hash_type, const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s);
 // belt-hash (STB 34.101.31) of the same slots: 32 digest bytes per item (ecamd_belt.h)
 hipError_t ecamd_launch_belt_slots(const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s);
+// SM3 and Streebog-256 / -512 of the same slots (ecamd_hash2.hip, ecamd_sm3.h, ecamd_streebog.h); here a slot whose length does not fit its
+// stride gets an all-zero digest.  hash_type: 13 or 14 for Streebog.
+hipError_t ecamd_launch_sm3_slots(const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s);
+hipError_t ecamd_launch_streebog_slots(int hash_type, const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s);
+// one door to the slot hashes: hash_type 1 .. 4 (SHA-2), 11 (SM3), 13, 14 (Streebog-256 / -512); the digest length is 0 for any other
+int ecamd_hash_digest_len(int hash_type);
+hipError_t ecamd_launch_hash_slots(int hash_type, const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s);
+// SM2's Z per item from the call's prefix (ecamd_sm2z.h) and the keys' 2 clen octets, hsize octets each into z
+namespace ecsm2z { struct Prefix; }
+hipError_t ecamd_launch_sm2_z(const ecsm2z::Prefix &P, const uint8_t *keys, uint32_t klen, uint8_t *z, uint32_t hsize, uint32_t n, hipStream_t s);
+// the message-level ECGDSA / ECRDSA / SM2 calls: bad[i] = 1 where the slot does not fit its stride, is shorter than `blank`, or kst[i] != 0
+// (kst may be NULL); and signing's "status 1 with zero bytes" for those items behind the digest-level core
+hipError_t ecamd_launch_sig_msg_bad(const uint8_t *slots, uint32_t stride, uint32_t blank, const uint8_t *kst, uint8_t *bad, uint32_t n, hipStream_t s);
+hipError_t ecamd_launch_sig_msg_reject_sign(uint8_t *sigs, uint32_t siglen, uint8_t *status, const uint8_t *bad, uint32_t n, hipStream_t s);
 struct EcamdPrjInArgs;
 // prj_pt_import_from_buf + prj_pt_unique on a radix-2^29 unit, one inversion per eight triples (k_prj_import_g)
 hipError_t ecamd_g29_prj_import(int pbits, int gslot, const EcamdPrjInArgs &a, hipStream_t s, int flavour);

@@ -6,7 +6,7 @@ torch.distributed.run, weak scaling, contiguous shards, one RCCL all-gather of t
 bytes per step); not the driver's headline bench.  --workload ecdsa_recover is the exception: one GPU, recovery beside the
 verification of the same signatures in alternating windows (recover_row).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..4 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|sig_msg_verify|sig_msg_sign|hash_slots [--alg sm2|ecrdsa|ecgdsa --hash 11|13|14|2 --curve C]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..4 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -200,6 +200,126 @@ def sig_family_row(a, ctx, dev, stream, rng, B):
                       "ecdsa_same_run": {"value": B / me, "unit": kind + "/s", "ecdsa_ms": [1e3 * x for x in te]},
                       "family_over_ecdsa": me / mf, "gate": gate,
                       "config": {"workload": a.workload, "alg": a.alg, "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+    cv.free()
+    ctx.close()
+
+
+def sig_msg_row(a, ctx, dev, stream, rng, B):
+    """ECGDSA / ECRDSA / SM2 from messages (ec_sig_verify_msg_batch_dev / ec_sig_sign_msg_batch_dev, --alg, --hash 1 .. 4, 11, 13, 14) beside
+    the digest-level twin (ec_sig_verify_batch_dev / ec_sig_sign_batch_dev) on the same keys in the same run, in alternating windows of
+    a.steps calls; --workload hash_slots: the bare slot hash (ec_hash_slots_batch_dev) beside SHA-256 of the same slots, ns per item.
+    32-octet messages, inputs resident in HBM.  The twin's digests are random octets of the hash's size: its cost does not depend on
+    them.  Gates: every signature the message-level call made is accepted by the message-level verification, none with its
+    neighbour's slot.  One GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload %s measures one GPU: run it with --gpus 1, outside torch.distributed.run" % a.workload)
+    import oracles as O
+    ht = a.hash
+    hl = libecc_amd.api.HASH_SLOT_SIZES.get(ht)
+    if hl is None:
+        raise SystemExit("--workload %s: --hash 1 .. 4, 11, 13 or 14" % a.workload)
+
+    def t(b):
+        return torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev)
+
+    def windows(fns):
+        for _ in range(a.warmup):
+            for fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        acc = [[] for _ in fns]
+        for _ in range(3):
+            for fn, ac in zip(fns, acc):
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    fn()
+                torch.cuda.synchronize()
+                ac.append((time.perf_counter() - t0) / a.steps)
+        return acc
+
+    mlen = 32
+    if a.workload == "hash_slots":
+        stride = 4 + mlen
+        sl = np.zeros((B, stride), dtype=np.uint8)
+        sl[:, 0] = mlen
+        sl[:, 4:] = rng.integers(0, 256, size=(B, mlen), dtype=np.uint8)
+        d_sl = t(sl.tobytes())
+        d_a, d_b = torch.empty(hl * B, dtype=torch.uint8, device=dev), torch.empty(32 * B, dtype=torch.uint8, device=dev)
+        ta, tb = windows([lambda: ctx.hash_slots_dev(ht, B, d_sl.data_ptr(), stride, d_a.data_ptr(), stream.cuda_stream),
+                          lambda: ctx.hash_slots_dev(2, B, d_sl.data_ptr(), stride, d_b.data_ptr(), stream.cuda_stream)])
+        ma, mb = float(np.median(ta)), float(np.median(tb))
+        print(json.dumps({"metric": "hash_type %d of 2^%d slots of 32-octet messages, ns per item (device-resident)" % (ht, a.batch_log2),
+                          "value": 1e9 * ma / B, "unit": "ns/item", "ms": [1e3 * x for x in ta],
+                          "sha256_same_run": {"value": 1e9 * mb / B, "unit": "ns/item", "ms": [1e3 * x for x in tb]},
+                          "config": {"workload": a.workload, "hash": ht, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+        ctx.close()
+        return
+    alg = {"ecgdsa": 6, "ecrdsa": 7, "sm2": 8}[a.alg]
+    ident = b"1234567812345678" if alg == 8 else None
+    blank = hl if alg == 8 else 0
+    curve = a.curve
+    cv = ctx.curve(curve)
+    q = O.CURVES[curve]["q"]
+    ql = O.qlen(curve)
+    raw = rng.integers(0, 256, size=(2, B, ql + 8), dtype=np.uint8)
+
+    def scal(rows, below):
+        return [(int.from_bytes(rows[i].tobytes(), "big") % below) + 1 for i in range(B)]
+    xs, ks = scal(raw[0], q - 2), scal(raw[1], q - 1)
+    privs, nonces = (b"".join(v.to_bytes(ql, "big") for v in vs) for vs in (xs, ks))
+    pubs, st = cv.scalar_mult(b"".join(pow(x, -1, q).to_bytes(ql, "big") for x in xs) if alg == 6 else privs)
+    assert set(st) == {0}
+    stride = 4 + blank + mlen
+    sl = np.zeros((B, stride), dtype=np.uint8)
+    sl[:, 0] = blank + mlen
+    sl[:, 4 + blank:] = rng.integers(0, 256, size=(B, mlen), dtype=np.uint8)
+    slots = sl.tobytes()
+    dg = rng.integers(0, 256, size=hl * B, dtype=np.uint8).tobytes()
+    sigs_t, st = cv.sig_sign(alg, privs, nonces, dg, hl)
+    assert set(st) == {0}
+    sigs, st = cv.sig_sign_msg(alg, ht, privs, nonces, slots, stride, ident, pubs if alg == 8 else None)
+    assert set(st) == {0}
+    d_pub, d_sig, d_sig_t, d_dg, d_x, d_k, d_sl = (t(b) for b in (pubs, sigs, sigs_t, dg, privs, nonces, slots))
+    d_res = torch.empty(B, dtype=torch.uint8, device=dev)
+    d_out, d_st = torch.empty(2 * ql * B, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    sign = a.workload == "sig_msg_sign"
+    p_pub = d_pub.data_ptr() if alg == 8 else None
+
+    def twin():
+        if sign:
+            cv.sig_sign_dev(alg, B, d_x.data_ptr(), d_k.data_ptr(), d_dg.data_ptr(), hl, d_out.data_ptr(), d_st.data_ptr(), stream.cuda_stream)
+        else:
+            cv.sig_verify_dev(alg, B, d_pub.data_ptr(), d_sig_t.data_ptr(), d_dg.data_ptr(), hl, d_res.data_ptr(), stream.cuda_stream)
+
+    def msg():
+        if sign:
+            cv.sig_sign_msg_dev(alg, ht, B, d_x.data_ptr(), p_pub, d_k.data_ptr(), d_sl.data_ptr(), stride, ident, d_out.data_ptr(), d_st.data_ptr(),
+                                stream.cuda_stream)
+        else:
+            cv.sig_verify_msg_dev(alg, ht, B, d_pub.data_ptr(), d_sig.data_ptr(), d_sl.data_ptr(), stride, ident, d_res.data_ptr(), stream.cuda_stream)
+    # ---- gates ----
+    cv.sig_verify_msg_dev(alg, ht, B, d_pub.data_ptr(), d_sig.data_ptr(), d_sl.data_ptr(), stride, ident, d_res.data_ptr(), stream.cuda_stream)
+    torch.cuda.synchronize()
+    if bytes(d_res.cpu().numpy()) != bytes(B):
+        raise SystemExit("PARITY FAILURE: a signature the device made was rejected")
+    d_rot = torch.roll(d_sl, stride)
+    cv.sig_verify_msg_dev(alg, ht, B, d_pub.data_ptr(), d_sig.data_ptr(), d_rot.data_ptr(), stride, ident, d_res.data_ptr(), stream.cuda_stream)
+    torch.cuda.synchronize()
+    if bytes(d_res.cpu().numpy()) != b"\1" * B:
+        raise SystemExit("PARITY FAILURE: a signature was accepted for another item's message")
+    msg()
+    torch.cuda.synchronize()
+    if sign and (bytes(d_out.cpu().numpy()) != sigs or bytes(d_st.cpu().numpy()) != bytes(B)):
+        raise SystemExit("PARITY FAILURE: the device-pointer form signs differently")
+    tt, tm = windows([twin, msg])
+    mt, mm = float(np.median(tt)), float(np.median(tm))
+    kind = "signatures" if sign else "verifications"
+    print(json.dumps({"metric": "%s %s/sec from 32-octet messages, hash_type %d (%s, batch=2^%d, device-resident)" % (a.alg.upper(), kind, ht, curve.lower(), a.batch_log2),
+                      "value": B / mm, "unit": kind + "/s", "msg_ms": [1e3 * x for x in tm],
+                      "digest_level_same_run": {"value": B / mt, "unit": kind + "/s", "ms": [1e3 * x for x in tt]},
+                      "msg_over_digest_level": mt / mm,
+                      "gate": "all 2^%d device-made signatures accepted, none for its neighbour's message" % a.batch_log2,
+                      "config": {"workload": a.workload, "alg": a.alg, "hash": ht, "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
     cv.free()
     ctx.close()
 
@@ -895,11 +1015,11 @@ def eddsa_sign_row(a, ctx, dev, stream, rng, B):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_msg_verify", "sig_msg_sign", "hash_slots", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
     ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa",
                                                     "ed25519", "ed25519ctx", "ed25519ph", "ed448", "ed448ph"],
                     help="eddsa_sign: ed25519, ed25519ctx, ed25519ph, ed448, ed448ph; sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
-    ap.add_argument("--hash", type=int, default=None, choices=[0, 1, 2, 3, 4, 16],
+    ap.add_argument("--hash", type=int, default=None, choices=[0, 1, 2, 3, 4, 11, 13, 14, 16],
                     help="bign_verify / bign_sign: 0 the caller hashed (SHA-256 digests supplied), 16 (default) belt-hash of message slots on the device; "
                          "decdsa_sign: 1 .. 4, SHA-224 / 256 (default) / 384 / 512")
     ap.add_argument("--secret", action="store_true", help="dbign_sign / bip0340_sign: the context in secret-scalar mode")
@@ -916,6 +1036,8 @@ def main():
     ap.add_argument("--mad-peak", type=float, default=0.0, help="lane-MADs/s of the v_mad_u64_u32 streams measured by ubench (VGPR multiplier); 0: measure now")
     ap.add_argument("--mad-peak-sgpr", type=float, default=0.0, help="the same with an SGPR multiplier")
     a = ap.parse_args()
+    if a.hash is None and a.workload in ("sig_msg_verify", "sig_msg_sign", "hash_slots"):
+        a.hash = {"sm2": 11, "ecrdsa": 13, "ecgdsa": 2}.get(a.alg, 11)   # the hash each scheme is deployed with
     if a.hash is None:
         a.hash = 2 if a.workload == "decdsa_sign" else 16
     # the option means something to these workloads only; the others ignore it, as they always have
@@ -959,6 +1081,8 @@ def main():
         return recover_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("sig_verify", "sig_sign"):
         return sig_family_row(a, ctx, dev, stream, rng, B)
+    if a.workload in ("sig_msg_verify", "sig_msg_sign", "hash_slots"):
+        return sig_msg_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("sig_hashed_verify", "sig_hashed_sign"):
         return sig_hashed_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("schnorr_verify", "schnorr_sign"):
