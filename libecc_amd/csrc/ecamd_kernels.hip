@@ -78,6 +78,15 @@ template <int NW> static __device__ __forceinline__ Pt<NW> tbl_load_masked(const
 	return R;
 }
 
+template <int NW> static __device__ __forceinline__ Pt<NW> pt_select(bool c, const Pt<NW> &a, const Pt<NW> &b)
+{
+	Pt<NW> r;
+	r.X = fe_select<NW>(c, a.X, b.X);
+	r.Y = fe_select<NW>(c, a.Y, b.Y);
+	r.Z = fe_select<NW>(c, a.Z, b.Z);
+	return r;
+}
+
 // MASKED: the scalar is secret -- table look-ups by full scan (above); the rest of the kernel is already uniform (complete
 // formulas, fixed window count, no digit-dependent branch)
 template <int NW, bool MASKED = false> __global__ __launch_bounds__(64) void k_smul(EcamdSmulArgs A)
@@ -122,9 +131,15 @@ template <int NW, bool MASKED = false> __global__ __launch_bounds__(64) void k_s
 	tbl_store<NW>(A.tbl, A.stride, i, 0, acc);
 	acc = P;
 	tbl_store<NW>(A.tbl, A.stride, i, 1, acc);
+	// The walk below adds multiples of P to one another.  On a curve of even order a base point of small even order (4, 6, ...)
+	// makes some acc - T a point of order two: the complete addition's exceptional pair (Y3 = Z3 = 0, curves/prj_pt.c:1058-1060).
+	// The reference's ladder never meets one (there T1 - T0 = P throughout, and a P of order two was refused above), so such an
+	// item is walked again the ladder's way further down.
+	bool exc = false;
 #pragma unroll 1
 	for (int e = 2; e < ECAMD_TBL_ENTRIES; e++) {
 		acc = pt_add<NW>(acc, P, slot);
+		exc = exc | (fe_is_zero<NW>(acc.Z) & fe_is_zero<NW>(acc.Y));
 		tbl_store<NW>(A.tbl, A.stride, i, e, acc);
 	}
 
@@ -142,6 +157,20 @@ template <int NW, bool MASKED = false> __global__ __launch_bounds__(64) void k_s
 		const u32 dig = (t & 1) ? (byte & 15u) : (byte >> 4);
 		const Pt<NW> T = MASKED ? tbl_load_masked<NW>(A.tbl, A.stride, i, dig) : tbl_load<NW>(A.tbl, A.stride, i, dig);
 		acc = pt_add<NW>(acc, T, slot);
+		exc = exc | (fe_is_zero<NW>(acc.Z) & fe_is_zero<NW>(acc.Y));
+	}
+	if (exc) {
+		// Montgomery ladder over all 8 * slen bits: R1 - R0 = P at every step, no exceptional pair; [m]P as the reference has it
+		Pt<NW> R0 = pt_infinity<NW>(slot), R1 = P;
+#pragma unroll 1
+		for (int t = 0; t < 8 * (int)A.slen; t++) {
+			const bool bit = ((sc[t >> 3] >> (7 - (t & 7))) & 1u) != 0;
+			const Pt<NW> S = pt_add<NW>(R0, R1, slot);
+			const Pt<NW> D = pt_dbl<NW>(pt_select<NW>(bit, R1, R0), slot);
+			R0 = pt_select<NW>(bit, S, D);
+			R1 = pt_select<NW>(bit, D, S);
+		}
+		acc = R0;
 	}
 
 	// ---- to affine (prj_pt_unique, prj_pt.c:241-273) and export (:600-624) ----

@@ -57,10 +57,118 @@ int get_unsafe_random(unsigned char *buf, u16 len) { return get_random(buf, len)
 void refdrv_seed(uint64_t s) { tl_seed = s; }
 
 /* ---- helpers ---- */
+/*
+ * User-defined curves: refdrv_define_curve keeps the seven byte strings an application would bring (p, a, b, #E, Gx, Gy, q)
+ * under a name of the caller's, and every entry point below then takes that name like a built-in one.  The ec_params come from
+ * the reference's own import_params over an ec_str_params filled here; the Montgomery and division constants that structure
+ * carries are the ones the reference's fp_ctx_init_from_p computes for p.  import_params insists on the name of a curve the
+ * library knows (it looks the curve type up by name), so the structure borrows SECP256R1's: the type is read by the structured
+ * key formats only, which nothing here uses on such a curve.
+ */
+#define UC_MAX 32
+#define UC_BYTES 96
+typedef struct {
+	char name[32];
+	uint8_t v[7][UC_BYTES];
+	uint8_t len[7];
+} user_curve;
+static user_curve g_user[UC_MAX];
+static int g_user_n;
+
+static int load_user_params(const user_curve *uc, ec_params *params)
+{
+	static const uint8_t one[1] = {1}, zero[1] = {0}, oid[] = "0.0", name[] = "SECP256R1";
+	uint8_t r[UC_BYTES], r2[UC_BYTES], pn[UC_BYTES], cof[UC_BYTES], pbl[2], qbl[2], mpinv[8], prec[8], psh[1];
+	nn p, q, order, h, rem;
+	fp_ctx f;
+	bitcnt_t qbits = 0;
+	uint8_t wl;
+	int ret, k;
+	p.magic = q.magic = order.magic = h.magic = rem.magic = WORD(0);
+	ret = nn_init_from_buf(&p, uc->v[0], uc->len[0]);
+	ret = ret || fp_ctx_init_from_p(&f, &p);
+	ret = ret || nn_init_from_buf(&order, uc->v[3], uc->len[3]) || nn_init_from_buf(&q, uc->v[6], uc->len[6]);
+	ret = ret || nn_bitlen(&q, &qbits) || nn_divrem(&h, &rem, &order, &q);
+	if (ret || f.p.wlen * 8u > UC_BYTES) {
+		return -1;
+	}
+	wl = (uint8_t)(f.p.wlen * 8u);
+	ret = nn_export_to_buf(r, wl, &f.r) || nn_export_to_buf(r2, wl, &f.r_square) || nn_export_to_buf(pn, wl, &f.p_normalized) ||
+	      nn_export_to_buf(cof, wl, &h);
+	if (ret) {
+		return -1;
+	}
+	for (k = 0; k < 8; k++) {
+		mpinv[k] = (uint8_t)(f.mpinv >> (56 - 8 * k));
+		prec[k] = (uint8_t)(f.p_reciprocal >> (56 - 8 * k));
+	}
+	psh[0] = (uint8_t)f.p_shift;
+	pbl[0] = (uint8_t)(f.p_bitlen >> 8);
+	pbl[1] = (uint8_t)f.p_bitlen;
+	qbl[0] = (uint8_t)(qbits >> 8);
+	qbl[1] = (uint8_t)qbits;
+	{
+		const ec_str_param s_p = {uc->v[0], uc->len[0]}, s_pbl = {pbl, 2}, s_r = {r, wl}, s_r2 = {r2, wl}, s_mpinv = {mpinv, 8},
+				   s_psh = {psh, 1}, s_pn = {pn, wl}, s_prec = {prec, 8}, s_a = {uc->v[1], uc->len[1]},
+				   s_b = {uc->v[2], uc->len[2]}, s_order = {uc->v[3], uc->len[3]}, s_gx = {uc->v[4], uc->len[4]},
+				   s_gy = {uc->v[5], uc->len[5]}, s_gz = {one, 1}, s_q = {uc->v[6], uc->len[6]}, s_qbl = {qbl, 2},
+				   s_cof = {cof, wl}, s_zero = {zero, 1}, s_oid = {oid, sizeof(oid)}, s_name = {name, sizeof(name)};
+		const ec_str_params sp = {
+			.p = &s_p, .p_bitlen = &s_pbl, .r = &s_r, .r_square = &s_r2, .mpinv = &s_mpinv, .p_shift = &s_psh,
+			.p_normalized = &s_pn, .p_reciprocal = &s_prec, .a = &s_a, .b = &s_b, .curve_order = &s_order, .gx = &s_gx,
+			.gy = &s_gy, .gz = &s_gz, .gen_order = &s_q, .gen_order_bitlen = &s_qbl, .cofactor = &s_cof,
+			.alpha_montgomery = &s_zero, .gamma_montgomery = &s_zero, .alpha_edwards = &s_zero, .oid = &s_oid, .name = &s_name,
+		};
+		return import_params(params, &sp);
+	}
+}
+
+/* 0: the curve is defined (or redefined) under `name`; -1: the reference cannot hold it (a p beyond its largest nn, for one) */
+int refdrv_define_curve(const char *name, const uint8_t *p, uint32_t plen, const uint8_t *a, uint32_t alen, const uint8_t *b,
+			uint32_t blen, const uint8_t *order, uint32_t olen, const uint8_t *gx, uint32_t gxlen, const uint8_t *gy,
+			uint32_t gylen, const uint8_t *q, uint32_t qlen)
+{
+	const uint8_t *src[7] = {p, a, b, order, gx, gy, q};
+	const uint32_t len[7] = {plen, alen, blen, olen, gxlen, gylen, qlen};
+	user_curve uc;
+	ec_params params;
+	int k, slot;
+	if (strlen(name) >= sizeof(uc.name)) {
+		return -1;
+	}
+	memset(&uc, 0, sizeof(uc));
+	strcpy(uc.name, name);
+	for (k = 0; k < 7; k++) {
+		if (!src[k] || len[k] < 1 || len[k] > UC_BYTES) {
+			return -1;
+		}
+		memcpy(uc.v[k], src[k], len[k]);
+		uc.len[k] = (uint8_t)len[k];
+	}
+	if (load_user_params(&uc, &params)) {
+		return -1;
+	}
+	for (slot = 0; slot < g_user_n && strcmp(g_user[slot].name, name); slot++) {
+	}
+	if (slot == UC_MAX) {
+		return -1;
+	}
+	g_user[slot] = uc;
+	if (slot == g_user_n) {
+		g_user_n++;
+	}
+	return 0;
+}
+
 static int load_params(const char *curve, ec_params *params)
 {
 	const ec_str_params *sp = NULL;
-	int ret;
+	int ret, k;
+	for (k = 0; k < g_user_n; k++) {
+		if (!strcmp(g_user[k].name, curve)) {
+			return load_user_params(&g_user[k], params);
+		}
+	}
 	ret = ec_get_curve_params_by_name((const u8 *)curve, (u8)(strlen(curve) + 1), &sp);
 	if (ret || sp == NULL) {
 		return -1;

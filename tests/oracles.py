@@ -34,12 +34,18 @@ def curve_type(curve):
     return int(CURVES[curve]["type"])
 
 
+def curve_params(curve):
+    """the parameters of a built-in curve (by name) or of a user-defined one (a dict with the ints p, a, b, order, gx, gy, q and
+    a 'name' of its own, as tests/user_curves.py loads them)"""
+    return curve if isinstance(curve, dict) else CURVES[curve]
+
+
 def clen(curve):
-    return (CURVES[curve]["p"].bit_length() + 7) // 8
+    return (curve_params(curve)["p"].bit_length() + 7) // 8
 
 
 def qlen(curve):
-    return (CURVES[curve]["q"].bit_length() + 7) // 8
+    return (curve_params(curve)["q"].bit_length() + 7) // 8
 
 
 def _be(x, n=None):
@@ -57,13 +63,13 @@ def build_oracle():
 
 
 class Oracle:
-    """Restatement oracle bound to one curve."""
+    """Restatement oracle bound to one curve: a built-in name, or a parameter dict (curve_params)."""
 
     def __init__(self, curve):
         self.L = C.CDLL(build_oracle())
-        self.curve = curve
-        c = CURVES[curve]
-        self.clen, self.qlen = clen(curve), qlen(curve)
+        c = curve_params(curve)
+        self.curve = c["name"]
+        self.clen, self.qlen = clen(c), qlen(c)
         self.nl = (c["p"].bit_length() + 63) // 64
         self.ctx = C.create_string_buffer(self.L.orc_sizeof_curve())
         args = []
@@ -200,6 +206,23 @@ def have_ref():
     return os.path.exists(REF_SO)
 
 
+def ref_name(curve):
+    """the name the driver knows a curve by.  A parameter dict (curve_params) is first handed to the driver, which builds the
+    reference's ec_params from it through the reference's own import_params; None when the reference cannot hold the curve
+    (a field beyond its largest integer)."""
+    if not isinstance(curve, dict):
+        return curve.encode()
+    L = C.CDLL(REF_SO)
+    if not hasattr(L, "refdrv_define_curve"):
+        raise RuntimeError("oracle/_ref/libecc_ref.so predates user-defined curves: rebuild it (make -C oracle ref)")
+    args = []
+    for k in ("p", "a", "b", "order", "gx", "gy", "q"):
+        b = _be(curve[k])
+        args += [b, C.c_uint32(len(b))]
+    name = curve["name"].encode()
+    return name if L.refdrv_define_curve(name, *args) == 0 else None
+
+
 def host_threads():
     try:
         n = len(os.sched_getaffinity(0))
@@ -240,10 +263,11 @@ class RefLib:
 
     def __init__(self, curve):
         self.L = C.CDLL(REF_SO)
-        self.curve = curve
-        self.name = curve.encode()
+        self.name = ref_name(curve)
+        assert self.name is not None, "the reference build cannot hold this curve"
+        self.curve = curve_params(curve)["name"]
         self.clen, self.qlen = clen(curve), qlen(curve)
-        self.nl = (CURVES[curve]["p"].bit_length() + 63) // 64
+        self.nl = (curve_params(curve)["p"].bit_length() + 63) // 64
         assert self.L.refdrv_coord_len(self.name) == self.clen
 
     def scalar_mult(self, scalars, points=None, slen=None, nthreads=1, timing=False):
@@ -325,7 +349,7 @@ def ref_y_from_x(curve, xs):
     cl = clen(curve)
     n = len(xs) // cl
     y1, y2, st = C.create_string_buffer(max(1, cl * n)), C.create_string_buffer(max(1, cl * n)), C.create_string_buffer(max(1, n))
-    assert L.refdrv_y_from_x_batch(curve.encode(), n, xs, y1, y2, st) == 0
+    assert L.refdrv_y_from_x_batch(ref_name(curve), n, xs, y1, y2, st) == 0
     return y1.raw[:cl * n], y2.raw[:cl * n], st.raw[:n]
 
 
