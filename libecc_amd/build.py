@@ -4,6 +4,7 @@ hipcc cross-compiles without a GPU, so this runs in the authoring container; the
 travels to the GPU box with the repo snapshot (it is git-ignored, not gpurun-ignored).
 """
 import os
+import re
 import subprocess
 import sys
 
@@ -11,21 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libecc_amd.so")
-SOURCES = ["ecamd_kernels.hip", "ecamd_p256_kernel.hip", "ecamd_hash.hip", "ecamd_hash2.hip", "ecamd_rfc6979.hip", "ecamd_detnonce.hip", "ecamd_eddsa_sign.hip", "ecamd_host.cpp", "ecamd_multi.cpp"]
-DEPS = ["ecamd_madchain.h", "ecamd_field.h", "ecamd_point.h", "ecamd_u29.h", "ecamd_p256.h", "ecamd_u29g.h", "ecamd_jacg.h",
-        "ecamd_internal.h", "ecamd_lattice.h", "ecamd_randmod.h", "ecamd_recover.h", "ecamd_recover_kernels.h",
-        "ecamd_sigfam.h", "ecamd_sigfam_kernels.h", "ecamd_sighash.h", "ecamd_sighash_kernels.h",
-        "ecamd_curve_table.inc"]
-# headers that only some translation units include
-SOURCE_DEPS = {"ecamd_kernels.hip": ["ecamd_schnorr.h", "ecamd_schnorr_kernels.h", "ecamd_bign.h", "ecamd_bign_kernels.h"],
-               "ecamd_host.cpp": ["ecamd_schnorr.h", "ecamd_bign.h", "ecamd_rfc6979.h", "ecamd_eddsa_sign.h", "ecamd_belt.h", "ecamd_dbign_nonce.h",
-                                  "ecamd_bip0340_nonce.h", "ecamd_sm3.h", "ecamd_sm2z.h"], "ecamd_hash.hip": ["ecamd_belt.h"],
-               "ecamd_hash2.hip": ["ecamd_sm3.h", "ecamd_streebog.h", "ecamd_sm2z.h", "ecamd_rfc6979.h"],
-               "ecamd_rfc6979.hip": ["ecamd_rfc6979.h"],
-               "ecamd_detnonce.hip": ["ecamd_rfc6979.h", "ecamd_belt.h", "ecamd_dbign_nonce.h", "ecamd_bip0340_nonce.h"],
-               "ecamd_eddsa_sign.hip": ["ecamd_rfc6979.h", "ecamd_eddsa_sign.h"]}
-# the public header only matters to the host-side translation units (the kernels see ecamd_internal.h)
-HOST_DEPS = [os.path.join("..", "..", "include", "libecc_amd.h")]
+SOURCES = ["ecamd_kernels.hip", "ecamd_p256_kernel.hip", "ecamd_hash.hip", "ecamd_hash2.hip", "ecamd_rfc6979.hip", "ecamd_detnonce.hip", "ecamd_eddsa_sign.hip",
+           "ecamd_host.cpp", "ecamd_host_sigfam.cpp", "ecamd_multi.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-bitwise-instead-of-logical", "-DU29_ASM_MAD"]
@@ -35,7 +23,18 @@ def _stale(target, inputs):
     if not os.path.exists(target):
         return True
     t = os.path.getmtime(target)
-    return any(os.path.getmtime(i) > t for i in inputs)
+    return any(not os.path.exists(i) or os.path.getmtime(i) > t for i in inputs)
+
+
+def _depfile_inputs(dpath):
+    """The prerequisites the compiler wrote beside an object (-MD -MF <obj>.d), or None when there is no such file."""
+    try:
+        text = open(dpath).read()
+    except OSError:
+        return None
+    # make syntax: rules "target: dep dep ...", continued over lines by a backslash, a space inside a path written as "\ "
+    words = re.split(r"(?<!\\)\s+", text.replace("\\\n", " "))
+    return [w.replace("\\ ", " ") for w in words if w and not w.endswith(":")]
 
 
 G29_SIZES = [192, 224, 255, 256, 320, 384, 448, 511, 512, 521]
@@ -68,20 +67,19 @@ def _jobs():
 def build(force=False, verbose=False):
     from concurrent.futures import ThreadPoolExecutor
     os.makedirs(LIBDIR, exist_ok=True)
-    deps = [os.path.join(CSRC, d) for d in DEPS]
-    hdeps = [os.path.join(CSRC, d) for d in HOST_DEPS]
     todo, objs = [], []
     for src, obj, extra in _jobs():
         spath, opath = os.path.join(CSRC, src), os.path.join(LIBDIR, obj)
         objs.append(opath)
-        cmd = [HIPCC] + FLAGS + extra + ["-x", "hip", "-c", spath, "-o", opath]
-        # an object is also stale when it was built with other flags (its command line is kept beside it)
+        cmd = [HIPCC] + FLAGS + extra + ["-MD", "-MF", opath + ".d", "-x", "hip", "-c", spath, "-o", opath]
+        # an object is stale when it was built with other flags (its command line is kept beside it), when the compiler's list of
+        # what it read (<obj>.d) is missing, or when anything on that list is newer than the object
         try:
             same_cmd = open(opath + ".cmd").read() == " ".join(cmd)
         except OSError:
             same_cmd = False
-        if force or not same_cmd or _stale(opath, [spath] + deps + (hdeps if src.endswith(".cpp") else []) +
-                                              [os.path.join(CSRC, d) for d in SOURCE_DEPS.get(src, [])]):
+        inputs = _depfile_inputs(opath + ".d")
+        if force or not same_cmd or inputs is None or _stale(opath, [spath] + inputs):
             todo.append(cmd)
 
     def run(cmd):

@@ -7,45 +7,21 @@
 //   * batch plumbing: staging buffers, per-lane window-table scratch, chunking, streams.
 // No arithmetic of the hot path runs on the host and there is no CPU fallback: every entry
 // point needs a live HIP device.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <string.h>
-#include <strings.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string>
-#include <vector>
-#include <functional>
-#include <mutex>
-#include <sys/random.h>
-
-#include "../../include/libecc_amd.h"
-#include "ecamd_internal.h"
-#include "ecamd_sighash.h"
-#include "ecamd_schnorr.h"
-#include "ecamd_bign.h"
+#include "ecamd_host_internal.h"
 #include "ecamd_rfc6979.h"
-#include "ecamd_dbign_nonce.h"
-#include "ecamd_bip0340_nonce.h"
-#include "ecamd_sm2z.h"
 #include "ecamd_eddsa_sign.h"
+
+using namespace ecamd_host;
 
 // ------------------------------------------------------------------------------------------
 // error reporting
 // ------------------------------------------------------------------------------------------
 static thread_local std::string g_err;
-static int fail(const std::string &m)
+int ecamd_host::fail(const std::string &m)
 {
 	g_err = m;
 	return -1;
 }
-#define HIPCHK(expr) \
-	do { \
-		hipError_t e_ = (expr); \
-		if (e_ != hipSuccess) { \
-			return fail(std::string(#expr) + ": " + hipGetErrorString(e_)); \
-		} \
-	} while (0)
 
 extern "C" const char *ecamd_last_error(void) { return g_err.c_str(); }
 // for the other translation units of the library (ecamd_multi.cpp): not part of the public ABI
@@ -54,7 +30,6 @@ __attribute__((visibility("default"))) void ecamd_set_error(const char *msg) { g
 // ------------------------------------------------------------------------------------------
 // small host big integers (little-endian 32-bit words); only used to derive constants
 // ------------------------------------------------------------------------------------------
-typedef std::vector<uint32_t> Big;
 
 static void big_trim(Big &a)
 {
@@ -99,7 +74,7 @@ static int big_cmp(const Big &a, const Big &b)
 	}
 	return 0;
 }
-static int big_bitlen(const Big &a)
+int ecamd_host::big_bitlen(const Big &a)
 {
 	for (size_t i = a.size(); i-- > 0;) {
 		if (a[i]) {
@@ -192,7 +167,7 @@ static void big_store(uint32_t *dst, int nw, const Big &a)
 		dst[i] = (size_t)i < a.size() ? a[(size_t)i] : 0;
 	}
 }
-static void big_to_be(uint8_t *dst, int len, const Big &a)
+void ecamd_host::big_to_be(uint8_t *dst, int len, const Big &a)
 {
 	for (int i = 0; i < len; i++) {
 		int pos = len - 1 - i;
@@ -212,185 +187,6 @@ static const CurveRow g_curve_rows[] = {
 #include "ecamd_curve_table.inc"
 };
 
-// ------------------------------------------------------------------------------------------
-// objects behind the opaque handles
-// ------------------------------------------------------------------------------------------
-// ------------------------------------------------------------------------------------------
-// The scratch slots of ecamd_ctx::stage[].  Every device core works in a FRAME: a set of named slots, sized by stage_need()
-// when the core starts and dead when it returns.  Frames of different cores share indices on purpose (one context runs one
-// call at a time, ctx->mu), so a buffer grown by one family serves the next.  This block is the one place that says which
-// frames exist, who uses them, and which may be live at the same time; two names with one value in frames that can be
-// live together are a bug.
-//
-//   frame (prefix)            slots         used by                                                live beside it
-//   HW_  hand-staged host     0..3          pt_batch, ec_prj_pt_op_batch_fmt, ec_prj_pt_unprotected_mult_batch, ec_fp_op_batch   nothing
-//   PF_  point formats        0..7          pt_fmt_batch                                           (smul_dev_locked: no slots)
-//   YX_  square roots         0..3          y_from_x_common                                        nothing
-//   MH_  EdDSA whole batch    0..3, 14      eddsa_msm_host_locked, eddsa448_msm_host_locked        EV_ 3..9, 12, 13 (Ed448 only: hence 14, not 3)
-//   MS_  Schnorr whole batch  0..4          schnorr_msm_host_locked                                nothing (the evaluation works in ctx->msm)
-//   XD_  X25519 / X448        2..5, 7, 8    xdh_dev_locked                                         nothing
-//   CD_  ECCCDH               3..8          ecccdh_dev_locked                                      nothing
-//   ST_  verification         3..15         two_mul_dev / two_mul_sum_dev and their callers: ecdsa_two_smul_dev, ecdsa_fused_g_dev,
-//                                           hsig_ / bign_ / schnorr_item_verify_dev_locked         ST_SLOTS.., ST_TARGET, SI_, EF_, BW_
-//   VP_  secp256r1 loop       3..5, 7       ecdsa_verify_dev_locked (ST_U, ST_V and VP_*); its redo pass is the ST_ frame, after it   ST_TARGET, EF_
-//   RC_  recovery             10..14        ecdsa_recover_dev_locked, on top of ST_U .. ST_FLAGS (it has no [q]Y pass and no W' of its own)
-//   SG_  signing              3..5, 7, 20   ecdsa_ / sig_ / hsig_ / bign_ / schnorr_item_sign_dev_locked, ec_ecdsa_sign_msg_batch,
-//                                           decdsa_sign_ / dbign_sign_ / bip0340_dev_locked (SG_NONCES)   ST_FLAGS, ST_SLOTS, ST_DIGESTS, ST_BELT
-//   EV_  EdDSA verification   3..15, 18, 19 eddsa_verify_dev_locked, eddsa448_verify_dev_locked, eddsa448_msm_dev_locked   ST_DIGESTS (h), EP_, EB_, MH_
-//   SR_  EdDSA [r]B           3..5          eddsa_sign_R_dev_locked                                ES_ (it runs inside the one-call signing)
-//   EN_  EdDSA point encoding 3, 4          ec_eddsa_encode_point_batch                            nothing
-//   BL_  blinded scalars      12, 13        ec_prj_pt_mul_blind_batch                              (smul_dev_locked: no slots)
-//   EF_  projective ECDSA keys 12, 14..16   ecdsa_verify_host_fmt: the imported keys; the regrouped items of keys at infinity   ST_ 3..11, VP_, ST_DIGESTS, ST_TARGET
-//        slots and digests    16..18        ST_SLOTS, ST_DIGESTS, ST_BELT: the staged message slots and what is hashed from them, for every family
-//   SI_  Schnorr item extras  18, 20..23    schnorr_item_verify_dev_locked; 20 / 21 also ec_schnorr_verify_msg_all_batch's key import   ST_, BW_
-//   EP_  EdDSA projective     20..23        eddsa_verify_msg_prj_impl, per chunk                   EV_, EB_, ST_DIGESTS
-//   BW_  Schnorr batch-wide   24..28        ec_schnorr_verify_msg_all_batch: filed chunk by chunk, read when the last chunk is in,
-//                                           so they outlive every per-chunk frame of the call     SI_PRJ_*, ST_DIGESTS, ST_ (item-by-item fallback)
-//   EB_  EdDSA batch-wide     24..27        eddsa_verify_msg_prj_impl, the same way                EP_, EV_, ST_DIGESTS
-//        sig_target           29            ST_TARGET: the comparison target of ECGDSA / ECRDSA / SM2, beside ST_ and VP_
-//   ES_  one-call EdDSA sign  30..40        eddsa_sign_msg_dev_locked, eddsa_pub_key_dev_locked    SR_
-//   SM_  sig from messages    41, 42        sig_msg_verify_ / sig_msg_sign_dev_locked, which outlive the digest-level core they call   ST_, VP_, SG_, ST_SLOTS, ST_DIGESTS, ST_TARGET
-//
-// smul_dev_locked itself takes no slot (ctx->tbl, ctx->tbl_fast); host_pipeline stages in ctx->hbuf.
-// ------------------------------------------------------------------------------------------
-enum StageSlot {
-	HW_IN0 = 0, HW_IN1 = 1, HW_OUT = 2, HW_STATUS = 3,
-	PF_SCALARS = 0, PF_IN = 1, PF_AFF = 2, PF_PRE = 3, PF_RES = 4, PF_RST = 5, PF_OUT = 6, PF_OST = 7,
-	YX_IN = 0, YX_Y1 = 1, YX_Y2 = 2, YX_ST = 3,
-	MH_PUB = 0, MH_SIG = 1, MH_HRAM = 2, MH_VERDICTS = 3, MH_VERDICT448 = 14,
-	MS_S = 0, MS_NE = 1, MS_KEYS = 2, MS_VERDICTS = 3, MS_R = 4,
-	XD_SCALARS = 2, XD_POINTS = 3, XD_FLAGS = 4, XD_REC = 5, XD_OUT = 7, XD_STK = 8,
-	CD_OUT = 3, CD_ST = 4, CD_HQ = 5, CD_STH = 6, CD_QP = 7, CD_STSUB = 8,
-	// W' = [u]G + [v]Y: the multipliers, A = [u]G, B = [v]Y and their status bytes, the flag byte of the prep kernel, the status and the
-	// point of the [q]Y pass, W' and its status, and the sinks of k_recover_fin's second sum A - B
-	ST_U = 3, ST_V = 4, ST_A = 5, ST_B = 6, ST_STA = 7, ST_STB = 8, ST_FLAGS = 9, ST_SUB = 10, ST_QY = 11,
-	ST_W = 12, ST_WSINK = 13, ST_STW = 14, ST_STWSINK = 15,
-	VP_FLAGS = 5, VP_KEYS = 7,   // VP_KEYS: the zeroed points of rejected keys, then the key status
-	RC_YST = 10, RC_X = 11, RC_Y1 = 12, RC_Y2 = 13, RC_R = 14,
-	SG_KG = 3, SG_STKG = 4, SG_Y = 5, SG_STY = 7, SG_NONCES = 20,   // SG_Y, SG_STY: BIP0340's public key
-	// 3: the key as a Weierstrass point, or v and |u| of the half-length scalars; 13: the status of [h]A, or the lattice kernel's meta bytes
-	EV_A = 3, EV_R = 4, EV_FLAGSA = 5, EV_FLAGSR = 6, EV_FLAGSS = 7, EV_S = 8, EV_H = 9, EV_EDA = 10, EV_REC = 11,
-	EV_HA = 12, EV_STHA = 13, EV_SG = 14, EV_STSG = 15, EV_TBL = 18, EV_EDR = 19,
-	EV_NE = 12, EV_GATE = 13,    // eddsa448_msm_dev_locked: q - h, and the gate word with the piece's verdict behind it
-	SR_R = 3, SR_RW = 4, SR_STR = 5,
-	EN_AFF = 3, EN_PRE = 4,
-	BL_SCALARS = 12, BL_BAD = 13,
-	EF_AFF = 12, EF_INF_SIGS = 14, EF_INF_DATA = 15, EF_INF_RES = 16,
-	ST_SLOTS = 16, ST_DIGESTS = 17, ST_BELT = 18,
-	SI_KEY = 18, SI_PRJ_AFF = 20, SI_PRJ_ST = 21, SI_WPT = 22, SI_WST = 23,   // the key as the equation uses it; the projective import; ECFSDSA's W
-	EP_AFF = 20, EP_PRE = 21, EP_KEY = 22, EP_KST = 23,
-	BW_S = 24, BW_NE = 25, BW_KEYS = 26, BW_R = 27, BW_VERDICTS = 28,
-	EB_KEYS = 24, EB_SIGS = 25, EB_HRAM = 26, EB_MARKS = 27,
-	ST_TARGET = 29,
-	ES_A = 30, ES_RHASH = 31, ES_AWIDE = 32, ES_HRAM = 33, ES_R = 34, ES_S = 35, ES_BAD = 36, ES_STR = 37, ES_STA = 38, ES_AENC = 39, ES_PH = 40,
-	SM_BAD = 41, SM_Z = 42,   // the items a message-level ECGDSA / ECRDSA / SM2 call rejects itself; SM2's Z
-	ECAMD_NSTAGE
-};
-static_assert(ECAMD_NSTAGE == SM_Z + 1, "ECAMD_NSTAGE counts the slots: the last frame ends the array");
-
-struct ecamd_ctx {
-	int device;
-	hipStream_t stream;
-	uint32_t max_chunk;
-	// grow-only scratch
-	uint32_t *tbl;      // complete-formula kernel: 16 x 3 x NW words per item, word-major
-	size_t tbl_bytes;
-	uint32_t *tbl_fast; // fast paths: per-item window tables (secp256r1: 512 B affine table + 1120 B staging per item)
-	size_t tbl_fast_bytes;
-	uint8_t *prep_scratch;     // k_ecdsa_prep_g: prefix products, n x NL words
-	size_t prep_scratch_bytes;
-	uint8_t *stage[ECAMD_NSTAGE];
-	size_t stage_bytes[ECAMD_NSTAGE];
-	// the scratch above is shared by every call: a call enqueued on another stream than the previous one first waits
-	// for `busy`, recorded behind the previous call's last kernel (StreamScope)
-	hipEvent_t busy;
-	hipStream_t last_stream;
-	bool inflight;
-	// host-pointer entry points: chunks of host_chunk items, the copy of chunk c+1 overlaps the kernels of chunk c
-	hipStream_t copy_stream;
-	hipEvent_t in_ready[2];
-	// ECDSA verification on secp256r1: k_ecdsa_prep (s^-1, u1, u2 mod q: two waves per SIMD, compute only) runs on this stream
-	// beside the bandwidth-bound k_p256_table / k_p256_affine of the same chunk; the interleaved window loop -- the first reader
-	// of u1, u2 and the flags -- waits for side_done ($ECAMD_NO_SIDE_STREAM: off).  66.0 -> 67.0 M verifications/s.
-	hipStream_t side_stream;
-	hipEvent_t side_fork, side_done, side_mid, side_aux;   // (side_mid / side_aux: the bucket evaluation's second and third joins)
-	hipEvent_t side_hi, side_red;   // the bucket evaluation: the key-only windows are summed (on the caller's stream) / reduced (on the side stream)
-	hipStream_t side2_stream;       // the bucket evaluation: the windows below 2^128 are filed here while the key-only windows are summed
-	hipEvent_t side2_fork, side2_done;
-	bool side2_ok;
-	bool side_ok;
-	uint32_t host_chunk;
-	uint32_t host_first_min;   // smallest first chunk of a multi-chunk call (ECAMD_HOST_RAMP_MIN, default 2^16; host_pipeline)
-	// producer hook of the host-pointer entry points (ecamd_ctx_set_host_ready_hook): called before a range of the caller's input arrays is read
-	ecamd_host_ready_fn ready_fn = nullptr;
-	void *ready_arg = nullptr;
-	uint8_t *hbuf[2][6];       // double-buffered device staging of the caller's arrays (inputs and outputs)
-	size_t hbuf_bytes[2][6];
-	uint32_t comb_min_batch;   // fixed-base batches of at least this many items build / use the generator's comb table (0: never)
-	bool secret_scalars;       // ecamd_ctx_set_secret_scalars: constant-address look-ups, no data-dependent kernel choice
-	int eddsa_msm;             // ecamd_ctx_set_eddsa_msm: 0 never, 1 batches of at least msm_min items, 2 always
-	uint32_t msm_min, msm_k;   // msm_k: items per lane of the Straus evaluation (0: chosen from the batch size)
-	uint8_t *msm;              // scratch of the multi-scalar multiplication
-	size_t msm_bytes;
-	uint8_t msm_seed_bytes[32]; // ecamd_ctx_set_msm_seed: key of the next whole-batch combination's z_i (used once)
-	bool msm_seed_valid;
-	bool timing;               // record HIP events around the kernels of the scalar-mult pipeline
-	hipEvent_t ev[ECAMD_NTIMED + 1];
-	bool ev_valid;
-	hipEvent_t ev_dom[2];      // around the dominant kernel of the last protocol call (verify loop, ladder, Edwards window loop)
-	bool ev_dom_valid;
-	std::mutex mu;
-};
-
-struct ecamd_curve {
-	ecamd_ctx *ctx;
-	int nw;     // 32-bit words per element
-	int slot;   // __constant__ slot: field of definition
-	int qslot;  // __constant__ slot: generator order q as a modulus (-1: protocol ops unavailable)
-	int curve_type;  // libecc's ec_curve_type of a built-in curve (structured keys carry it), 0 for user curves
-	int qnw;    // words of the mod-q kernels: nw, or more when q is longer than p (secp224k1: |q| = 225 > 224)
-	int clen;   // BYTECEIL(pbits)
-	int qlen;   // BYTECEIL(qbits)
-	int pbits, qbits;
-	Big p, a, b, order, gx, gy, q;
-	uint8_t *d_gen;  // generator, affine X||Y big-endian, in HBM; followed by q (qlen bytes) and the cofactor byte
-	uint32_t cofactor; // order / q when that is 1..255, else 0
-	// per-curve constants of the Ed25519 / X25519 / X448 entry points, computed on first use (ctx->mu held)
-	int ed_state;    // 0 not yet, 1 ready, -1 this handle is not the Ed25519 model (ed_err says why)
-	const char *ed_err;
-	EcamdEdDecodeArgs ed_tmpl;
-	uint32_t ed_cof_dbl;
-	int ed448_state;     // Ed448 on the WEI448 handle: 0 not yet, 1 ready, -1 not that curve
-	const char *ed448_err;
-	EcamdEd448DecodeArgs ed448_tmpl;
-	uint8_t ed448_c4[56]; // 4^-1 mod q, big-endian (eddsa_import_pub_key multiplies the key by it)
-	uint32_t ed_2d[9];   // 2 d mod p, plain radix-2^29 digits (Edwards arithmetic of the 2^255 - 19 unit)
-	uint32_t ed_Bx[9], ed_By[9];  // the Ed25519 base point, the same digits
-	int xdh_state;
-	const char *xdh_err;
-	EcamdXdhPrepArgs xdh_tmpl;
-	uint32_t xdh_A3[17];
-	uint8_t xdh_cof;
-	int sqrt_state;  // Tonelli-Shanks constants of fp_sqrt for this field: 0 not yet, 1 ready (ctx->mu held)
-	EcamdYfromXArgs sqrt_tmpl;
-	bool is_p256;    // exactly secp256r1: hand-specialised radix-2^29 Jacobian kernel
-	int gslot;       // constant slot of the generic radix-2^29 Jacobian kernel (-1: none)
-	int gpslot;      // secp256r1 handles only (their scalar multiplication has its own kernels): slot of the dense 256-bit radix-2^29 unit holding
-			 // the curve, for k_prj_import_g (-1: none, k_prj_import<8> serves)
-	int gqslot;      // constant slot of the dense radix-2^29 unit of the ORDER's size holding q as its modulus (k_ecdsa_prep_g; -1: none)
-	int gflavour;    // 0 dense reduction, 1 secp521r1 (p = 2^521 - 1), 2 p = 2^255 - 19, 3 secp384r1's prime, 4 secp256k1's prime, 5 p = 2^448 - 2^224 - 1,
-	                 // 6 secp224r1's prime, 7 secp192r1's prime (3, 6, 7: signed sparse Montgomery reduction)
-	uint32_t *d_comb4;  // the 4-bit comb of the generator for SECRET scalars: secp256r1 65 x 8 entries of 40 words (k_p256_comb4m, built with the
-			    // handle), radix-2^29 units (8 NW + 1) x 8 comb entries (k_comb_g<.., SCAN4>, built on first use); NULL: none
-	bool comb4_off;     // ... its construction was tried
-	uint32_t *d_gtab; // secp256r1: affine window table [1..8]G, radix-2^29 Montgomery digits, 8 x 40 words
-	uint32_t *d_comb; // fast paths: 16-bit comb table of G, built on the first large fixed-base batch (NULL before / disabled)
-	bool comb_off;    // construction failed or is in progress: do not try (again)
-	uint32_t *d_edcomb; // WEI25519 on the 2^255 - 19 unit: 16-bit comb table of the Ed25519 base point ON THE EDWARDS CURVE
-	                    // (k_ed_tail_c25519), built on the first verification batch of comb_min_batch items; NULL before / disabled
-	bool edcomb_off;
-	uint32_t qdig[9]; // secp256r1: digits of the group order
-};
 
 static const int k_widths[] = {6, 7, 8, 10, 12, 14, 16, 17};
 
@@ -779,40 +575,26 @@ extern "C" int ecamd_ctx_synchronize(ecamd_ctx *c)
 // (the stream of the innermost scope on this thread: what ensure() orders the wipe of a growing scratch buffer behind)
 static thread_local hipStream_t t_scope_stream = nullptr;
 static thread_local bool t_scope_active = false;
-struct StreamScope {
-	ecamd_ctx *c;
-	hipStream_t s, outer;
-	bool outer_active;
-	StreamScope(ecamd_ctx *ctx, hipStream_t stream) : c(ctx), s(stream), outer(t_scope_stream), outer_active(t_scope_active)
-	{
-		if (c->inflight && c->last_stream != s) {
-			(void)hipStreamWaitEvent(s, c->busy, 0);
-		}
-		t_scope_stream = s;
-		t_scope_active = true;
+StreamScope::StreamScope(ecamd_ctx *ctx, hipStream_t stream) : c(ctx), s(stream), outer(t_scope_stream), outer_active(t_scope_active)
+{
+	if (c->inflight && c->last_stream != s) {
+		(void)hipStreamWaitEvent(s, c->busy, 0);
 	}
-	~StreamScope()
-	{
-		if (hipEventRecord(c->busy, s) == hipSuccess) {
-			c->last_stream = s;
-			c->inflight = true;
-		}
-		t_scope_stream = outer;
-		t_scope_active = outer_active;
+	t_scope_stream = s;
+	t_scope_active = true;
+}
+StreamScope::~StreamScope()
+{
+	if (hipEventRecord(c->busy, s) == hipSuccess) {
+		c->last_stream = s;
+		c->inflight = true;
 	}
-};
+	t_scope_stream = outer;
+	t_scope_active = outer_active;
+}
 
-// Scalars that are public by construction (u1, u2 of a verification, h and S of EdDSA, the group order and cofactor of a
-// subgroup check) keep the digit-indexed look-ups and the comb table even when the context is in secret-scalar mode
-// (ecamd_ctx_set_secret_scalars is about private keys, nonces and blinded scalars).  ctx->mu held.
-struct PublicScalars {
-	ecamd_ctx *c;
-	bool saved;
-	explicit PublicScalars(ecamd_ctx *ctx) : c(ctx), saved(ctx->secret_scalars) { c->secret_scalars = false; }
-	~PublicScalars() { c->secret_scalars = saved; }
-};
 
-static int ensure(uint8_t **buf, size_t *have, size_t need)
+int ecamd_host::ensure(uint8_t **buf, size_t *have, size_t need)
 {
 	if (*have >= need) {
 		return 0;
@@ -846,12 +628,7 @@ static int ensure(uint8_t **buf, size_t *have, size_t need)
 	return 0;
 }
 
-// Size slots of a frame by name (the StageSlot block above ecamd_ctx): ensured in the order given; 0 bytes asks for nothing.
-struct StageNeed {
-	StageSlot slot;
-	size_t bytes;
-};
-static int stage_need(ecamd_ctx *ctx, std::initializer_list<StageNeed> needs)
+int ecamd_host::stage_need(ecamd_ctx *ctx, std::initializer_list<StageNeed> needs)
 {
 	for (const StageNeed &k : needs) {
 		if (ensure(&ctx->stage[k.slot], &ctx->stage_bytes[k.slot], k.bytes)) {
@@ -860,7 +637,7 @@ static int stage_need(ecamd_ctx *ctx, std::initializer_list<StageNeed> needs)
 	}
 	return 0;
 }
-static int stage_need(ecamd_ctx *ctx, StageSlot slot, size_t bytes) { return stage_need(ctx, {{slot, bytes}}); }
+int ecamd_host::stage_need(ecamd_ctx *ctx, StageSlot slot, size_t bytes) { return stage_need(ctx, {{slot, bytes}}); }
 
 
 // ------------------------------------------------------------------------------------------
@@ -1001,13 +778,6 @@ static void release_modulus(int device, int nw, int slot)
 	}
 }
 
-static int smul_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_scalars, uint32_t slen,
-			   const uint8_t *d_points, uint8_t *d_out, uint8_t *d_status, hipStream_t s,
-			   uint32_t sstride = 0xffffffffu, bool redo_only = false, const uint8_t *d_scalars2 = nullptr);
-static int prep_scratch_ok(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n);
-#define SIG_ECDSA 1   /* libecc's ec_alg_type number of ECDSA: the `alg` of the verification paths when they serve ECDSA */
-static hipError_t launch_ecdsa_prep(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEcdsaPrepArgs &P, hipStream_t s, int alg = SIG_ECDSA,
-				    uint8_t *target = nullptr);
 
 // w-bit digits of a (nl of them, the last one takes whatever is left): 29 bits on every radix-2^29 unit but the Goldilocks one
 // (flavour 5), which runs on 28-bit limbs so that 2^224 falls on a limb boundary (ecamd_u29g.h)
@@ -1147,7 +917,7 @@ static int upload_g29(ecamd_curve *cv)
 
 // prj_pt_import_from_buf + prj_pt_unique of a batch: the handle's radix-2^29 unit when it has one (one inversion per eight triples),
 // else one Fermat inversion per triple on saturated words.  ECAMD_NO_PRJ_IMPORT_G29 keeps the latter (A/B hook).
-static hipError_t launch_prj_import(const ecamd_curve *cv, const EcamdPrjInArgs &I, hipStream_t s)
+hipError_t ecamd_host::launch_prj_import(const ecamd_curve *cv, const EcamdPrjInArgs &I, hipStream_t s)
 {
 	static const bool off = getenv("ECAMD_NO_PRJ_IMPORT_G29") != nullptr;
 	if (!off && cv->gslot >= 0) {
@@ -1254,6 +1024,16 @@ static int curve_finish(ecamd_ctx *ctx, ecamd_curve *cv, ecamd_curve **out)
 	}
 	cv->pbits = big_bitlen(cv->p);
 	cv->qbits = big_bitlen(cv->q);
+	{
+		// jmax = floor((p - 1) / q), tiny (1 for cofactor-1 curves with p > q, up to 8 for WEI25519)
+		uint32_t j = 0;
+		Big t = cv->q;
+		while (big_cmp(t, cv->p) < 0 && j < 64) {
+			t = big_add(t, cv->q);
+			j++;
+		}
+		cv->jmax = j;
+	}
 	cv->nw = pick_nw(cv->pbits);
 	if (!cv->nw || !ecamd_nw_supported(cv->nw)) {
 		return curve_abort(cv, "curve: field size not supported (max 544 bits)");
@@ -1652,7 +1432,7 @@ static void maybe_build_comb4(ecamd_ctx *ctx, ecamd_curve *cv)
 }
 
 // sstride = slen normally; 0 broadcasts one scalar to every item (subgroup / cofactor passes)
-static int smul_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_scalars,
+int ecamd_host::smul_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_scalars,
 			   uint32_t slen, const uint8_t *d_points, uint8_t *d_out, uint8_t *d_status,
 			   hipStream_t s, uint32_t sstride, bool redo_only, const uint8_t *d_scalars2)
 {
@@ -1775,18 +1555,6 @@ static int smul_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, co
 // their per-item strides (a NULL input is passed on as NULL); core(m, in_ptrs, out_ptrs, stream) enqueues one
 // chunk and may synchronise (after calling `between`).  ctx->mu held.
 // ------------------------------------------------------------------------------------------
-struct HostArr {
-	const uint8_t *in;   // input array (or NULL)
-	uint8_t *out;        // output array (or NULL)
-	size_t stride;       // bytes per item
-};
-
-// what host_pipeline hands its core for one chunk: the item count, the device copies of the caller's arrays (index = position in `arrs`;
-// NULL where the array is not an input / output), the stream, and `between` (see below)
-using DevIn = std::vector<const uint8_t *>;
-using DevOut = std::vector<uint8_t *>;
-using Between = std::function<int()>;
-using HostCore = std::function<int(uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &between)>;
 
 template <class Core>
 static int host_pipeline(ecamd_ctx *ctx, int pbits, uint32_t n, const std::vector<HostArr> &arrs, Core core, uint32_t even_chunk = 0)
@@ -1918,22 +1686,8 @@ static int host_pipeline(ecamd_ctx *ctx, int pbits, uint32_t n, const std::vecto
 	return 0;
 }
 
-// ------------------------------------------------------------------------------------------
-// The head of an entry point, after its own argument checks and the n == 0 return.  Device pointers: the lock, the device, the
-// caller's stream or the context's, the StreamScope, then body(s).  Host pointers: the lock, the device, host_pipeline.
-// Entry points that take the lock earlier (a setup step under it), drop it in between or open no scope keep their own head.
-// ------------------------------------------------------------------------------------------
-template <class Body>
-static int dev_call(ecamd_ctx *ctx, void *hip_stream, Body body)
-{
-	std::lock_guard<std::mutex> lk(ctx->mu);
-	HIPCHK(hipSetDevice(ctx->device));
-	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
-	StreamScope scope(ctx, s);
-	return body(s);
-}
 
-static int host_call(ecamd_ctx *ctx, int pbits, uint32_t n, const std::vector<HostArr> &arrs, const HostCore &core)
+int ecamd_host::host_call(ecamd_ctx *ctx, int pbits, uint32_t n, const std::vector<HostArr> &arrs, const HostCore &core)
 {
 	std::lock_guard<std::mutex> lk(ctx->mu);
 	HIPCHK(hipSetDevice(ctx->device));
@@ -2332,16 +2086,50 @@ static int two_mul_sum_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, co
 	return 0;
 }
 // the verifications: a public key, W' into ST_W / ST_STW
-static int verify_sum_need(ecamd_ctx *ctx, const ecamd_curve *cv, size_t chunk)
+int ecamd_host::verify_sum_need(ecamd_ctx *ctx, const ecamd_curve *cv, size_t chunk)
 {
 	const size_t plen = (size_t)2 * cv->clen;
 	return two_mul_need(ctx, cv, chunk) || stage_need(ctx, {{ST_SUB, chunk}, {ST_QY, chunk * plen + 256}, {ST_W, chunk * plen},
 							       {ST_WSINK, chunk * plen}, {ST_STW, chunk}, {ST_STWSINK, chunk}});
 }
-static int verify_sum_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, const uint8_t *d_Y, hipStream_t s)
+int ecamd_host::verify_sum_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, const uint8_t *d_Y, hipStream_t s)
 {
 	uint8_t **S = ctx->stage;
 	return two_mul_sum_dev(ctx, cv, m, d_Y, true, S[ST_FLAGS], S[ST_W], S[ST_WSINK], S[ST_STW], S[ST_STWSINK], s);
+}
+
+// The mod-q algebra in front of a verification: on the dense radix-2^29 unit of the order's size when the handle has q in a slot
+// there (round 4: k_ecdsa_prep_g, sixteen items per inversion from 320 bits on, eight below), else on the saturated words.
+// The caller has sized ctx->prep_scratch (prep_scratch_ok).
+static bool prep_g29(const ecamd_curve *cv)
+{
+	return cv->gqslot >= 0 && getenv("ECAMD_NO_PREP_G29") == nullptr;
+}
+static int prep_scratch_ok(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n)
+{
+	if (!prep_g29(cv)) {
+		return 0;
+	}
+	return ensure(&ctx->prep_scratch, &ctx->prep_scratch_bytes, (size_t)n * (size_t)ecamd_g29_nl(big_bitlen(cv->q), 0) * 4);
+}
+// alg != SIG_ECDSA: the front end of ECGDSA / ECRDSA / SM2 (k_sig_prep, saturated words), which also writes the comparison target
+static hipError_t launch_ecdsa_prep(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEcdsaPrepArgs &P, hipStream_t s, int alg = SIG_ECDSA,
+				    uint8_t *target = nullptr)
+{
+	if (alg != SIG_ECDSA) {
+		EcamdSigPrepArgs SP;
+		SP.p = P;
+		SP.target = target;
+		SP.alg = alg;
+		return ecamd_launch_sig_prep(cv->qnw, SP, s);
+	}
+	if (prep_g29(cv) && ctx->prep_scratch) {
+		const int qbits = big_bitlen(cv->q);
+		static const int kp_env = getenv("ECAMD_PREP_KP") ? atoi(getenv("ECAMD_PREP_KP")) : 0;   // A/B hook
+		const int kp = (kp_env >= 1 && kp_env <= 64) ? kp_env : (qbits > 320 ? 16 : 8);
+		return ecamd_g29_ecdsa_prep(qbits, cv->gqslot, P, (uint32_t *)ctx->prep_scratch, kp, s);
+	}
+	return ecamd_launch_ecdsa_prep(cv->qnw, P, s);
 }
 
 // ECDSA the reference's way: two independent scalar multiplications and one addition per item (k_ecdsa_fin: x mod q == r over the
@@ -2402,16 +2190,7 @@ static int ecdsa_two_smul_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n,
 	Fn.n = n;
 	Fn.clen = (uint32_t)cv->clen;
 	Fn.qlen = (uint32_t)cv->qlen;
-	{
-		// jmax = floor((p - 1) / q), tiny (1 for cofactor-1 curves with p > q, up to 8 for WEI25519)
-		uint32_t j = 0;
-		Big t = cv->q;
-		while (big_cmp(t, cv->p) < 0 && j < 64) {
-			t = big_add(t, cv->q);
-			j++;
-		}
-		Fn.jmax = j;
-	}
+	Fn.jmax = cv->jmax;
 	for (int w = 0; w < 17; w++) {
 		Fn.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
 	}
@@ -2419,39 +2198,6 @@ static int ecdsa_two_smul_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n,
 	Fn.only = d_only;
 	HIPCHK(ecamd_launch_ecdsa_fin(cv->nw, Fn, s));
 	return 0;
-}
-
-// The mod-q algebra in front of a verification: on the dense radix-2^29 unit of the order's size when the handle has q in a slot
-// there (round 4: k_ecdsa_prep_g, sixteen items per inversion from 320 bits on, eight below), else on the saturated words.
-// The caller has sized ctx->prep_scratch (prep_scratch_ok).
-static bool prep_g29(const ecamd_curve *cv)
-{
-	return cv->gqslot >= 0 && getenv("ECAMD_NO_PREP_G29") == nullptr;
-}
-static int prep_scratch_ok(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n)
-{
-	if (!prep_g29(cv)) {
-		return 0;
-	}
-	return ensure(&ctx->prep_scratch, &ctx->prep_scratch_bytes, (size_t)n * (size_t)ecamd_g29_nl(big_bitlen(cv->q), 0) * 4);
-}
-// alg != SIG_ECDSA: the front end of ECGDSA / ECRDSA / SM2 (k_sig_prep, saturated words), which also writes the comparison target
-static hipError_t launch_ecdsa_prep(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEcdsaPrepArgs &P, hipStream_t s, int alg, uint8_t *target)
-{
-	if (alg != SIG_ECDSA) {
-		EcamdSigPrepArgs SP;
-		SP.p = P;
-		SP.target = target;
-		SP.alg = alg;
-		return ecamd_launch_sig_prep(cv->qnw, SP, s);
-	}
-	if (prep_g29(cv) && ctx->prep_scratch) {
-		const int qbits = big_bitlen(cv->q);
-		static const int kp_env = getenv("ECAMD_PREP_KP") ? atoi(getenv("ECAMD_PREP_KP")) : 0;   // A/B hook
-		const int kp = (kp_env >= 1 && kp_env <= 64) ? kp_env : (qbits > 320 ? 16 : 8);
-		return ecamd_g29_ecdsa_prep(qbits, cv->gqslot, P, (uint32_t *)ctx->prep_scratch, kp, s);
-	}
-	return ecamd_launch_ecdsa_prep(cv->qnw, P, s);
 }
 
 // k_ecdsa_prep of a chunk on the side stream: it starts when everything enqueued on s so far is done (the stage buffers it
@@ -2518,14 +2264,6 @@ static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 		return -1;
 	}
 	uint8_t **S = ctx->stage;
-	uint32_t jmax = 0;
-	{
-		Big t = cv->q;
-		while (big_cmp(t, cv->p) < 0 && jmax < 64) {
-			t = big_add(t, cv->q);
-			jmax++;
-		}
-	}
 	for (uint32_t off = 0; off < n; off += chunk) {
 		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
 		EcamdEcdsaPrepArgs P;
@@ -2561,7 +2299,7 @@ static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 		Fn.n = m;
 		Fn.clen = (uint32_t)cv->clen;
 		Fn.qlen = (uint32_t)cv->qlen;
-		Fn.jmax = jmax;
+		Fn.jmax = cv->jmax;
 		for (int w = 0; w < 17; w++) {
 			Fn.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
 		}
@@ -2573,9 +2311,9 @@ static int ecdsa_fused_g_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, 
 	return ecdsa_two_smul_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s, d_res, alg);
 }
 
-static int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_pub,
+int ecamd_host::ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_pub,
 				   const uint8_t *d_sig, const uint8_t *d_dig, uint32_t hlen, uint8_t *d_res, hipStream_t s,
-				   const Between *between = nullptr, int alg = SIG_ECDSA)
+				   const Between *between, int alg)
 {
 	if (!cv->is_p256 || !cv->d_gtab) {
 		if (fused_verify_ok(ctx, cv, n) ? ecdsa_fused_g_dev(ctx, cv, n, d_pub, d_sig, d_dig, hlen, d_res, s, alg)
@@ -2904,15 +2642,7 @@ static int ecdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t
 	A.qlen = (uint32_t)cv->qlen;
 	A.hlen = hlen;
 	A.qbits = (uint32_t)cv->qbits;
-	{
-		uint32_t j = 0;
-		Big t = cv->q;
-		while (big_cmp(t, cv->p) < 0 && j < 64) {
-			t = big_add(t, cv->q);
-			j++;
-		}
-		A.jmax = j;
-	}
+	A.jmax = cv->jmax;
 	A.qslot = cv->qslot;
 	HIPCHK(ecamd_launch_ecdsa_sign(cv->qnw, A, s));
 	return 0;
@@ -2971,7 +2701,7 @@ extern "C" int ec_ecdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32
 // batched ECGDSA / ECRDSA / SM2 (include/libecc_amd.h: ec_sig_*): the ECDSA verification paths with the scheme's front end
 // (k_sig_prep) and the ECDSA signing path with the scheme's back end (k_sig_sign)
 // ------------------------------------------------------------------------------------------
-static int sig_alg_ok(const char *fn, int alg)
+int ecamd_host::sig_alg_ok(const char *fn, int alg)
 {
 	if (alg != ECAMD_SIG_ECGDSA && alg != ECAMD_SIG_ECRDSA && alg != ECAMD_SIG_SM2) {
 		return fail(std::string(fn) + ": alg must be ECAMD_SIG_ECGDSA, ECAMD_SIG_ECRDSA or ECAMD_SIG_SM2");
@@ -3012,7 +2742,7 @@ extern "C" int ec_sig_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int al
 }
 
 // Device core of signing: every pointer a device pointer; [k]G and its status live in SG_KG, SG_STKG as for ECDSA.
-static int sig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
+int ecamd_host::sig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
 			       const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
 {
 	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen;
@@ -3046,15 +2776,7 @@ static int sig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, u
 	A.a.qlen = (uint32_t)cv->qlen;
 	A.a.hlen = hlen;
 	A.a.qbits = (uint32_t)cv->qbits;
-	{
-		uint32_t j = 0;
-		Big t = cv->q;
-		while (big_cmp(t, cv->p) < 0 && j < 64) {
-			t = big_add(t, cv->q);
-			j++;
-		}
-		A.a.jmax = j;
-	}
+	A.a.jmax = cv->jmax;
 	A.a.qslot = cv->qslot;
 	A.alg = alg;
 	HIPCHK(ecamd_launch_sig_sign(cv->qnw, A, s));
@@ -4549,7 +4271,38 @@ extern "C" int ec_eddsa_verify_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv_i
 }
 
 static int eddsa_sign_setup(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const void *a, const void *b,
-			    const void *c, EcamdEdSignArgs *T);
+			    const void *c, EcamdEdSignArgs *T)
+{
+	if (!ctx || !cv_in || cv_in->ctx != ctx || (n && (!a || !b || !c))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	ecamd_curve *cv = const_cast<ecamd_curve *>(cv_in);
+	memset(T, 0, sizeof(*T));
+	if (cv->pbits == 448) {
+		if (cv->ed448_state == 0) {
+			ed448_setup(cv);
+		}
+		if (cv->ed448_state < 0) {
+			return fail(std::string(fn) + ": Ed448 signing needs the WEI448 curve handle");
+		}
+		memcpy(T->alpha, cv->ed448_tmpl.alpha, sizeof(T->alpha));
+		memcpy(T->A3, cv->ed448_tmpl.A3, sizeof(T->A3));
+		big_store(T->c4, 17, big_from_be(cv->ed448_c4, 56));
+		T->is448 = 1;
+	} else {
+		if (cv->ed_state == 0) {
+			ed_setup(cv);
+		}
+		if (cv->ed_state < 0) {
+			return fail(std::string(fn) + ": EdDSA signing needs the WEI25519 or the WEI448 curve handle");
+		}
+		memcpy(T->alpha, cv->ed_tmpl.alpha, sizeof(T->alpha));
+		memcpy(T->A3, cv->ed_tmpl.A3, sizeof(T->A3));
+	}
+	T->slot = cv->slot;
+	T->qslot = cv->qslot;
+	return 0;
+}
 // The same from the PROJECTIVE key an ec_pub_key holds (X || Y || Z on WEI25519): what a verifier that starts from libecc structures
 // needs -- the reference hashes the key's Ed25519 ENCODING (eddsa_export_pub_key, sig/eddsa.c:795: Weierstrass -> Edwards -> octets), which
 // ec_eddsa_encode_point_batch computes; here that encoding goes straight into the item's hash input on the device (bytes a_offset ..
@@ -5869,17 +5622,6 @@ extern "C" int ecamd_debug_schnorr_msm(ecamd_ctx *ctx, const ecamd_curve *cv, ui
 
 static int eddsa_verify_all_batch_dev_impl(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const void *d_pubkeys,
 					     const void *d_sigs, const void *d_hram, uint32_t hram_len, void *d_verdict,
-					     void *hip_stream);
-extern "C" int ec_eddsa_verify_all_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const void *d_pubkeys,
-					     const void *d_sigs, const void *d_hram, uint32_t hram_len, void *d_verdict,
-					     void *hip_stream)
-{
-	const int r = eddsa_verify_all_batch_dev_impl(ctx, cv_in, n, d_pubkeys, d_sigs, d_hram, hram_len, d_verdict, hip_stream);
-	msm_seed_discard(ctx);
-	return r;
-}
-static int eddsa_verify_all_batch_dev_impl(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const void *d_pubkeys,
-					     const void *d_sigs, const void *d_hram, uint32_t hram_len, void *d_verdict,
 					     void *hip_stream)
 {
 	if (!ctx) {
@@ -5919,6 +5661,14 @@ static int eddsa_verify_all_batch_dev_impl(ecamd_ctx *ctx, const ecamd_curve *cv
 	}
 	return 0;
 }
+extern "C" int ec_eddsa_verify_all_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const void *d_pubkeys,
+					     const void *d_sigs, const void *d_hram, uint32_t hram_len, void *d_verdict,
+					     void *hip_stream)
+{
+	const int r = eddsa_verify_all_batch_dev_impl(ctx, cv_in, n, d_pubkeys, d_sigs, d_hram, hram_len, d_verdict, hip_stream);
+	msm_seed_discard(ctx);
+	return r;
+}
 
 // test hook: the combination with a caller-chosen seed; z_out (n x 16 little-endian z_i) and sum_out (36 words: X, Y, Z, T of
 // the sum before the cofactor, radix-2^29 digits of lazily reduced residues) may be NULL.  n <= the context's max_chunk.
@@ -5946,17 +5696,6 @@ extern "C" int ecamd_debug_eddsa_msm(ecamd_ctx *ctx, const ecamd_curve *cv_in, u
 // batch when one random linear combination of the cofactored equations vanishes, which holds when every signature verifies
 // and fails otherwise except with probability ~2^-128 over its random z_i.  Here every item is verified (the batch is the
 // parallel dimension already), so the bit is the exact conjunction and the first rejected index comes for free.
-static int eddsa_verify_all_batch_impl(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *pubkeys,
-				       const uint8_t *sigs, const uint8_t *hram, uint32_t hram_len, int *all_valid,
-				       uint32_t *first_rejected);
-extern "C" int ec_eddsa_verify_all_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *pubkeys,
-					 const uint8_t *sigs, const uint8_t *hram, uint32_t hram_len, int *all_valid,
-					 uint32_t *first_rejected)
-{
-	const int r = eddsa_verify_all_batch_impl(ctx, cv, n, pubkeys, sigs, hram, hram_len, all_valid, first_rejected);
-	msm_seed_discard(ctx);
-	return r;
-}
 static int eddsa_verify_all_batch_impl(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *pubkeys,
 				       const uint8_t *sigs, const uint8_t *hram, uint32_t hram_len, int *all_valid,
 				       uint32_t *first_rejected)
@@ -6026,43 +5765,18 @@ static int eddsa_verify_all_batch_impl(ecamd_ctx *ctx, const ecamd_curve *cv, ui
 	}
 	return 0;
 }
+extern "C" int ec_eddsa_verify_all_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *pubkeys,
+					 const uint8_t *sigs, const uint8_t *hram, uint32_t hram_len, int *all_valid,
+					 uint32_t *first_rejected)
+{
+	const int r = eddsa_verify_all_batch_impl(ctx, cv, n, pubkeys, sigs, hram, hram_len, all_valid, first_rejected);
+	msm_seed_discard(ctx);
+	return r;
+}
 
 // ------------------------------------------------------------------------------------------
 // Ed25519 signing: the two device-side steps of _eddsa_sign (sig/eddsa.c:1554-1870) around the caller's hashes
 // ------------------------------------------------------------------------------------------
-static int eddsa_sign_setup(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const void *a, const void *b,
-			    const void *c, EcamdEdSignArgs *T)
-{
-	if (!ctx || !cv_in || cv_in->ctx != ctx || (n && (!a || !b || !c))) {
-		return fail(std::string(fn) + ": bad argument");
-	}
-	ecamd_curve *cv = const_cast<ecamd_curve *>(cv_in);
-	memset(T, 0, sizeof(*T));
-	if (cv->pbits == 448) {
-		if (cv->ed448_state == 0) {
-			ed448_setup(cv);
-		}
-		if (cv->ed448_state < 0) {
-			return fail(std::string(fn) + ": Ed448 signing needs the WEI448 curve handle");
-		}
-		memcpy(T->alpha, cv->ed448_tmpl.alpha, sizeof(T->alpha));
-		memcpy(T->A3, cv->ed448_tmpl.A3, sizeof(T->A3));
-		big_store(T->c4, 17, big_from_be(cv->ed448_c4, 56));
-		T->is448 = 1;
-	} else {
-		if (cv->ed_state == 0) {
-			ed_setup(cv);
-		}
-		if (cv->ed_state < 0) {
-			return fail(std::string(fn) + ": EdDSA signing needs the WEI25519 or the WEI448 curve handle");
-		}
-		memcpy(T->alpha, cv->ed_tmpl.alpha, sizeof(T->alpha));
-		memcpy(T->A3, cv->ed_tmpl.A3, sizeof(T->A3));
-	}
-	T->slot = cv->slot;
-	T->qslot = cv->qslot;
-	return 0;
-}
 
 // SR_: r big-endian, [r]G and its status
 static int eddsa_sign_R_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEdSignArgs &T, uint32_t n,
@@ -6786,1411 +6500,6 @@ extern "C" int ec_ecdsa_recover_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uin
 					   {nullptr, pub2_aff, plen}, {nullptr, status1, 1}, {nullptr, status2, 1}};
 	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return ecdsa_recover_dev_locked(ctx, cv, m, ip[0], ip[1], hlen, op[2], op[3], op[4], op[5], s);
-	});
-}
-
-// ------------------------------------------------------------------------------------------
-// batched ECSDSA / ECOSDSA / ECKCDSA (include/libecc_amd.h: ec_sig_hashed_*): the schemes that hash the commitment.  Per chunk of
-// at most max_chunk items, verification is
-//   k_hsig_prep       s in [1, q - 1], e from r, the multipliers u (of G) and v (of Y), the flag byte
-//   A = [u]G, B = [v]Y one fixed-base and one variable-base pass; on a cofactor curve [q]Y too, as ECDSA verification does
-//   k_recover_fin     W' = A + B as affine bytes, one shared inversion per eight items (its second sum A - B is not used)
-//   k_recover_redo    the items with A or B at infinity or x_A = x_B, on the complete formulas
-//   k_hsig_fill       W' into the blank of a copy of the caller's slots, or ECKCDSA's slot of FE2OS(W'x)
-//   k_sha2_slots      the digest
-//   k_hsig_cmp        the digest against r
-// and signing is [k]G (secret-scalar mode as the context says), k_hsig_fill, k_sha2_slots, k_hsig_sign.
-// Frames: ST_ with ST_SLOTS and ST_DIGESTS; signing SG_.  Only enqueues.
-// ------------------------------------------------------------------------------------------
-static uint32_t hsig_staged_stride(const ecamd_curve *cv, int alg, uint32_t stride)
-{
-	return alg == ECAMD_SIG_ECKCDSA ? (uint32_t)((4 + cv->clen + 3) & ~3) : stride;
-}
-
-// a stride that cannot hold the length word and the blank: no slot is usable, every item is rejected
-static bool hsig_no_room(const ecamd_curve *cv, int alg, uint32_t stride)
-{
-	return alg != ECAMD_SIG_ECKCDSA && stride < 4u + (uint32_t)echsig::blank_len(alg, cv->clen);
-}
-
-static int hsig_stage_hash(ecamd_ctx *ctx, int hash_type, uint32_t m, EcamdHsigArgs &H, const uint8_t *d_in, uint32_t stride,
-			   hipStream_t s)
-{
-	uint8_t **S = ctx->stage;
-	if (H.alg != ECAMD_SIG_ECKCDSA) {
-		// the caller's array is not modified: the coordinates go into a copy
-		HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
-	}
-	H.slots = S[ST_SLOTS];
-	H.dg = S[ST_DIGESTS];
-	HIPCHK(ecamd_launch_hsig_fill(H, s));
-	HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], H.sstride, m, S[ST_DIGESTS], H.hsize, s));
-	return 0;
-}
-
-static int hsig_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_pub,
-				  const uint8_t *d_sig, const uint8_t *d_in, uint32_t stride, uint8_t *d_res, hipStream_t s)
-{
-	PublicScalars pub_scope(ctx);   // u, v and the group order are public
-	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
-	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
-	if (hsig_no_room(cv, alg, stride)) {
-		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
-		return 0;
-	}
-	const size_t siglen = (size_t)echsig::r_len(alg, (int)hsize, (int)ql) + ql;
-	const uint32_t sstride = hsig_staged_stride(cv, alg, stride);
-	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (verify_sum_need(ctx, cv, chunk) || stage_need(ctx, {{ST_SLOTS, (size_t)chunk * sstride}, {ST_DIGESTS, (size_t)chunk * hsize}})) {
-		return -1;
-	}
-	uint8_t **S = ctx->stage;
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		const uint8_t *pub = d_pub + (size_t)off * plen, *in = d_in + (size_t)off * stride;
-		EcamdHsigArgs H;
-		memset(&H, 0, sizeof(H));
-		H.sigs = d_sig + (size_t)off * siglen;
-		H.inputs = in;
-		H.u = S[ST_U];
-		H.v = S[ST_V];
-		H.flags = S[ST_FLAGS];
-		H.W = S[ST_W];
-		H.stW = S[ST_STW];
-		H.out = d_res + off;
-		H.n = m;
-		H.qlen = (uint32_t)ql;
-		H.clen = (uint32_t)cl;
-		H.hsize = hsize;
-		H.sstride = sstride;
-		H.qslot = cv->qslot;
-		H.alg = alg;
-		HIPCHK(ecamd_launch_hsig_prep(cv->qnw, H, s));
-		if (verify_sum_dev(ctx, cv, m, pub, s) || hsig_stage_hash(ctx, hash_type, m, H, in, stride, s)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_hsig_cmp(H, s));
-	}
-	return 0;
-}
-
-static int hsig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_privs,
-				const uint8_t *d_nonces, const uint8_t *d_in, uint32_t stride, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
-{
-	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
-	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
-	const size_t siglen = (size_t)echsig::r_len(alg, (int)hsize, (int)ql) + ql;
-	const uint32_t sstride = hsig_staged_stride(cv, alg, stride);
-	if (hsig_no_room(cv, alg, stride)) {
-		HIPCHK(hipMemsetAsync(d_sigs, 0, n * siglen, s));
-		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
-		return 0;
-	}
-	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (stage_need(ctx, SG_KG, chunk * plen) || stage_need(ctx, SG_STKG, chunk) ||
-	    stage_need(ctx, ST_FLAGS, chunk) || stage_need(ctx, ST_SLOTS, (size_t)chunk * sstride) ||
-	    stage_need(ctx, ST_DIGESTS, (size_t)chunk * hsize)) {
-		return -1;
-	}
-	uint8_t **S = ctx->stage;
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		const uint8_t *in = d_in + (size_t)off * stride;
-		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {   // W = [k]G
-			return -1;
-		}
-		EcamdHsigArgs H;
-		memset(&H, 0, sizeof(H));
-		H.inputs = in;
-		H.privs = d_privs + off * ql;
-		H.nonces = d_nonces + off * ql;
-		H.flags = S[ST_FLAGS];
-		H.W = S[SG_KG];
-		H.stW = S[SG_STKG];
-		H.out = d_sigs + (size_t)off * siglen;
-		H.status = d_status + off;
-		H.n = m;
-		H.qlen = (uint32_t)ql;
-		H.clen = (uint32_t)cl;
-		H.hsize = hsize;
-		H.sstride = sstride;
-		H.qslot = cv->qslot;
-		H.alg = alg;
-		H.sign = 1;
-		if (hsig_stage_hash(ctx, hash_type, m, H, in, stride, s)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_hsig_sign(cv->qnw, H, s));
-	}
-	return 0;
-}
-
-static int hsig_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a, const void *b,
-			const void *c, const void *d, const void *e, uint32_t stride)
-{
-	if (!echsig::alg_known(alg)) {
-		return fail(std::string(fn) + ": alg must be ECAMD_SIG_ECKCDSA, ECAMD_SIG_ECSDSA or ECAMD_SIG_ECOSDSA");
-	}
-	if (echsig::hash_size(hash_type) == 0) {
-		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224, SHA-256, SHA-384, SHA-512)");
-	}
-	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
-		return fail(std::string(fn) + ": bad argument");
-	}
-	if (cv->qslot < 0) {
-		return fail(std::string(fn) + ": generator order not supported for this curve");
-	}
-	if (alg == ECAMD_SIG_ECKCDSA) {
-		if (stride != (uint32_t)echsig::hash_size(hash_type)) {
-			return fail(std::string(fn) + ": ECKCDSA takes digests h = H(z || m): stride must be the hash's digest size");
-		}
-	} else if ((stride & 3u) || stride > 4096 || stride < 4) {
-		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
-	}
-	return 0;
-}
-
-extern "C" int ec_sig_hashed_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
-					      const void *d_sigs, const void *d_inputs, uint32_t stride, void *d_result, void *hip_stream)
-{
-	if (hsig_args_ok("ec_sig_hashed_verify_batch_dev", ctx, cv, alg, hash_type, n, d_pubkeys, d_sigs, d_inputs, d_result, d_result, stride)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return hsig_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_inputs, stride,
-					      (uint8_t *)d_result, s);
-	});
-}
-
-extern "C" int ec_sig_hashed_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
-					  const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, uint8_t *result)
-{
-	if (hsig_args_ok("ec_sig_hashed_verify_batch", ctx, cv, alg, hash_type, n, pubkeys, sigs, inputs, result, result, stride)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	const size_t siglen = (size_t)echsig::r_len(alg, echsig::hash_size(hash_type), cv->qlen) + cv->qlen;
-	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, siglen}, {inputs, nullptr, stride}, {nullptr, result, 1}};
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return hsig_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], s);
-	});
-}
-
-extern "C" int ec_sig_hashed_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
-					    const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs, void *d_status, void *hip_stream)
-{
-	if (hsig_args_ok("ec_sig_hashed_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_inputs, d_sigs, d_status, stride)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return hsig_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_inputs, stride,
-					    (uint8_t *)d_sigs, (uint8_t *)d_status, s);
-	});
-}
-
-extern "C" int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
-					const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, uint8_t *sigs, uint8_t *status)
-{
-	if (hsig_args_ok("ec_sig_hashed_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, inputs, sigs, status, stride)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	const size_t ql = (size_t)cv->qlen;
-	const size_t siglen = (size_t)echsig::r_len(alg, echsig::hash_size(hash_type), cv->qlen) + ql;
-	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {inputs, nullptr, stride}, {nullptr, sigs, siglen}, {nullptr, status, 1}};
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return hsig_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], op[4], s);
-	});
-}
-
-// ------------------------------------------------------------------------------------------
-// batched BIGN / DBIGN (include/libecc_amd.h: ec_bign_*): the scheme that hashes its commitment with belt-hash.  Per chunk of at
-// most max_chunk items, verification is
-//   k_sha2_slots / k_belt_slots   hash_type != 0 only: the digests of the caller's message slots
-//   k_bign_prep       s1 < q, hbar, the multipliers u (of G) and v (of Y), the flag byte
-//   A = [u]G, B = [v]Y one fixed-base and one variable-base pass (public scalars); on a cofactor curve [q]Y too, as ECDSA verification does
-//   k_recover_fin     W' = A + B as affine bytes, one shared inversion per eight items (its second sum A - B is not used)
-//   k_recover_redo    the items with A or B at infinity (u = 0) or x_A = x_B, on the complete formulas
-//   k_bign_fill       belt-hash's slot OID || <LE(W'x) || LE(W'y)>_2l || digest
-//   k_belt_slots      t
-//   k_bign_cmp        t against s0
-// and signing is [k]G (secret-scalar mode as the context says), k_bign_fill, k_belt_slots, k_bign_sign.
-// Frames: ST_ with ST_SLOTS (belt-hash's slots), ST_DIGESTS (the digests of the messages) and ST_BELT; signing SG_.  Only enqueues.
-// ------------------------------------------------------------------------------------------
-static int bign_message_digests(ecamd_ctx *ctx, int hash_type, uint32_t m, const uint8_t *d_in, uint32_t stride, EcamdBignArgs &B, hipStream_t s)
-{
-	if (hash_type == 0) {
-		B.dg = d_in;          // the caller hashed: stride is the digest length
-		B.mslots = nullptr;
-		return 0;
-	}
-	uint8_t **S = ctx->stage;
-	if (hash_type == ecbign::HASH_BELT) {
-		HIPCHK(ecamd_launch_belt_slots(d_in, stride, m, S[ST_DIGESTS], B.hsize, s));
-	} else {
-		HIPCHK(ecamd_launch_sha2_slots(hash_type, d_in, stride, m, S[ST_DIGESTS], B.hsize, s));
-	}
-	B.dg = S[ST_DIGESTS];
-	B.mslots = d_in;
-	B.mstride = stride;
-	return 0;
-}
-
-static void bign_args(EcamdBignArgs &B, const ecamd_curve *cv, int hash_type, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint32_t m)
-{
-	memset(&B, 0, sizeof(B));
-	B.n = m;
-	B.qlen = (uint32_t)cv->qlen;
-	B.clen = (uint32_t)cv->clen;
-	B.hsize = hash_type == 0 ? stride : (uint32_t)ecbign::hash_size(hash_type);
-	B.oid_len = oid_len;
-	B.bstride = ecbign::belt_stride(oid_len, cv->qlen, B.hsize);
-	B.qslot = cv->qslot;
-	if (oid_len) {
-		memcpy(B.oid, oid, oid_len);
-	}
-}
-
-static int bign_stage_belt(ecamd_ctx *ctx, EcamdBignArgs &B, hipStream_t s)
-{
-	uint8_t **S = ctx->stage;
-	B.slots = S[ST_SLOTS];
-	B.bt = S[ST_BELT];
-	HIPCHK(ecamd_launch_bign_fill(B, s));
-	HIPCHK(ecamd_launch_belt_slots(S[ST_SLOTS], B.bstride, B.n, S[ST_BELT], ecbign::DIGEST_BT, s));
-	return 0;
-}
-
-static int bign_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_pub, const uint8_t *d_sig,
-				  const uint8_t *d_in, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *d_res, hipStream_t s)
-{
-	PublicScalars pub_scope(ctx);   // u, v and the group order are public
-	const size_t cl = (size_t)cv->clen, plen = 2 * cl, siglen = (size_t)ecbign::sig_len(cv->qlen);
-	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	EcamdBignArgs B;
-	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
-	if (verify_sum_need(ctx, cv, chunk) ||
-	    stage_need(ctx, {{ST_SLOTS, (size_t)chunk * B.bstride}, {ST_DIGESTS, hash_type ? (size_t)chunk * B.hsize : 0},
-			     {ST_BELT, (size_t)chunk * ecbign::DIGEST_BT}})) {
-		return -1;
-	}
-	uint8_t **S = ctx->stage;
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		const uint8_t *pub = d_pub + (size_t)off * plen;
-		B.n = m;
-		B.sigs = d_sig + (size_t)off * siglen;
-		B.u = S[ST_U];
-		B.v = S[ST_V];
-		B.flags = S[ST_FLAGS];
-		B.W = S[ST_W];
-		B.stW = S[ST_STW];
-		B.out = d_res + off;
-		if (bign_message_digests(ctx, hash_type, m, d_in + (size_t)off * stride, stride, B, s)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_bign_prep(cv->qnw, B, s));
-		if (verify_sum_dev(ctx, cv, m, pub, s) || bign_stage_belt(ctx, B, s)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_bign_cmp(B, s));
-	}
-	return 0;
-}
-
-static int bign_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
-				const uint8_t *d_in, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *d_sigs, uint8_t *d_status,
-				hipStream_t s)
-{
-	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen, siglen = (size_t)ecbign::sig_len(cv->qlen);
-	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	EcamdBignArgs B;
-	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
-	if (stage_need(ctx, SG_KG, chunk * plen) || stage_need(ctx, SG_STKG, chunk) ||
-	    stage_need(ctx, ST_SLOTS, (size_t)chunk * B.bstride) ||
-	    stage_need(ctx, ST_DIGESTS, hash_type ? (size_t)chunk * B.hsize : 0) ||
-	    stage_need(ctx, ST_BELT, (size_t)chunk * ecbign::DIGEST_BT)) {
-		return -1;
-	}
-	uint8_t **S = ctx->stage;
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {   // W = [k]G
-			return -1;
-		}
-		B.n = m;
-		B.privs = d_privs + off * ql;
-		B.nonces = d_nonces + off * ql;
-		B.W = S[SG_KG];
-		B.stW = S[SG_STKG];
-		B.out = d_sigs + (size_t)off * siglen;
-		B.status = d_status + off;
-		B.sign = 1;
-		if (bign_message_digests(ctx, hash_type, m, d_in + (size_t)off * stride, stride, B, s) || bign_stage_belt(ctx, B, s)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_bign_sign(cv->qnw, B, s));
-	}
-	return 0;
-}
-
-static int bign_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a, const void *b,
-			const void *c, const void *d, const void *e, uint32_t stride, const uint8_t *oid, uint32_t oid_len)
-{
-	if (!ecbign::alg_known(alg)) {
-		return fail(std::string(fn) + ": alg must be ECAMD_SIG_BIGN or ECAMD_SIG_DBIGN");
-	}
-	if (hash_type != 0 && ecbign::hash_size(hash_type) == 0) {
-		return fail(std::string(fn) + ": hash_type must be 0 (inputs are digests), 1 .. 4 (SHA-224 / 256 / 384 / 512) or ECAMD_HASH_BELT");
-	}
-	if (oid_len > (uint32_t)ecbign::MAX_OID || (oid_len && !oid)) {
-		return fail(std::string(fn) + ": oid_len must be 0 .. 64, and oid non-NULL when it is not 0");
-	}
-	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
-		return fail(std::string(fn) + ": bad argument");
-	}
-	if (cv->qslot < 0) {
-		return fail(std::string(fn) + ": generator order not supported for this curve");
-	}
-	if (hash_type == 0) {
-		if (stride < 1 || stride > (uint32_t)ecbign::MAX_DIGEST) {
-			return fail(std::string(fn) + ": hash_type 0 takes digests: stride must be the digest length, 1 .. 128");
-		}
-	} else if ((stride & 3u) || stride > 4096 || stride < 4) {
-		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
-	}
-	return 0;
-}
-
-extern "C" int ec_bign_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
-					const void *d_sigs, const void *d_inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, void *d_result,
-					void *hip_stream)
-{
-	if (bign_args_ok("ec_bign_verify_batch_dev", ctx, cv, alg, hash_type, n, d_pubkeys, d_sigs, d_inputs, d_result, d_result, stride, oid, oid_len)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return bign_verify_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_inputs, stride, oid,
-					      oid_len, (uint8_t *)d_result, s);
-	});
-}
-
-extern "C" int ec_bign_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
-				    const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *result)
-{
-	if (bign_args_ok("ec_bign_verify_batch", ctx, cv, alg, hash_type, n, pubkeys, sigs, inputs, result, result, stride, oid, oid_len)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, (size_t)ecbign::sig_len(cv->qlen)},
-					   {inputs, nullptr, stride}, {nullptr, result, 1}};
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return bign_verify_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], ip[2], stride, oid, oid_len, op[3], s);
-	});
-}
-
-extern "C" int ec_bign_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
-				      const void *d_nonces, const void *d_inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, void *d_sigs,
-				      void *d_status, void *hip_stream)
-{
-	if (bign_args_ok("ec_bign_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_inputs, d_sigs, d_status, stride, oid, oid_len)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return bign_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_inputs, stride, oid,
-					    oid_len, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
-	});
-}
-
-extern "C" int ec_bign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
-				  const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *sigs,
-				  uint8_t *status)
-{
-	if (bign_args_ok("ec_bign_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, inputs, sigs, status, stride, oid, oid_len)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	const size_t ql = (size_t)cv->qlen;
-	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {inputs, nullptr, stride},
-					   {nullptr, sigs, (size_t)ecbign::sig_len(cv->qlen)}, {nullptr, status, 1}};
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return bign_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], ip[2], stride, oid, oid_len, op[3], op[4], s);
-	});
-}
-
-// ------------------------------------------------------------------------------------------
-// BIP0340 / ECFSDSA item by item (include/libecc_amd.h: ec_schnorr_verify_batch, ec_schnorr_sign_batch): the two schemes whose
-// signature carries the commitment as a point.  Per chunk of at most max_chunk items, verification is
-//   k_prj_import           projective keys only: prj_pt_import_from_buf + prj_pt_unique (affine keys are validated by the multiplication)
-//   k_schnorr_item_prep    key status and ranges, r < p (W.x, W.y < p), s in range, the slot's length; the flag byte, the key as
-//                          the equation uses it, s; the copy of the caller's slots patched with the signature's r (W) and the key's x
-//   k_ptf (op 2)           ECFSDSA: W on the curve
-//   k_sha2_slots, k_schnorr_ne   e = H(slot) mod q, then q - e
-//   A = [s]G, B = [q - e]Y one fixed-base and one variable-base pass; on a cofactor curve [q]Y too, as ECDSA verification does
-//   k_recover_fin / _redo  W' = A + B as affine bytes, one shared inversion per eight items; the exceptional pairs on the complete formulas
-//   k_schnorr_item_cmp     BIP0340: finite, y even, x = r; ECFSDSA: finite, x || y = r
-// and signing is [k]G (secret-scalar mode as the context says), BIP0340: Y = [x]G (the same) or the caller's key through k_ptf (op 2),
-// k_schnorr_item_fill, k_sha2_slots, k_schnorr_item_sign.
-// Frames: ST_ (ST_U holds s, ST_V q - e) with ST_SLOTS, ST_DIGESTS and SI_; signing SG_.  Only enqueues.
-// ------------------------------------------------------------------------------------------
-static bool schnorr_item_no_room(const ecamd_curve *cv, int alg, uint32_t hsize, uint32_t stride)
-{
-	return stride < 4u + (uint32_t)ecschnorr::fixed_len(alg, (int)hsize, cv->clen);
-}
-
-static void schnorr_item_args(EcamdSchnorrItemArgs &H, const ecamd_curve *cv, int alg, uint32_t hsize, uint32_t stride, uint32_t m)
-{
-	memset(&H, 0, sizeof(H));
-	H.n = m;
-	H.qlen = (uint32_t)cv->qlen;
-	H.clen = (uint32_t)cv->clen;
-	H.hsize = hsize;
-	H.sstride = stride;
-	H.qslot = cv->qslot;
-	H.alg = alg;
-	big_to_be(H.p_be, cv->clen, cv->p);
-}
-
-static int schnorr_item_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_keys,
-					  int key_fmt, const uint8_t *d_sig, const uint8_t *d_in, uint32_t stride, uint8_t *d_res, hipStream_t s)
-{
-	PublicScalars pub_scope(ctx);   // s, q - e and the group order are public
-	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
-	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
-	if (schnorr_item_no_room(cv, alg, hsize, stride)) {
-		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
-		return 0;
-	}
-	const bool fs = alg == ECAMD_SIG_ECFSDSA, prj = key_fmt == ECAMD_PT_PROJECTIVE;
-	const size_t siglen = (size_t)ecschnorr::r_len(alg, (int)cl) + ql, kw = (prj ? 3 : 2) * cl;
-	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (verify_sum_need(ctx, cv, chunk) ||
-	    stage_need(ctx, {{ST_SLOTS, (size_t)chunk * stride}, {ST_DIGESTS, (size_t)chunk * hsize}, {SI_KEY, chunk * plen},
-			     {SI_PRJ_AFF, prj ? chunk * plen : 0}, {SI_PRJ_ST, prj ? chunk : 0}, {SI_WPT, fs ? chunk * plen : 0}, {SI_WST, fs ? chunk : 0}})) {
-		return -1;
-	}
-	uint8_t **S = ctx->stage;
-	EcamdSchnorrNeArgs N;
-	memset(&N, 0, sizeof(N));
-	for (int w = 0; w < 18; w++) {
-		N.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
-	}
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		const uint8_t *keys = d_keys + (size_t)off * kw, *kst = nullptr;
-		if (prj) {
-			EcamdPrjInArgs I;
-			I.in = keys;
-			I.aff = S[SI_PRJ_AFF];
-			I.pre = S[SI_PRJ_ST];
-			I.n = m;
-			I.clen = (uint32_t)cl;
-			I.for_mul = fs ? 1 : 0;   // (0 : 0 : 0): ECFSDSA multiplies the key as it is, BIP0340 takes its unique representative
-			I.slot = cv->slot;
-			HIPCHK(launch_prj_import(cv, I, s));
-			keys = S[SI_PRJ_AFF];
-			kst = S[SI_PRJ_ST];
-		}
-		// the caller's array is not modified: the patches go into a copy
-		HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
-		EcamdSchnorrItemArgs H;
-		schnorr_item_args(H, cv, alg, hsize, stride, m);
-		H.keys = keys;
-		H.kst = kst;
-		H.gen = cv->d_gen;
-		H.sigs = d_sig + (size_t)off * siglen;
-		H.slots = S[ST_SLOTS];
-		H.key_out = S[SI_KEY];
-		H.s_out = S[ST_U];
-		H.w_out = fs ? S[SI_WPT] : nullptr;
-		H.flags = S[ST_FLAGS];
-		H.wst = fs ? S[SI_WST] : nullptr;
-		H.A = S[ST_A];
-		H.stA = S[ST_STA];
-		H.W = S[ST_W];
-		H.stW = S[ST_STW];
-		H.out = d_res + off;
-		HIPCHK(ecamd_launch_schnorr_item_prep(cv->qnw, H, s));
-		if (fs) {
-			// "Reject the signature if r is not a valid point on the curve" (ecfsdsa.c:449-460): the on-curve test the point calls use
-			EcamdPtfArgs T;
-			memset(&T, 0, sizeof(T));
-			T.p1 = S[SI_WPT];
-			T.p2 = S[SI_WPT];
-			T.out = S[SI_WPT];   // untouched by op 2
-			T.status = S[SI_WST];
-			T.n = m;
-			T.clen = (uint32_t)cl;
-			T.op = 2;
-			T.slot = cv->slot;
-			HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
-		}
-		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], stride, m, S[ST_DIGESTS], hsize, s));
-		N.dig = S[ST_DIGESTS];
-		N.ne = S[ST_V];
-		N.n = m;
-		N.hlen = hsize;
-		N.qlen = (uint32_t)ql;
-		HIPCHK(ecamd_launch_schnorr_ne(cv->qnw, N, s));
-		// k_recover_fin takes ANY non-zero flag as "no sum for this item": that holds for flag 2 too (ECFSDSA, the key at infinity),
-		// whose verdict k_schnorr_item_cmp reads from A = [s]G and stA, not from W'
-		if (verify_sum_dev(ctx, cv, m, S[SI_KEY], s)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_schnorr_item_cmp(H, s));
-	}
-	return 0;
-}
-
-static int schnorr_item_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_privs,
-					const uint8_t *d_pubs, const uint8_t *d_nonces, const uint8_t *d_in, uint32_t stride, uint8_t *d_sigs,
-					uint8_t *d_status, hipStream_t s)
-{
-	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
-	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
-	const size_t siglen = (size_t)ecschnorr::r_len(alg, (int)cl) + ql;
-	if (schnorr_item_no_room(cv, alg, hsize, stride)) {
-		HIPCHK(hipMemsetAsync(d_sigs, 0, n * siglen, s));
-		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
-		return 0;
-	}
-	const bool bip = alg == ECAMD_SIG_BIP0340;
-	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (stage_need(ctx, SG_KG, chunk * plen) || stage_need(ctx, SG_STKG, chunk) ||
-	    stage_need(ctx, ST_FLAGS, chunk) || stage_need(ctx, ST_SLOTS, (size_t)chunk * stride) ||
-	    stage_need(ctx, ST_DIGESTS, (size_t)chunk * hsize) ||
-	    (bip && (stage_need(ctx, SG_Y, chunk * plen) || stage_need(ctx, SG_STY, chunk)))) {
-		return -1;
-	}
-	uint8_t **S = ctx->stage;
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {   // R = [k]G
-			return -1;
-		}
-		EcamdSchnorrItemArgs H;
-		schnorr_item_args(H, cv, alg, hsize, stride, m);
-		if (bip && d_pubs) {
-			// the key pair's public half as the caller holds it: coordinates < p and on the curve
-			EcamdPtfArgs T;
-			memset(&T, 0, sizeof(T));
-			T.p1 = d_pubs + off * plen;
-			T.p2 = T.p1;
-			T.out = S[SG_Y];   // untouched by op 2
-			T.status = S[SG_STY];
-			T.n = m;
-			T.clen = (uint32_t)cl;
-			T.op = 2;
-			T.slot = cv->slot;
-			HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
-			H.keys = d_pubs + off * plen;
-		} else if (bip) {
-			if (smul_dev_locked(ctx, cv, m, d_privs + off * ql, (uint32_t)ql, nullptr, S[SG_Y], S[SG_STY], s)) {   // Y = [x]G
-				return -1;
-			}
-			H.keys = S[SG_Y];
-		}
-		H.kst = bip ? S[SG_STY] : nullptr;
-		H.privs = d_privs + off * ql;
-		H.nonces = d_nonces + off * ql;
-		H.slots = S[ST_SLOTS];
-		H.flags = S[ST_FLAGS];
-		H.W = S[SG_KG];
-		H.stW = S[SG_STKG];
-		H.dg = S[ST_DIGESTS];
-		H.out = d_sigs + (size_t)off * siglen;
-		H.status = d_status + off;
-		HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
-		HIPCHK(ecamd_launch_schnorr_item_fill(H, s));
-		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], stride, m, S[ST_DIGESTS], hsize, s));
-		HIPCHK(ecamd_launch_schnorr_item_sign(cv->qnw, H, s));
-	}
-	return 0;
-}
-
-static int schnorr_item_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a,
-				const void *b, const void *c, const void *d, const void *e, uint32_t stride)
-{
-	if (!ecschnorr::alg_known(alg)) {
-		return fail(std::string(fn) + ": alg must be ECAMD_SIG_BIP0340 or ECAMD_SIG_ECFSDSA");
-	}
-	if (echsig::hash_size(hash_type) == 0) {
-		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224, SHA-256, SHA-384, SHA-512)");
-	}
-	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
-		return fail(std::string(fn) + ": bad argument");
-	}
-	if (cv->qslot < 0) {
-		return fail(std::string(fn) + ": generator order not supported for this curve");
-	}
-	if ((stride & 3u) || stride > 4096 || stride < 4) {
-		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
-	}
-	return 0;
-}
-
-static int schnorr_item_fmt_ok(const char *fn, int key_fmt)
-{
-	if (key_fmt != ECAMD_PT_AFFINE && key_fmt != ECAMD_PT_PROJECTIVE) {
-		return fail(std::string(fn) + ": key_fmt must be ECAMD_PT_AFFINE or ECAMD_PT_PROJECTIVE");
-	}
-	return 0;
-}
-
-extern "C" int ec_schnorr_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_keys,
-					   int key_fmt, const void *d_sigs, const void *d_hash_slots, uint32_t stride, void *d_result,
-					   void *hip_stream)
-{
-	if (schnorr_item_args_ok("ec_schnorr_verify_batch_dev", ctx, cv, alg, hash_type, n, d_keys, d_sigs, d_hash_slots, d_result, d_result, stride) ||
-	    schnorr_item_fmt_ok("ec_schnorr_verify_batch_dev", key_fmt)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return schnorr_item_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_keys, key_fmt, (const uint8_t *)d_sigs,
-						      (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_result, s);
-	});
-}
-
-extern "C" int ec_schnorr_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *keys, int key_fmt,
-				       const uint8_t *sigs, const uint8_t *hash_slots, uint32_t stride, uint8_t *result)
-{
-	if (schnorr_item_args_ok("ec_schnorr_verify_batch", ctx, cv, alg, hash_type, n, keys, sigs, hash_slots, result, result, stride) ||
-	    schnorr_item_fmt_ok("ec_schnorr_verify_batch", key_fmt)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	const size_t cl = (size_t)cv->clen, siglen = (size_t)ecschnorr::r_len(alg, cv->clen) + cv->qlen;
-	const std::vector<HostArr> arrs = {{keys, nullptr, (key_fmt == ECAMD_PT_PROJECTIVE ? 3 : 2) * cl}, {sigs, nullptr, siglen},
-					   {hash_slots, nullptr, stride}, {nullptr, result, 1}};
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return schnorr_item_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], key_fmt, ip[1], ip[2], stride, op[3], s);
-	});
-}
-
-extern "C" int ec_schnorr_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
-					 const void *d_pubkeys_aff, const void *d_nonces, const void *d_hash_slots, uint32_t stride, void *d_sigs,
-					 void *d_status, void *hip_stream)
-{
-	if (schnorr_item_args_ok("ec_schnorr_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_hash_slots, d_sigs, d_status, stride)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return schnorr_item_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff,
-						    (const uint8_t *)d_nonces, (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
-	});
-}
-
-extern "C" int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
-				     const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
-				     uint8_t *status)
-{
-	if (schnorr_item_args_ok("ec_schnorr_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, hash_slots, sigs, status, stride)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	const size_t ql = (size_t)cv->qlen, plen = (size_t)2 * cv->clen;
-	const size_t siglen = (size_t)ecschnorr::r_len(alg, cv->clen) + ql;
-	const bool with_pub = alg == ECAMD_SIG_BIP0340 && pubkeys_aff != nullptr;   // ECFSDSA ignores it
-	std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {hash_slots, nullptr, stride}, {nullptr, sigs, siglen},
-				     {nullptr, status, 1}};
-	if (with_pub) {
-		arrs.push_back({pubkeys_aff, nullptr, plen});
-	}
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return schnorr_item_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], with_pub ? ip[5] : nullptr, ip[1], ip[2], stride, op[3], op[4], s);
-	});
-}
-
-// ------------------------------------------------------------------------------------------
-// DBIGN and BIP0340 with the nonce derived ON THE DEVICE (include/libecc_amd.h: ec_dbign_nonce_batch, ec_dbign_sign_batch,
-// ec_bip0340_nonce_batch, ec_bip0340_sign_batch): the two generators of ecamd_detnonce.hip in front of the signing cores above.
-// Per chunk of at most max_chunk items
-//   DBIGN    k_sha2_slots / k_belt_slots (hash_type != 0), k_dbign_nonce into SG_NONCES (the table scanned in secret-scalar mode),
-//            bign_sign_dev_locked on the chunk (it hashes the chunk's messages again for its own frame: a compression or two per item)
-//   BIP0340  Y = [x]G into SG_Y (or the on-curve test of the caller's keys), k_bip0340_nonce into SG_NONCES,
-//            schnorr_item_sign_dev_locked on the chunk with Y as its supplied key (so [x]G is computed once)
-// Every slot the cores size is sized here first, for the whole chunk, so no buffer moves between the generator and the core.
-// SG_NONCES is secret: ensure() wipes what it frees, ecamd_ctx_wipe_scratch the rest.  Only enqueues.
-// ------------------------------------------------------------------------------------------
-static const uint32_t h_sha256_k[64] = {ECAMD_SHA256_K};
-static const uint64_t h_sha512_k[80] = {ECAMD_SHA512_K};
-
-static int det_order_ok(const char *fn, const ecamd_curve *cv)
-{
-	if (cv->qslot < 0 || big_bitlen(cv->q) < 2 || cv->q.size() > 17 || cv->qlen > ecrfc::MAX_QLEN ||
-	    (uint32_t)cv->qlen != ((uint32_t)cv->qbits + 7) / 8 || cv->clen > ecbip::MAX_CLEN) {
-		return fail(std::string(fn) + ": generator order not supported for this curve");
-	}
-	return 0;
-}
-
-static int dbign_nonce_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_privs, const uint8_t *d_digests, uint32_t hlen,
-				  const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *d_nonces, uint8_t *d_status,
-				  hipStream_t s)
-{
-	EcamdDbignNonceArgs D;
-	memset(&D, 0, sizeof(D));
-	D.privs = d_privs;
-	D.digests = d_digests;
-	D.nonces = d_nonces;
-	D.status = d_status;
-	D.n = n;
-	D.qlen = (uint32_t)cv->qlen;
-	D.qbits = (uint32_t)cv->qbits;
-	D.hlen = hlen;
-	D.oid_len = oid_len;
-	D.t_len = t_len;
-	D.scan = ctx->secret_scalars ? 1 : 0;
-	for (int w = 0; w < 17; w++) {
-		D.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
-	}
-	if (oid_len) {
-		memcpy(D.oid, oid, oid_len);
-	}
-	if (t_len) {
-		memcpy(D.t, t, t_len);
-	}
-	HIPCHK(ecamd_launch_dbign_nonce(D, s));
-	return 0;
-}
-
-static int dbign_common_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, const uint8_t *oid, uint32_t oid_len, const uint8_t *t,
-			   uint32_t t_len)
-{
-	if (oid_len > (uint32_t)ecdbign::MAX_OID || (oid_len && !oid)) {
-		return fail(std::string(fn) + ": oid_len must be 0 .. 64, and oid non-NULL when it is not 0");
-	}
-	if (t_len > (uint32_t)ecdbign::MAX_T || (t_len && !t)) {
-		return fail(std::string(fn) + ": t_len must be 0 .. 64, and t non-NULL when it is not 0");
-	}
-	if (!ctx || !cv || cv->ctx != ctx) {
-		return fail(std::string(fn) + ": bad argument");
-	}
-	return det_order_ok(fn, cv);
-}
-
-static int dbign_nonce_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const void *a, const void *b, uint32_t digest_len,
-			       const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, const void *c, const void *d)
-{
-	if (digest_len < 1 || digest_len > (uint32_t)ecdbign::MAX_DIGEST) {
-		return fail(std::string(fn) + ": digest_len must be 1 .. 128");
-	}
-	if (dbign_common_ok(fn, ctx, cv, oid, oid_len, t, t_len)) {
-		return -1;
-	}
-	if (n && (!a || !b || !c || !d)) {
-		return fail(std::string(fn) + ": bad argument");
-	}
-	return 0;
-}
-
-extern "C" int ec_dbign_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const void *d_privs, const void *d_digests,
-					uint32_t digest_len, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, void *d_nonces,
-					void *d_status, void *hip_stream)
-{
-	if (dbign_nonce_args_ok("ec_dbign_nonce_batch_dev", ctx, cv, n, d_privs, d_digests, digest_len, oid, oid_len, t, t_len, d_nonces, d_status)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return dbign_nonce_dev_locked(ctx, cv, n, (const uint8_t *)d_privs, (const uint8_t *)d_digests, digest_len, oid, oid_len, t, t_len,
-					      (uint8_t *)d_nonces, (uint8_t *)d_status, s);
-	});
-}
-
-extern "C" int ec_dbign_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *privs, const uint8_t *digests,
-				    uint32_t digest_len, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *nonces,
-				    uint8_t *status)
-{
-	if (dbign_nonce_args_ok("ec_dbign_nonce_batch", ctx, cv, n, privs, digests, digest_len, oid, oid_len, t, t_len, nonces, status)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	const size_t ql = (size_t)cv->qlen;
-	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {digests, nullptr, digest_len}, {nullptr, nonces, ql}, {nullptr, status, 1}};
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return dbign_nonce_dev_locked(ctx, cv, m, ip[0], ip[1], digest_len, oid, oid_len, t, t_len, op[2], op[3], s);
-	});
-}
-
-static int dbign_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_in,
-				 uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *d_sigs,
-				 uint8_t *d_status, hipStream_t s)
-{
-	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen, siglen = (size_t)ecbign::sig_len(cv->qlen);
-	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	EcamdBignArgs B;
-	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
-	if (stage_need(ctx, {{SG_NONCES, (size_t)chunk * ql}, {SG_KG, chunk * plen}, {SG_STKG, chunk}, {ST_SLOTS, (size_t)chunk * B.bstride},
-			     {ST_DIGESTS, hash_type ? (size_t)chunk * B.hsize : 0}, {ST_BELT, (size_t)chunk * ecbign::DIGEST_BT}})) {
-		return -1;
-	}
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		const uint8_t *in = d_in + (size_t)off * stride;
-		B.n = m;
-		if (bign_message_digests(ctx, hash_type, m, in, stride, B, s)) {
-			return -1;
-		}
-		// (the generator's status lands in the caller's status bytes and is replaced by the signing core's: a zero nonce is status 1 there)
-		if (dbign_nonce_dev_locked(ctx, cv, m, d_privs + off * ql, B.dg, B.hsize, oid, oid_len, t, t_len, ctx->stage[SG_NONCES], d_status + off, s) ||
-		    bign_sign_dev_locked(ctx, cv, hash_type, m, d_privs + off * ql, ctx->stage[SG_NONCES], in, stride, oid, oid_len,
-					 d_sigs + (size_t)off * siglen, d_status + off, s)) {
-			return -1;
-		}
-	}
-	return 0;
-}
-
-static int dbign_sign_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *a, const void *b,
-			      uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, const void *c, const void *d)
-{
-	if (bign_args_ok(fn, ctx, cv, ECAMD_SIG_DBIGN, hash_type, n, a, b, b, c, d, stride, oid, oid_len)) {
-		return -1;
-	}
-	return dbign_common_ok(fn, ctx, cv, oid, oid_len, t, t_len);
-}
-
-extern "C" int ec_dbign_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs, const void *d_inputs,
-				       uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, void *d_sigs,
-				       void *d_status, void *hip_stream)
-{
-	if (dbign_sign_args_ok("ec_dbign_sign_batch_dev", ctx, cv, hash_type, n, d_privs, d_inputs, stride, oid, oid_len, t, t_len, d_sigs, d_status)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return dbign_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_inputs, stride, oid, oid_len, t, t_len,
-					     (uint8_t *)d_sigs, (uint8_t *)d_status, s);
-	});
-}
-
-extern "C" int ec_dbign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *inputs,
-				   uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *sigs,
-				   uint8_t *status)
-{
-	if (dbign_sign_args_ok("ec_dbign_sign_batch", ctx, cv, hash_type, n, privs, inputs, stride, oid, oid_len, t, t_len, sigs, status)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	const size_t ql = (size_t)cv->qlen;
-	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {inputs, nullptr, stride}, {nullptr, sigs, (size_t)ecbign::sig_len(cv->qlen)},
-					   {nullptr, status, 1}};
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return dbign_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], stride, oid, oid_len, t, t_len, op[2], op[3], s);
-	});
-}
-
-// the two tag hashes of the call's hash, as its words
-template <int ALG, typename KT> static void bip0340_tags_of(EcamdBip0340NonceArgs &N, KT Kt)
-{
-	typename ecrfc::Alg<ALG>::W w[8];
-	ecbip::tag_hash<ALG>("BIP0340/aux", 11, w, Kt);
-	for (int t = 0; t < 8; t++) {
-		N.tag_aux[t] = (uint64_t)w[t];
-	}
-	ecbip::tag_hash<ALG>("BIP0340/nonce", 13, w, Kt);
-	for (int t = 0; t < 8; t++) {
-		N.tag_nonce[t] = (uint64_t)w[t];
-	}
-}
-
-static void bip0340_nonce_args(EcamdBip0340NonceArgs &N, const ecamd_curve *cv, int hash_type, uint32_t stride)
-{
-	memset(&N, 0, sizeof(N));
-	N.qlen = (uint32_t)cv->qlen;
-	N.qbits = (uint32_t)cv->qbits;
-	N.clen = (uint32_t)cv->clen;
-	N.stride = stride;
-	for (int w = 0; w < 17; w++) {
-		N.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
-	}
-	switch (hash_type) {
-	case 1: bip0340_tags_of<224>(N, h_sha256_k); break;
-	case 2: bip0340_tags_of<256>(N, h_sha256_k); break;
-	case 3: bip0340_tags_of<384>(N, h_sha512_k); break;
-	default: bip0340_tags_of<512>(N, h_sha512_k); break;
-	}
-}
-
-// Y of one chunk: [x]G into SG_Y, or the caller's keys with their on-curve test; either way SG_STY holds the status.  *keys: where Y lies.
-static int bip0340_keys_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, const uint8_t *d_privs, const uint8_t *d_pubs, const uint8_t **keys,
-			    hipStream_t s)
-{
-	uint8_t **S = ctx->stage;
-	if (d_pubs) {
-		EcamdPtfArgs T;
-		memset(&T, 0, sizeof(T));
-		T.p1 = d_pubs;
-		T.p2 = d_pubs;
-		T.out = S[SG_Y];   // untouched by op 2
-		T.status = S[SG_STY];
-		T.n = m;
-		T.clen = (uint32_t)cv->clen;
-		T.op = 2;
-		T.slot = cv->slot;
-		HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
-		*keys = d_pubs;
-		return 0;
-	}
-	*keys = S[SG_Y];
-	return smul_dev_locked(ctx, cv, m, d_privs, (uint32_t)cv->qlen, nullptr, S[SG_Y], S[SG_STY], s);
-}
-
-// sign = false: the nonces go to d_out (n x qlen); true: into SG_NONCES, and the signatures (n x (clen + qlen)) to d_out
-static int bip0340_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_pubs,
-			      const uint8_t *d_aux, const uint8_t *d_in, uint32_t stride, uint8_t *d_out, uint8_t *d_status, bool sign, hipStream_t s)
-{
-	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen, siglen = cl + ql;
-	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
-	if (sign && schnorr_item_no_room(cv, ECAMD_SIG_BIP0340, hsize, stride)) {
-		HIPCHK(hipMemsetAsync(d_out, 0, n * siglen, s));
-		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
-		return 0;
-	}
-	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (stage_need(ctx, {{SG_Y, chunk * plen}, {SG_STY, chunk}}) ||
-	    (sign && stage_need(ctx, {{SG_NONCES, (size_t)chunk * ql}, {SG_KG, chunk * plen}, {SG_STKG, chunk}, {ST_FLAGS, chunk},
-				      {ST_SLOTS, (size_t)chunk * stride}, {ST_DIGESTS, (size_t)chunk * hsize}}))) {
-		return -1;
-	}
-	EcamdBip0340NonceArgs N;
-	bip0340_nonce_args(N, cv, hash_type, stride);
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		const uint8_t *in = d_in + (size_t)off * stride;
-		if (bip0340_keys_dev(ctx, cv, m, d_privs + off * ql, d_pubs ? d_pubs + off * plen : nullptr, &N.keys, s)) {
-			return -1;
-		}
-		N.n = m;
-		N.privs = d_privs + off * ql;
-		N.kst = ctx->stage[SG_STY];
-		N.aux = d_aux + off * ql;
-		N.slots = in;
-		N.nonces = sign ? ctx->stage[SG_NONCES] : d_out + off * ql;
-		N.status = d_status + off;   // signing: replaced by the core's, where a zero nonce is status 1
-		HIPCHK(ecamd_launch_bip0340_nonce(hash_type, N, s));
-		// the core takes Y as a supplied key ([x]G is computed once): derived here, it fails the core's on-curve test only as the point at infinity
-		if (sign && schnorr_item_sign_dev_locked(ctx, cv, ECAMD_SIG_BIP0340, hash_type, m, N.privs, N.keys, N.nonces, in, stride,
-							 d_out + (size_t)off * siglen, d_status + off, s)) {
-			return -1;
-		}
-	}
-	return 0;
-}
-
-static int bip0340_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *privs, const void *aux,
-			   const void *slots, const void *out, const void *status, uint32_t stride)
-{
-	if (schnorr_item_args_ok(fn, ctx, cv, ECAMD_SIG_BIP0340, hash_type, n, privs, aux, slots, out, status, stride)) {
-		return -1;
-	}
-	return det_order_ok(fn, cv);
-}
-
-extern "C" int ec_bip0340_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
-					  const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_nonces,
-					  void *d_status, void *hip_stream)
-{
-	if (bip0340_args_ok("ec_bip0340_nonce_batch_dev", ctx, cv, hash_type, n, d_privs, d_aux, d_hash_slots, d_nonces, d_status, stride)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return bip0340_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff, (const uint8_t *)d_aux,
-					  (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_nonces, (uint8_t *)d_status, false, s);
-	});
-}
-
-extern "C" int ec_bip0340_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
-					 const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_sigs,
-					 void *d_status, void *hip_stream)
-{
-	if (bip0340_args_ok("ec_bip0340_sign_batch_dev", ctx, cv, hash_type, n, d_privs, d_aux, d_hash_slots, d_sigs, d_status, stride)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return bip0340_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff, (const uint8_t *)d_aux,
-					  (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_sigs, (uint8_t *)d_status, true, s);
-	});
-}
-
-static int bip0340_host(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *pubkeys_aff,
-			const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *out, size_t outlen, uint8_t *status, bool sign)
-{
-	const size_t ql = (size_t)cv->qlen, plen = (size_t)2 * cv->clen;
-	std::vector<HostArr> arrs = {{privs, nullptr, ql}, {aux, nullptr, ql}, {hash_slots, nullptr, stride}, {nullptr, out, outlen}, {nullptr, status, 1}};
-	if (pubkeys_aff) {
-		arrs.push_back({pubkeys_aff, nullptr, plen});
-	}
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return bip0340_dev_locked(ctx, cv, hash_type, m, ip[0], pubkeys_aff ? ip[5] : nullptr, ip[1], ip[2], stride, op[3], op[4], sign, s);
-	});
-}
-
-extern "C" int ec_bip0340_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
-				      const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *nonces,
-				      uint8_t *status)
-{
-	if (bip0340_args_ok("ec_bip0340_nonce_batch", ctx, cv, hash_type, n, privs, aux, hash_slots, nonces, status, stride)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return bip0340_host(ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, nonces, (size_t)cv->qlen, status, false);
-}
-
-extern "C" int ec_bip0340_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
-				     const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
-				     uint8_t *status)
-{
-	if (bip0340_args_ok("ec_bip0340_sign_batch", ctx, cv, hash_type, n, privs, aux, hash_slots, sigs, status, stride)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return bip0340_host(ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, sigs, (size_t)cv->clen + cv->qlen, status, true);
-}
-
-// ------------------------------------------------------------------------------------------
-// ECGDSA / ECRDSA / SM2 from messages (include/libecc_amd.h: ec_sig_verify_msg_batch, ec_sig_sign_msg_batch, ec_hash_slots_batch): the
-// hashes of ecamd_hash.hip / ecamd_hash2.hip in front of the digest-level cores ecdsa_verify_dev_locked(.., alg) / sig_sign_dev_locked,
-// which run unchanged.  Per chunk of at most max_chunk items:
-//   (signing, SM2)     Y: the caller's keys through the on-curve test, or [x]G (bip0340_keys_dev: SG_Y, SG_STY)
-//   k_sig_msg_bad      SM_BAD: the slot does not fit its stride, is shorter than SM2's blank, or the key did not import
-//   (SM2) k_sm2_z      Z from the prefix midstate into SM_Z; a copy of the slots in ST_SLOTS; k_slot_patch puts Z into the blank
-//   k_*_slots          the digests into ST_DIGESTS
-//   the core           verdicts / signatures and status as for the digest-level call
-//   k_reject_where / k_sig_msg_reject_sign   SM_BAD's items: result 1 / status 1 with zero bytes
-// Frames: SM_ with ST_SLOTS and ST_DIGESTS around the core's own (ST_ / VP_ / SG_).  Only enqueues.
-// ------------------------------------------------------------------------------------------
-static int sig_msg_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t stride, const uint8_t *id,
-			   uint32_t id_len)
-{
-	if (sig_alg_ok(fn, alg)) {
-		return -1;
-	}
-	if (ecamd_hash_digest_len(hash_type) == 0) {
-		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224 / 256 / 384 / 512), 11 (SM3), 13 or 14 (Streebog-256 / -512)");
-	}
-	if (stride < 4 || (stride & 3u) || stride > 4096) {
-		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
-	}
-	if (!ctx || !cv || cv->ctx != ctx) {
-		return fail(std::string(fn) + ": bad argument");
-	}
-	if (cv->qslot < 0) {
-		return fail(std::string(fn) + ": generator order not supported for this curve");
-	}
-	if (alg == ECAMD_SIG_SM2) {
-		if (ecsm2z::hash_size(hash_type) == 0) {
-			return fail(std::string(fn) + ": SM2's Z is computed with SM3 or SHA-2 (hash_type 11 or 1 .. 4)");
-		}
-		if (id_len > (uint32_t)ecsm2z::MAX_ID) {
-			return fail(std::string(fn) + ": id_len must be at most 1024");
-		}
-		if (id_len && !id) {
-			return fail(std::string(fn) + ": id is NULL with a positive id_len");
-		}
-		if (cv->clen > ecsm2z::MAX_CLEN) {
-			return fail(std::string(fn) + ": field not supported");
-		}
-	}
-	return 0;
-}
-
-// the prefix of the call's Z (SM2 only; otherwise left alone)
-static int sig_msg_prefix(const ecamd_curve *cv, int alg, int hash_type, const uint8_t *id, uint32_t id_len, ecsm2z::Prefix &P)
-{
-	if (alg != ECAMD_SIG_SM2) {
-		return 0;
-	}
-	uint8_t a[ecsm2z::MAX_CLEN], b[ecsm2z::MAX_CLEN], gx[ecsm2z::MAX_CLEN], gy[ecsm2z::MAX_CLEN];
-	big_to_be(a, cv->clen, cv->a);
-	big_to_be(b, cv->clen, cv->b);
-	big_to_be(gx, cv->clen, cv->gx);
-	big_to_be(gy, cv->clen, cv->gy);
-	if (ecsm2z::prefix_init(P, hash_type, id, id_len, a, b, gx, gy, (uint32_t)cv->clen, h_sha256_k, h_sha512_k)) {
-		return fail("internal: Z prefix");
-	}
-	return 0;
-}
-
-// SM2: Z of the chunk's keys into the blank of a staged copy of its slots; *hin: the slots to hash
-static int sig_msg_stage_z(ecamd_ctx *ctx, const ecsm2z::Prefix &P, uint32_t m, const uint8_t *d_keys, uint32_t plen, const uint8_t *d_in,
-			   uint32_t stride, uint32_t hl, const uint8_t **hin, hipStream_t s)
-{
-	uint8_t **S = ctx->stage;
-	HIPCHK(ecamd_launch_sm2_z(P, d_keys, plen, S[SM_Z], hl, m, s));
-	HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in, (size_t)m * stride, hipMemcpyDeviceToDevice, s));   // the caller's array is not modified
-	HIPCHK(ecamd_launch_slot_patch(S[ST_SLOTS], stride, 0, S[SM_Z], hl, S[SM_BAD], m, s));
-	*hin = S[ST_SLOTS];
-	return 0;
-}
-
-static int sig_msg_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_pub,
-				     const uint8_t *d_sig, const uint8_t *d_in, uint32_t stride, const ecsm2z::Prefix &P, uint8_t *d_res, hipStream_t s,
-				     const Between *between = nullptr)
-{
-	const size_t plen = (size_t)2 * cv->clen, sl = (size_t)2 * cv->qlen;
-	const uint32_t hl = (uint32_t)ecamd_hash_digest_len(hash_type), blank = alg == ECAMD_SIG_SM2 ? hl : 0u;
-	const bool sm2 = alg == ECAMD_SIG_SM2;
-	if (stride < 4u + blank) {   // no slot can hold the blank: every item is rejected
-		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
-		return 0;
-	}
-	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (stage_need(ctx, {{ST_DIGESTS, (size_t)chunk * hl}, {SM_BAD, chunk}, {ST_SLOTS, sm2 ? (size_t)chunk * stride : 0}, {SM_Z, sm2 ? (size_t)chunk * hl : 0}})) {
-		return -1;
-	}
-	uint8_t **S = ctx->stage;
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		const uint8_t *pub = d_pub + (size_t)off * plen, *in = d_in + (size_t)off * stride, *hin = in;
-		HIPCHK(ecamd_launch_sig_msg_bad(in, stride, blank, nullptr, S[SM_BAD], m, s));
-		if (sm2 && sig_msg_stage_z(ctx, P, m, pub, (uint32_t)plen, in, stride, hl, &hin, s)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_hash_slots(hash_type, hin, stride, m, S[ST_DIGESTS], hl, s));
-		if (ecdsa_verify_dev_locked(ctx, cv, m, pub, d_sig + (size_t)off * sl, S[ST_DIGESTS], hl, d_res + off, s,
-					    off + m == n ? between : nullptr, alg)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_reject_where(d_res + off, S[SM_BAD], m, s));
-	}
-	return 0;
-}
-
-static int sig_msg_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_privs,
-				   const uint8_t *d_pubs, const uint8_t *d_nonces, const uint8_t *d_in, uint32_t stride, const ecsm2z::Prefix &P,
-				   uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
-{
-	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen, sl = 2 * ql;
-	const uint32_t hl = (uint32_t)ecamd_hash_digest_len(hash_type), blank = alg == ECAMD_SIG_SM2 ? hl : 0u;
-	const bool sm2 = alg == ECAMD_SIG_SM2;
-	if (stride < 4u + blank) {
-		HIPCHK(hipMemsetAsync(d_sigs, 0, n * sl, s));
-		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
-		return 0;
-	}
-	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	if (stage_need(ctx, {{ST_DIGESTS, (size_t)chunk * hl}, {SM_BAD, chunk}, {ST_SLOTS, sm2 ? (size_t)chunk * stride : 0}, {SM_Z, sm2 ? (size_t)chunk * hl : 0},
-			     {SG_Y, sm2 ? chunk * plen : 0}, {SG_STY, sm2 ? chunk : 0}})) {
-		return -1;
-	}
-	uint8_t **S = ctx->stage;
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		const uint8_t *in = d_in + (size_t)off * stride, *hin = in, *keys = nullptr;
-		// SM2: Y for Z, supplied (with its on-curve test) or [x]G by the fixed-base multiplication in the context's secret-scalar mode
-		if (sm2 && bip0340_keys_dev(ctx, cv, m, d_privs + off * ql, d_pubs ? d_pubs + off * plen : nullptr, &keys, s)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_sig_msg_bad(in, stride, blank, sm2 ? S[SG_STY] : nullptr, S[SM_BAD], m, s));
-		if (sm2 && sig_msg_stage_z(ctx, P, m, keys, (uint32_t)plen, in, stride, hl, &hin, s)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_hash_slots(hash_type, hin, stride, m, S[ST_DIGESTS], hl, s));
-		if (sig_sign_dev_locked(ctx, cv, alg, m, d_privs + off * ql, d_nonces + off * ql, S[ST_DIGESTS], hl, d_sigs + off * sl, d_status + off, s)) {
-			return -1;
-		}
-		HIPCHK(ecamd_launch_sig_msg_reject_sign(d_sigs + off * sl, (uint32_t)sl, d_status + off, S[SM_BAD], m, s));
-	}
-	return 0;
-}
-
-extern "C" int ec_sig_verify_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
-					   const void *d_sigs, const void *d_msg_slots, uint32_t stride, const uint8_t *id, uint32_t id_len,
-					   void *d_result, void *hip_stream)
-{
-	ecsm2z::Prefix P;
-	if (sig_msg_args_ok("ec_sig_verify_msg_batch_dev", ctx, cv, alg, hash_type, stride, id, id_len)) {
-		return -1;
-	}
-	if (n && (!d_pubkeys || !d_sigs || !d_msg_slots || !d_result)) {
-		return fail("ec_sig_verify_msg_batch_dev: bad argument");
-	}
-	if (n == 0) {
-		return 0;
-	}
-	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
-		return -1;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return sig_msg_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_msg_slots,
-						 stride, P, (uint8_t *)d_result, s);
-	});
-}
-
-extern "C" int ec_sig_verify_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
-				       const uint8_t *sigs, const uint8_t *msg_slots, uint32_t stride, const uint8_t *id, uint32_t id_len,
-				       uint8_t *result)
-{
-	ecsm2z::Prefix P;
-	if (sig_msg_args_ok("ec_sig_verify_msg_batch", ctx, cv, alg, hash_type, stride, id, id_len)) {
-		return -1;
-	}
-	if (n && (!pubkeys || !sigs || !msg_slots || !result)) {
-		return fail("ec_sig_verify_msg_batch: bad argument");
-	}
-	if (n == 0) {
-		return 0;
-	}
-	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
-		return -1;
-	}
-	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, (size_t)2 * cv->qlen}, {msg_slots, nullptr, stride},
-					   {nullptr, result, 1}};
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &between) {
-		return sig_msg_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, P, op[3], s, &between);
-	});
-}
-
-extern "C" int ec_sig_sign_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
-					 const void *d_pubkeys, const void *d_nonces, const void *d_msg_slots, uint32_t stride, const uint8_t *id,
-					 uint32_t id_len, void *d_sigs, void *d_status, void *hip_stream)
-{
-	ecsm2z::Prefix P;
-	if (sig_msg_args_ok("ec_sig_sign_msg_batch_dev", ctx, cv, alg, hash_type, stride, id, id_len)) {
-		return -1;
-	}
-	if (n && (!d_privs || !d_nonces || !d_msg_slots || !d_sigs || !d_status)) {
-		return fail("ec_sig_sign_msg_batch_dev: bad argument");
-	}
-	if (n == 0) {
-		return 0;
-	}
-	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
-		return -1;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return sig_msg_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, alg == ECAMD_SIG_SM2 ? (const uint8_t *)d_pubkeys : nullptr,
-					       (const uint8_t *)d_nonces, (const uint8_t *)d_msg_slots, stride, P, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
-	});
-}
-
-extern "C" int ec_sig_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
-				     const uint8_t *pubkeys, const uint8_t *nonces, const uint8_t *msg_slots, uint32_t stride, const uint8_t *id,
-				     uint32_t id_len, uint8_t *sigs, uint8_t *status)
-{
-	ecsm2z::Prefix P;
-	if (sig_msg_args_ok("ec_sig_sign_msg_batch", ctx, cv, alg, hash_type, stride, id, id_len)) {
-		return -1;
-	}
-	if (n && (!privs || !nonces || !msg_slots || !sigs || !status)) {
-		return fail("ec_sig_sign_msg_batch: bad argument");
-	}
-	if (n == 0) {
-		return 0;
-	}
-	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
-		return -1;
-	}
-	const size_t ql = (size_t)cv->qlen;
-	const bool with_keys = alg == ECAMD_SIG_SM2 && pubkeys;
-	std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {msg_slots, nullptr, stride}, {nullptr, sigs, 2 * ql}, {nullptr, status, 1}};
-	if (with_keys) {
-		arrs.push_back({pubkeys, nullptr, (size_t)2 * cv->clen});
-	}
-	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return sig_msg_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], with_keys ? ip[5] : nullptr, ip[1], ip[2], stride, P, op[3], op[4], s);
-	});
-}
-
-static int hash_slots_args_ok(const char *fn, ecamd_ctx *ctx, int hash_type, uint32_t n, const void *slots, uint32_t stride, const void *out)
-{
-	if (ecamd_hash_digest_len(hash_type) == 0) {
-		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224 / 256 / 384 / 512), 11 (SM3), 13 or 14 (Streebog-256 / -512)");
-	}
-	if (stride < 4 || (stride & 3u) || stride > 4096) {
-		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
-	}
-	if (!ctx || (n && (!slots || !out))) {
-		return fail(std::string(fn) + ": bad argument");
-	}
-	return 0;
-}
-
-static int hash_slots_dev_locked(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *d_slots, uint32_t stride, uint8_t *d_out, hipStream_t s)
-{
-	const uint32_t hl = (uint32_t)ecamd_hash_digest_len(hash_type), chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
-	for (uint32_t off = 0; off < n; off += chunk) {
-		const uint32_t m = (n - off) < chunk ? (n - off) : chunk;
-		HIPCHK(ecamd_launch_hash_slots(hash_type, d_slots + (size_t)off * stride, stride, m, d_out + (size_t)off * hl, hl, s));
-	}
-	return 0;
-}
-
-extern "C" int ec_hash_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_msg_slots, uint32_t stride, void *d_digests,
-				       void *hip_stream)
-{
-	if (hash_slots_args_ok("ec_hash_slots_batch_dev", ctx, hash_type, n, d_msg_slots, stride, d_digests)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
-		return hash_slots_dev_locked(ctx, hash_type, n, (const uint8_t *)d_msg_slots, stride, (uint8_t *)d_digests, s);
-	});
-}
-
-extern "C" int ec_hash_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *msg_slots, uint32_t stride, uint8_t *digests)
-{
-	if (hash_slots_args_ok("ec_hash_slots_batch", ctx, hash_type, n, msg_slots, stride, digests)) {
-		return -1;
-	}
-	if (n == 0) {
-		return 0;
-	}
-	const std::vector<HostArr> arrs = {{msg_slots, nullptr, stride}, {nullptr, digests, (size_t)ecamd_hash_digest_len(hash_type)}};
-	return host_call(ctx, 256, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
-		return hash_slots_dev_locked(ctx, hash_type, m, ip[0], stride, op[1], s);
 	});
 }
 

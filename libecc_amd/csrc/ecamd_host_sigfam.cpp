@@ -1,0 +1,1407 @@
+// libecc_amd/csrc/ecamd_host_sigfam.cpp -- host side of the C ABI declared in include/libecc_amd.h: the signature families that hash on the device, and the message-level forms
+// (ecamd_host_internal.h says what the host units share and how they are laid out).
+#include "ecamd_host_internal.h"
+#include "ecamd_sighash.h"
+#include "ecamd_schnorr.h"
+#include "ecamd_bign.h"
+#include "ecamd_rfc6979.h"
+#include "ecamd_dbign_nonce.h"
+#include "ecamd_bip0340_nonce.h"
+#include "ecamd_sm2z.h"
+
+using namespace ecamd_host;
+
+// ------------------------------------------------------------------------------------------
+// batched ECSDSA / ECOSDSA / ECKCDSA (include/libecc_amd.h: ec_sig_hashed_*): the schemes that hash the commitment.  Per chunk of
+// at most max_chunk items, verification is
+//   k_hsig_prep       s in [1, q - 1], e from r, the multipliers u (of G) and v (of Y), the flag byte
+//   A = [u]G, B = [v]Y one fixed-base and one variable-base pass; on a cofactor curve [q]Y too, as ECDSA verification does
+//   k_recover_fin     W' = A + B as affine bytes, one shared inversion per eight items (its second sum A - B is not used)
+//   k_recover_redo    the items with A or B at infinity or x_A = x_B, on the complete formulas
+//   k_hsig_fill       W' into the blank of a copy of the caller's slots, or ECKCDSA's slot of FE2OS(W'x)
+//   k_sha2_slots      the digest
+//   k_hsig_cmp        the digest against r
+// and signing is [k]G (secret-scalar mode as the context says), k_hsig_fill, k_sha2_slots, k_hsig_sign.
+// Frames: ST_ with ST_SLOTS and ST_DIGESTS; signing SG_.  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static uint32_t hsig_staged_stride(const ecamd_curve *cv, int alg, uint32_t stride)
+{
+	return alg == ECAMD_SIG_ECKCDSA ? (uint32_t)((4 + cv->clen + 3) & ~3) : stride;
+}
+
+// a stride that cannot hold the length word and the blank: no slot is usable, every item is rejected
+static bool hsig_no_room(const ecamd_curve *cv, int alg, uint32_t stride)
+{
+	return alg != ECAMD_SIG_ECKCDSA && stride < 4u + (uint32_t)echsig::blank_len(alg, cv->clen);
+}
+
+static int hsig_stage_hash(ecamd_ctx *ctx, int hash_type, uint32_t m, EcamdHsigArgs &H, const uint8_t *d_in, uint32_t stride,
+			   hipStream_t s)
+{
+	uint8_t **S = ctx->stage;
+	if (H.alg != ECAMD_SIG_ECKCDSA) {
+		// the caller's array is not modified: the coordinates go into a copy
+		HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
+	}
+	H.slots = S[ST_SLOTS];
+	H.dg = S[ST_DIGESTS];
+	HIPCHK(ecamd_launch_hsig_fill(H, s));
+	HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], H.sstride, m, S[ST_DIGESTS], H.hsize, s));
+	return 0;
+}
+
+static int hsig_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_pub,
+				  const uint8_t *d_sig, const uint8_t *d_in, uint32_t stride, uint8_t *d_res, hipStream_t s)
+{
+	PublicScalars pub_scope(ctx);   // u, v and the group order are public
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
+	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	if (hsig_no_room(cv, alg, stride)) {
+		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
+		return 0;
+	}
+	const size_t siglen = (size_t)echsig::r_len(alg, (int)hsize, (int)ql) + ql;
+	const uint32_t sstride = hsig_staged_stride(cv, alg, stride);
+	const uint32_t chunk = chunk_items(ctx, n);
+	if (verify_sum_need(ctx, cv, chunk) || stage_need(ctx, {{ST_SLOTS, (size_t)chunk * sstride}, {ST_DIGESTS, (size_t)chunk * hsize}})) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		const uint8_t *pub = d_pub + (size_t)off * plen, *in = d_in + (size_t)off * stride;
+		EcamdHsigArgs H;
+		memset(&H, 0, sizeof(H));
+		H.sigs = d_sig + (size_t)off * siglen;
+		H.inputs = in;
+		H.u = S[ST_U];
+		H.v = S[ST_V];
+		H.flags = S[ST_FLAGS];
+		H.W = S[ST_W];
+		H.stW = S[ST_STW];
+		H.out = d_res + off;
+		H.n = m;
+		H.qlen = (uint32_t)ql;
+		H.clen = (uint32_t)cl;
+		H.hsize = hsize;
+		H.sstride = sstride;
+		H.qslot = cv->qslot;
+		H.alg = alg;
+		HIPCHK(ecamd_launch_hsig_prep(cv->qnw, H, s));
+		if (verify_sum_dev(ctx, cv, m, pub, s) || hsig_stage_hash(ctx, hash_type, m, H, in, stride, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_hsig_cmp(H, s));
+		return 0;
+	});
+}
+
+static int hsig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_privs,
+				const uint8_t *d_nonces, const uint8_t *d_in, uint32_t stride, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
+{
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
+	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	const size_t siglen = (size_t)echsig::r_len(alg, (int)hsize, (int)ql) + ql;
+	const uint32_t sstride = hsig_staged_stride(cv, alg, stride);
+	if (hsig_no_room(cv, alg, stride)) {
+		HIPCHK(hipMemsetAsync(d_sigs, 0, n * siglen, s));
+		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
+		return 0;
+	}
+	const uint32_t chunk = chunk_items(ctx, n);
+	if (stage_need(ctx, SG_KG, chunk * plen) || stage_need(ctx, SG_STKG, chunk) ||
+	    stage_need(ctx, ST_FLAGS, chunk) || stage_need(ctx, ST_SLOTS, (size_t)chunk * sstride) ||
+	    stage_need(ctx, ST_DIGESTS, (size_t)chunk * hsize)) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		const uint8_t *in = d_in + (size_t)off * stride;
+		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {   // W = [k]G
+			return -1;
+		}
+		EcamdHsigArgs H;
+		memset(&H, 0, sizeof(H));
+		H.inputs = in;
+		H.privs = d_privs + off * ql;
+		H.nonces = d_nonces + off * ql;
+		H.flags = S[ST_FLAGS];
+		H.W = S[SG_KG];
+		H.stW = S[SG_STKG];
+		H.out = d_sigs + (size_t)off * siglen;
+		H.status = d_status + off;
+		H.n = m;
+		H.qlen = (uint32_t)ql;
+		H.clen = (uint32_t)cl;
+		H.hsize = hsize;
+		H.sstride = sstride;
+		H.qslot = cv->qslot;
+		H.alg = alg;
+		H.sign = 1;
+		if (hsig_stage_hash(ctx, hash_type, m, H, in, stride, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_hsig_sign(cv->qnw, H, s));
+		return 0;
+	});
+}
+
+static int hsig_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a, const void *b,
+			const void *c, const void *d, const void *e, uint32_t stride)
+{
+	if (!echsig::alg_known(alg)) {
+		return fail(std::string(fn) + ": alg must be ECAMD_SIG_ECKCDSA, ECAMD_SIG_ECSDSA or ECAMD_SIG_ECOSDSA");
+	}
+	if (echsig::hash_size(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224, SHA-256, SHA-384, SHA-512)");
+	}
+	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	if (alg == ECAMD_SIG_ECKCDSA) {
+		if (stride != (uint32_t)echsig::hash_size(hash_type)) {
+			return fail(std::string(fn) + ": ECKCDSA takes digests h = H(z || m): stride must be the hash's digest size");
+		}
+	} else if ((stride & 3u) || stride > 4096 || stride < 4) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	return 0;
+}
+
+extern "C" int ec_sig_hashed_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
+					      const void *d_sigs, const void *d_inputs, uint32_t stride, void *d_result, void *hip_stream)
+{
+	if (hsig_args_ok("ec_sig_hashed_verify_batch_dev", ctx, cv, alg, hash_type, n, d_pubkeys, d_sigs, d_inputs, d_result, d_result, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return hsig_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_inputs, stride,
+					      (uint8_t *)d_result, s);
+	});
+}
+
+extern "C" int ec_sig_hashed_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
+					  const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, uint8_t *result)
+{
+	if (hsig_args_ok("ec_sig_hashed_verify_batch", ctx, cv, alg, hash_type, n, pubkeys, sigs, inputs, result, result, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t siglen = (size_t)echsig::r_len(alg, echsig::hash_size(hash_type), cv->qlen) + cv->qlen;
+	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, siglen}, {inputs, nullptr, stride}, {nullptr, result, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return hsig_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], s);
+	});
+}
+
+extern "C" int ec_sig_hashed_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+					    const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs, void *d_status, void *hip_stream)
+{
+	if (hsig_args_ok("ec_sig_hashed_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_inputs, d_sigs, d_status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return hsig_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_inputs, stride,
+					    (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+					const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, uint8_t *sigs, uint8_t *status)
+{
+	if (hsig_args_ok("ec_sig_hashed_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, inputs, sigs, status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t ql = (size_t)cv->qlen;
+	const size_t siglen = (size_t)echsig::r_len(alg, echsig::hash_size(hash_type), cv->qlen) + ql;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {inputs, nullptr, stride}, {nullptr, sigs, siglen}, {nullptr, status, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return hsig_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], op[4], s);
+	});
+}
+
+// ------------------------------------------------------------------------------------------
+// batched BIGN / DBIGN (include/libecc_amd.h: ec_bign_*): the scheme that hashes its commitment with belt-hash.  Per chunk of at
+// most max_chunk items, verification is
+//   k_sha2_slots / k_belt_slots   hash_type != 0 only: the digests of the caller's message slots
+//   k_bign_prep       s1 < q, hbar, the multipliers u (of G) and v (of Y), the flag byte
+//   A = [u]G, B = [v]Y one fixed-base and one variable-base pass (public scalars); on a cofactor curve [q]Y too, as ECDSA verification does
+//   k_recover_fin     W' = A + B as affine bytes, one shared inversion per eight items (its second sum A - B is not used)
+//   k_recover_redo    the items with A or B at infinity (u = 0) or x_A = x_B, on the complete formulas
+//   k_bign_fill       belt-hash's slot OID || <LE(W'x) || LE(W'y)>_2l || digest
+//   k_belt_slots      t
+//   k_bign_cmp        t against s0
+// and signing is [k]G (secret-scalar mode as the context says), k_bign_fill, k_belt_slots, k_bign_sign.
+// Frames: ST_ with ST_SLOTS (belt-hash's slots), ST_DIGESTS (the digests of the messages) and ST_BELT; signing SG_.  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static int bign_message_digests(ecamd_ctx *ctx, int hash_type, uint32_t m, const uint8_t *d_in, uint32_t stride, EcamdBignArgs &B, hipStream_t s)
+{
+	if (hash_type == 0) {
+		B.dg = d_in;          // the caller hashed: stride is the digest length
+		B.mslots = nullptr;
+		return 0;
+	}
+	uint8_t **S = ctx->stage;
+	if (hash_type == ecbign::HASH_BELT) {
+		HIPCHK(ecamd_launch_belt_slots(d_in, stride, m, S[ST_DIGESTS], B.hsize, s));
+	} else {
+		HIPCHK(ecamd_launch_sha2_slots(hash_type, d_in, stride, m, S[ST_DIGESTS], B.hsize, s));
+	}
+	B.dg = S[ST_DIGESTS];
+	B.mslots = d_in;
+	B.mstride = stride;
+	return 0;
+}
+
+static void bign_args(EcamdBignArgs &B, const ecamd_curve *cv, int hash_type, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint32_t m)
+{
+	memset(&B, 0, sizeof(B));
+	B.n = m;
+	B.qlen = (uint32_t)cv->qlen;
+	B.clen = (uint32_t)cv->clen;
+	B.hsize = hash_type == 0 ? stride : (uint32_t)ecbign::hash_size(hash_type);
+	B.oid_len = oid_len;
+	B.bstride = ecbign::belt_stride(oid_len, cv->qlen, B.hsize);
+	B.qslot = cv->qslot;
+	if (oid_len) {
+		memcpy(B.oid, oid, oid_len);
+	}
+}
+
+static int bign_stage_belt(ecamd_ctx *ctx, EcamdBignArgs &B, hipStream_t s)
+{
+	uint8_t **S = ctx->stage;
+	B.slots = S[ST_SLOTS];
+	B.bt = S[ST_BELT];
+	HIPCHK(ecamd_launch_bign_fill(B, s));
+	HIPCHK(ecamd_launch_belt_slots(S[ST_SLOTS], B.bstride, B.n, S[ST_BELT], ecbign::DIGEST_BT, s));
+	return 0;
+}
+
+static int bign_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_pub, const uint8_t *d_sig,
+				  const uint8_t *d_in, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *d_res, hipStream_t s)
+{
+	PublicScalars pub_scope(ctx);   // u, v and the group order are public
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, siglen = (size_t)ecbign::sig_len(cv->qlen);
+	const uint32_t chunk = chunk_items(ctx, n);
+	EcamdBignArgs B;
+	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
+	if (verify_sum_need(ctx, cv, chunk) ||
+	    stage_need(ctx, {{ST_SLOTS, (size_t)chunk * B.bstride}, {ST_DIGESTS, hash_type ? (size_t)chunk * B.hsize : 0},
+			     {ST_BELT, (size_t)chunk * ecbign::DIGEST_BT}})) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		const uint8_t *pub = d_pub + (size_t)off * plen;
+		B.n = m;
+		B.sigs = d_sig + (size_t)off * siglen;
+		B.u = S[ST_U];
+		B.v = S[ST_V];
+		B.flags = S[ST_FLAGS];
+		B.W = S[ST_W];
+		B.stW = S[ST_STW];
+		B.out = d_res + off;
+		if (bign_message_digests(ctx, hash_type, m, d_in + (size_t)off * stride, stride, B, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_bign_prep(cv->qnw, B, s));
+		if (verify_sum_dev(ctx, cv, m, pub, s) || bign_stage_belt(ctx, B, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_bign_cmp(B, s));
+		return 0;
+	});
+}
+
+static int bign_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
+				const uint8_t *d_in, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *d_sigs, uint8_t *d_status,
+				hipStream_t s)
+{
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen, siglen = (size_t)ecbign::sig_len(cv->qlen);
+	const uint32_t chunk = chunk_items(ctx, n);
+	EcamdBignArgs B;
+	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
+	if (stage_need(ctx, SG_KG, chunk * plen) || stage_need(ctx, SG_STKG, chunk) ||
+	    stage_need(ctx, ST_SLOTS, (size_t)chunk * B.bstride) ||
+	    stage_need(ctx, ST_DIGESTS, hash_type ? (size_t)chunk * B.hsize : 0) ||
+	    stage_need(ctx, ST_BELT, (size_t)chunk * ecbign::DIGEST_BT)) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {   // W = [k]G
+			return -1;
+		}
+		B.n = m;
+		B.privs = d_privs + off * ql;
+		B.nonces = d_nonces + off * ql;
+		B.W = S[SG_KG];
+		B.stW = S[SG_STKG];
+		B.out = d_sigs + (size_t)off * siglen;
+		B.status = d_status + off;
+		B.sign = 1;
+		if (bign_message_digests(ctx, hash_type, m, d_in + (size_t)off * stride, stride, B, s) || bign_stage_belt(ctx, B, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_bign_sign(cv->qnw, B, s));
+		return 0;
+	});
+}
+
+static int bign_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a, const void *b,
+			const void *c, const void *d, const void *e, uint32_t stride, const uint8_t *oid, uint32_t oid_len)
+{
+	if (!ecbign::alg_known(alg)) {
+		return fail(std::string(fn) + ": alg must be ECAMD_SIG_BIGN or ECAMD_SIG_DBIGN");
+	}
+	if (hash_type != 0 && ecbign::hash_size(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 0 (inputs are digests), 1 .. 4 (SHA-224 / 256 / 384 / 512) or ECAMD_HASH_BELT");
+	}
+	if (oid_len > (uint32_t)ecbign::MAX_OID || (oid_len && !oid)) {
+		return fail(std::string(fn) + ": oid_len must be 0 .. 64, and oid non-NULL when it is not 0");
+	}
+	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	if (hash_type == 0) {
+		if (stride < 1 || stride > (uint32_t)ecbign::MAX_DIGEST) {
+			return fail(std::string(fn) + ": hash_type 0 takes digests: stride must be the digest length, 1 .. 128");
+		}
+	} else if ((stride & 3u) || stride > 4096 || stride < 4) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	return 0;
+}
+
+extern "C" int ec_bign_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
+					const void *d_sigs, const void *d_inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, void *d_result,
+					void *hip_stream)
+{
+	if (bign_args_ok("ec_bign_verify_batch_dev", ctx, cv, alg, hash_type, n, d_pubkeys, d_sigs, d_inputs, d_result, d_result, stride, oid, oid_len)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return bign_verify_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_inputs, stride, oid,
+					      oid_len, (uint8_t *)d_result, s);
+	});
+}
+
+extern "C" int ec_bign_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
+				    const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *result)
+{
+	if (bign_args_ok("ec_bign_verify_batch", ctx, cv, alg, hash_type, n, pubkeys, sigs, inputs, result, result, stride, oid, oid_len)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, (size_t)ecbign::sig_len(cv->qlen)},
+					   {inputs, nullptr, stride}, {nullptr, result, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return bign_verify_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], ip[2], stride, oid, oid_len, op[3], s);
+	});
+}
+
+extern "C" int ec_bign_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+				      const void *d_nonces, const void *d_inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, void *d_sigs,
+				      void *d_status, void *hip_stream)
+{
+	if (bign_args_ok("ec_bign_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_inputs, d_sigs, d_status, stride, oid, oid_len)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return bign_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_nonces, (const uint8_t *)d_inputs, stride, oid,
+					    oid_len, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_bign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+				  const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, const uint8_t *oid, uint32_t oid_len, uint8_t *sigs,
+				  uint8_t *status)
+{
+	if (bign_args_ok("ec_bign_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, inputs, sigs, status, stride, oid, oid_len)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {inputs, nullptr, stride},
+					   {nullptr, sigs, (size_t)ecbign::sig_len(cv->qlen)}, {nullptr, status, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return bign_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], ip[2], stride, oid, oid_len, op[3], op[4], s);
+	});
+}
+
+// ------------------------------------------------------------------------------------------
+// BIP0340 / ECFSDSA item by item (include/libecc_amd.h: ec_schnorr_verify_batch, ec_schnorr_sign_batch): the two schemes whose
+// signature carries the commitment as a point.  Per chunk of at most max_chunk items, verification is
+//   k_prj_import           projective keys only: prj_pt_import_from_buf + prj_pt_unique (affine keys are validated by the multiplication)
+//   k_schnorr_item_prep    key status and ranges, r < p (W.x, W.y < p), s in range, the slot's length; the flag byte, the key as
+//                          the equation uses it, s; the copy of the caller's slots patched with the signature's r (W) and the key's x
+//   k_ptf (op 2)           ECFSDSA: W on the curve
+//   k_sha2_slots, k_schnorr_ne   e = H(slot) mod q, then q - e
+//   A = [s]G, B = [q - e]Y one fixed-base and one variable-base pass; on a cofactor curve [q]Y too, as ECDSA verification does
+//   k_recover_fin / _redo  W' = A + B as affine bytes, one shared inversion per eight items; the exceptional pairs on the complete formulas
+//   k_schnorr_item_cmp     BIP0340: finite, y even, x = r; ECFSDSA: finite, x || y = r
+// and signing is [k]G (secret-scalar mode as the context says), BIP0340: Y = [x]G (the same) or the caller's key through k_ptf (op 2),
+// k_schnorr_item_fill, k_sha2_slots, k_schnorr_item_sign.
+// Frames: ST_ (ST_U holds s, ST_V q - e) with ST_SLOTS, ST_DIGESTS and SI_; signing SG_.  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static bool schnorr_item_no_room(const ecamd_curve *cv, int alg, uint32_t hsize, uint32_t stride)
+{
+	return stride < 4u + (uint32_t)ecschnorr::fixed_len(alg, (int)hsize, cv->clen);
+}
+
+static void schnorr_item_args(EcamdSchnorrItemArgs &H, const ecamd_curve *cv, int alg, uint32_t hsize, uint32_t stride, uint32_t m)
+{
+	memset(&H, 0, sizeof(H));
+	H.n = m;
+	H.qlen = (uint32_t)cv->qlen;
+	H.clen = (uint32_t)cv->clen;
+	H.hsize = hsize;
+	H.sstride = stride;
+	H.qslot = cv->qslot;
+	H.alg = alg;
+	big_to_be(H.p_be, cv->clen, cv->p);
+}
+
+static int schnorr_item_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_keys,
+					  int key_fmt, const uint8_t *d_sig, const uint8_t *d_in, uint32_t stride, uint8_t *d_res, hipStream_t s)
+{
+	PublicScalars pub_scope(ctx);   // s, q - e and the group order are public
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
+	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	if (schnorr_item_no_room(cv, alg, hsize, stride)) {
+		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
+		return 0;
+	}
+	const bool fs = alg == ECAMD_SIG_ECFSDSA, prj = key_fmt == ECAMD_PT_PROJECTIVE;
+	const size_t siglen = (size_t)ecschnorr::r_len(alg, (int)cl) + ql, kw = (prj ? 3 : 2) * cl;
+	const uint32_t chunk = chunk_items(ctx, n);
+	if (verify_sum_need(ctx, cv, chunk) ||
+	    stage_need(ctx, {{ST_SLOTS, (size_t)chunk * stride}, {ST_DIGESTS, (size_t)chunk * hsize}, {SI_KEY, chunk * plen},
+			     {SI_PRJ_AFF, prj ? chunk * plen : 0}, {SI_PRJ_ST, prj ? chunk : 0}, {SI_WPT, fs ? chunk * plen : 0}, {SI_WST, fs ? chunk : 0}})) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	EcamdSchnorrNeArgs N;
+	memset(&N, 0, sizeof(N));
+	for (int w = 0; w < 18; w++) {
+		N.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
+	}
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		const uint8_t *keys = d_keys + (size_t)off * kw, *kst = nullptr;
+		if (prj) {
+			EcamdPrjInArgs I;
+			I.in = keys;
+			I.aff = S[SI_PRJ_AFF];
+			I.pre = S[SI_PRJ_ST];
+			I.n = m;
+			I.clen = (uint32_t)cl;
+			I.for_mul = fs ? 1 : 0;   // (0 : 0 : 0): ECFSDSA multiplies the key as it is, BIP0340 takes its unique representative
+			I.slot = cv->slot;
+			HIPCHK(launch_prj_import(cv, I, s));
+			keys = S[SI_PRJ_AFF];
+			kst = S[SI_PRJ_ST];
+		}
+		// the caller's array is not modified: the patches go into a copy
+		HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
+		EcamdSchnorrItemArgs H;
+		schnorr_item_args(H, cv, alg, hsize, stride, m);
+		H.keys = keys;
+		H.kst = kst;
+		H.gen = cv->d_gen;
+		H.sigs = d_sig + (size_t)off * siglen;
+		H.slots = S[ST_SLOTS];
+		H.key_out = S[SI_KEY];
+		H.s_out = S[ST_U];
+		H.w_out = fs ? S[SI_WPT] : nullptr;
+		H.flags = S[ST_FLAGS];
+		H.wst = fs ? S[SI_WST] : nullptr;
+		H.A = S[ST_A];
+		H.stA = S[ST_STA];
+		H.W = S[ST_W];
+		H.stW = S[ST_STW];
+		H.out = d_res + off;
+		HIPCHK(ecamd_launch_schnorr_item_prep(cv->qnw, H, s));
+		if (fs) {
+			// "Reject the signature if r is not a valid point on the curve" (ecfsdsa.c:449-460): the on-curve test the point calls use
+			EcamdPtfArgs T;
+			memset(&T, 0, sizeof(T));
+			T.p1 = S[SI_WPT];
+			T.p2 = S[SI_WPT];
+			T.out = S[SI_WPT];   // untouched by op 2
+			T.status = S[SI_WST];
+			T.n = m;
+			T.clen = (uint32_t)cl;
+			T.op = 2;
+			T.slot = cv->slot;
+			HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
+		}
+		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], stride, m, S[ST_DIGESTS], hsize, s));
+		N.dig = S[ST_DIGESTS];
+		N.ne = S[ST_V];
+		N.n = m;
+		N.hlen = hsize;
+		N.qlen = (uint32_t)ql;
+		HIPCHK(ecamd_launch_schnorr_ne(cv->qnw, N, s));
+		// k_recover_fin takes ANY non-zero flag as "no sum for this item": that holds for flag 2 too (ECFSDSA, the key at infinity),
+		// whose verdict k_schnorr_item_cmp reads from A = [s]G and stA, not from W'
+		if (verify_sum_dev(ctx, cv, m, S[SI_KEY], s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_schnorr_item_cmp(H, s));
+		return 0;
+	});
+}
+
+static int schnorr_item_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_privs,
+					const uint8_t *d_pubs, const uint8_t *d_nonces, const uint8_t *d_in, uint32_t stride, uint8_t *d_sigs,
+					uint8_t *d_status, hipStream_t s)
+{
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
+	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	const size_t siglen = (size_t)ecschnorr::r_len(alg, (int)cl) + ql;
+	if (schnorr_item_no_room(cv, alg, hsize, stride)) {
+		HIPCHK(hipMemsetAsync(d_sigs, 0, n * siglen, s));
+		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
+		return 0;
+	}
+	const bool bip = alg == ECAMD_SIG_BIP0340;
+	const uint32_t chunk = chunk_items(ctx, n);
+	if (stage_need(ctx, SG_KG, chunk * plen) || stage_need(ctx, SG_STKG, chunk) ||
+	    stage_need(ctx, ST_FLAGS, chunk) || stage_need(ctx, ST_SLOTS, (size_t)chunk * stride) ||
+	    stage_need(ctx, ST_DIGESTS, (size_t)chunk * hsize) ||
+	    (bip && (stage_need(ctx, SG_Y, chunk * plen) || stage_need(ctx, SG_STY, chunk)))) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		if (smul_dev_locked(ctx, cv, m, d_nonces + off * ql, (uint32_t)ql, nullptr, S[SG_KG], S[SG_STKG], s)) {   // R = [k]G
+			return -1;
+		}
+		EcamdSchnorrItemArgs H;
+		schnorr_item_args(H, cv, alg, hsize, stride, m);
+		if (bip && d_pubs) {
+			// the key pair's public half as the caller holds it: coordinates < p and on the curve
+			EcamdPtfArgs T;
+			memset(&T, 0, sizeof(T));
+			T.p1 = d_pubs + off * plen;
+			T.p2 = T.p1;
+			T.out = S[SG_Y];   // untouched by op 2
+			T.status = S[SG_STY];
+			T.n = m;
+			T.clen = (uint32_t)cl;
+			T.op = 2;
+			T.slot = cv->slot;
+			HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
+			H.keys = d_pubs + off * plen;
+		} else if (bip) {
+			if (smul_dev_locked(ctx, cv, m, d_privs + off * ql, (uint32_t)ql, nullptr, S[SG_Y], S[SG_STY], s)) {   // Y = [x]G
+				return -1;
+			}
+			H.keys = S[SG_Y];
+		}
+		H.kst = bip ? S[SG_STY] : nullptr;
+		H.privs = d_privs + off * ql;
+		H.nonces = d_nonces + off * ql;
+		H.slots = S[ST_SLOTS];
+		H.flags = S[ST_FLAGS];
+		H.W = S[SG_KG];
+		H.stW = S[SG_STKG];
+		H.dg = S[ST_DIGESTS];
+		H.out = d_sigs + (size_t)off * siglen;
+		H.status = d_status + off;
+		HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
+		HIPCHK(ecamd_launch_schnorr_item_fill(H, s));
+		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], stride, m, S[ST_DIGESTS], hsize, s));
+		HIPCHK(ecamd_launch_schnorr_item_sign(cv->qnw, H, s));
+		return 0;
+	});
+}
+
+static int schnorr_item_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a,
+				const void *b, const void *c, const void *d, const void *e, uint32_t stride)
+{
+	if (!ecschnorr::alg_known(alg)) {
+		return fail(std::string(fn) + ": alg must be ECAMD_SIG_BIP0340 or ECAMD_SIG_ECFSDSA");
+	}
+	if (echsig::hash_size(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224, SHA-256, SHA-384, SHA-512)");
+	}
+	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	if ((stride & 3u) || stride > 4096 || stride < 4) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	return 0;
+}
+
+static int schnorr_item_fmt_ok(const char *fn, int key_fmt)
+{
+	if (key_fmt != ECAMD_PT_AFFINE && key_fmt != ECAMD_PT_PROJECTIVE) {
+		return fail(std::string(fn) + ": key_fmt must be ECAMD_PT_AFFINE or ECAMD_PT_PROJECTIVE");
+	}
+	return 0;
+}
+
+extern "C" int ec_schnorr_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_keys,
+					   int key_fmt, const void *d_sigs, const void *d_hash_slots, uint32_t stride, void *d_result,
+					   void *hip_stream)
+{
+	if (schnorr_item_args_ok("ec_schnorr_verify_batch_dev", ctx, cv, alg, hash_type, n, d_keys, d_sigs, d_hash_slots, d_result, d_result, stride) ||
+	    schnorr_item_fmt_ok("ec_schnorr_verify_batch_dev", key_fmt)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return schnorr_item_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_keys, key_fmt, (const uint8_t *)d_sigs,
+						      (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_result, s);
+	});
+}
+
+extern "C" int ec_schnorr_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *keys, int key_fmt,
+				       const uint8_t *sigs, const uint8_t *hash_slots, uint32_t stride, uint8_t *result)
+{
+	if (schnorr_item_args_ok("ec_schnorr_verify_batch", ctx, cv, alg, hash_type, n, keys, sigs, hash_slots, result, result, stride) ||
+	    schnorr_item_fmt_ok("ec_schnorr_verify_batch", key_fmt)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t cl = (size_t)cv->clen, siglen = (size_t)ecschnorr::r_len(alg, cv->clen) + cv->qlen;
+	const std::vector<HostArr> arrs = {{keys, nullptr, (key_fmt == ECAMD_PT_PROJECTIVE ? 3 : 2) * cl}, {sigs, nullptr, siglen},
+					   {hash_slots, nullptr, stride}, {nullptr, result, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return schnorr_item_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], key_fmt, ip[1], ip[2], stride, op[3], s);
+	});
+}
+
+extern "C" int ec_schnorr_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+					 const void *d_pubkeys_aff, const void *d_nonces, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+					 void *d_status, void *hip_stream)
+{
+	if (schnorr_item_args_ok("ec_schnorr_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_hash_slots, d_sigs, d_status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return schnorr_item_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff,
+						    (const uint8_t *)d_nonces, (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+				     const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+				     uint8_t *status)
+{
+	if (schnorr_item_args_ok("ec_schnorr_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, hash_slots, sigs, status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t ql = (size_t)cv->qlen, plen = (size_t)2 * cv->clen;
+	const size_t siglen = (size_t)ecschnorr::r_len(alg, cv->clen) + ql;
+	const bool with_pub = alg == ECAMD_SIG_BIP0340 && pubkeys_aff != nullptr;   // ECFSDSA ignores it
+	std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {hash_slots, nullptr, stride}, {nullptr, sigs, siglen},
+				     {nullptr, status, 1}};
+	if (with_pub) {
+		arrs.push_back({pubkeys_aff, nullptr, plen});
+	}
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return schnorr_item_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], with_pub ? ip[5] : nullptr, ip[1], ip[2], stride, op[3], op[4], s);
+	});
+}
+
+// ------------------------------------------------------------------------------------------
+// DBIGN and BIP0340 with the nonce derived ON THE DEVICE (include/libecc_amd.h: ec_dbign_nonce_batch, ec_dbign_sign_batch,
+// ec_bip0340_nonce_batch, ec_bip0340_sign_batch): the two generators of ecamd_detnonce.hip in front of the signing cores above.
+// Per chunk of at most max_chunk items
+//   DBIGN    k_sha2_slots / k_belt_slots (hash_type != 0), k_dbign_nonce into SG_NONCES (the table scanned in secret-scalar mode),
+//            bign_sign_dev_locked on the chunk (it hashes the chunk's messages again for its own frame: a compression or two per item)
+//   BIP0340  Y = [x]G into SG_Y (or the on-curve test of the caller's keys), k_bip0340_nonce into SG_NONCES,
+//            schnorr_item_sign_dev_locked on the chunk with Y as its supplied key (so [x]G is computed once)
+// Every slot the cores size is sized here first, for the whole chunk, so no buffer moves between the generator and the core.
+// SG_NONCES is secret: ensure() wipes what it frees, ecamd_ctx_wipe_scratch the rest.  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static const uint32_t h_sha256_k[64] = {ECAMD_SHA256_K};
+static const uint64_t h_sha512_k[80] = {ECAMD_SHA512_K};
+
+static int det_order_ok(const char *fn, const ecamd_curve *cv)
+{
+	if (cv->qslot < 0 || big_bitlen(cv->q) < 2 || cv->q.size() > 17 || cv->qlen > ecrfc::MAX_QLEN ||
+	    (uint32_t)cv->qlen != ((uint32_t)cv->qbits + 7) / 8 || cv->clen > ecbip::MAX_CLEN) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	return 0;
+}
+
+static int dbign_nonce_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_privs, const uint8_t *d_digests, uint32_t hlen,
+				  const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *d_nonces, uint8_t *d_status,
+				  hipStream_t s)
+{
+	EcamdDbignNonceArgs D;
+	memset(&D, 0, sizeof(D));
+	D.privs = d_privs;
+	D.digests = d_digests;
+	D.nonces = d_nonces;
+	D.status = d_status;
+	D.n = n;
+	D.qlen = (uint32_t)cv->qlen;
+	D.qbits = (uint32_t)cv->qbits;
+	D.hlen = hlen;
+	D.oid_len = oid_len;
+	D.t_len = t_len;
+	D.scan = ctx->secret_scalars ? 1 : 0;
+	for (int w = 0; w < 17; w++) {
+		D.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
+	}
+	if (oid_len) {
+		memcpy(D.oid, oid, oid_len);
+	}
+	if (t_len) {
+		memcpy(D.t, t, t_len);
+	}
+	HIPCHK(ecamd_launch_dbign_nonce(D, s));
+	return 0;
+}
+
+static int dbign_common_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, const uint8_t *oid, uint32_t oid_len, const uint8_t *t,
+			   uint32_t t_len)
+{
+	if (oid_len > (uint32_t)ecdbign::MAX_OID || (oid_len && !oid)) {
+		return fail(std::string(fn) + ": oid_len must be 0 .. 64, and oid non-NULL when it is not 0");
+	}
+	if (t_len > (uint32_t)ecdbign::MAX_T || (t_len && !t)) {
+		return fail(std::string(fn) + ": t_len must be 0 .. 64, and t non-NULL when it is not 0");
+	}
+	if (!ctx || !cv || cv->ctx != ctx) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	return det_order_ok(fn, cv);
+}
+
+static int dbign_nonce_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const void *a, const void *b, uint32_t digest_len,
+			       const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, const void *c, const void *d)
+{
+	if (digest_len < 1 || digest_len > (uint32_t)ecdbign::MAX_DIGEST) {
+		return fail(std::string(fn) + ": digest_len must be 1 .. 128");
+	}
+	if (dbign_common_ok(fn, ctx, cv, oid, oid_len, t, t_len)) {
+		return -1;
+	}
+	if (n && (!a || !b || !c || !d)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	return 0;
+}
+
+extern "C" int ec_dbign_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const void *d_privs, const void *d_digests,
+					uint32_t digest_len, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, void *d_nonces,
+					void *d_status, void *hip_stream)
+{
+	if (dbign_nonce_args_ok("ec_dbign_nonce_batch_dev", ctx, cv, n, d_privs, d_digests, digest_len, oid, oid_len, t, t_len, d_nonces, d_status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return dbign_nonce_dev_locked(ctx, cv, n, (const uint8_t *)d_privs, (const uint8_t *)d_digests, digest_len, oid, oid_len, t, t_len,
+					      (uint8_t *)d_nonces, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_dbign_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *privs, const uint8_t *digests,
+				    uint32_t digest_len, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *nonces,
+				    uint8_t *status)
+{
+	if (dbign_nonce_args_ok("ec_dbign_nonce_batch", ctx, cv, n, privs, digests, digest_len, oid, oid_len, t, t_len, nonces, status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {digests, nullptr, digest_len}, {nullptr, nonces, ql}, {nullptr, status, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return dbign_nonce_dev_locked(ctx, cv, m, ip[0], ip[1], digest_len, oid, oid_len, t, t_len, op[2], op[3], s);
+	});
+}
+
+static int dbign_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_in,
+				 uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *d_sigs,
+				 uint8_t *d_status, hipStream_t s)
+{
+	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen, siglen = (size_t)ecbign::sig_len(cv->qlen);
+	const uint32_t chunk = chunk_items(ctx, n);
+	EcamdBignArgs B;
+	bign_args(B, cv, hash_type, stride, oid, oid_len, chunk);
+	if (stage_need(ctx, {{SG_NONCES, (size_t)chunk * ql}, {SG_KG, chunk * plen}, {SG_STKG, chunk}, {ST_SLOTS, (size_t)chunk * B.bstride},
+			     {ST_DIGESTS, hash_type ? (size_t)chunk * B.hsize : 0}, {ST_BELT, (size_t)chunk * ecbign::DIGEST_BT}})) {
+		return -1;
+	}
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		const uint8_t *in = d_in + (size_t)off * stride;
+		B.n = m;
+		if (bign_message_digests(ctx, hash_type, m, in, stride, B, s)) {
+			return -1;
+		}
+		// (the generator's status lands in the caller's status bytes and is replaced by the signing core's: a zero nonce is status 1 there)
+		if (dbign_nonce_dev_locked(ctx, cv, m, d_privs + off * ql, B.dg, B.hsize, oid, oid_len, t, t_len, ctx->stage[SG_NONCES], d_status + off, s) ||
+		    bign_sign_dev_locked(ctx, cv, hash_type, m, d_privs + off * ql, ctx->stage[SG_NONCES], in, stride, oid, oid_len,
+					 d_sigs + (size_t)off * siglen, d_status + off, s)) {
+			return -1;
+		}
+		return 0;
+	});
+}
+
+static int dbign_sign_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *a, const void *b,
+			      uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, const void *c, const void *d)
+{
+	if (bign_args_ok(fn, ctx, cv, ECAMD_SIG_DBIGN, hash_type, n, a, b, b, c, d, stride, oid, oid_len)) {
+		return -1;
+	}
+	return dbign_common_ok(fn, ctx, cv, oid, oid_len, t, t_len);
+}
+
+extern "C" int ec_dbign_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs, const void *d_inputs,
+				       uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, void *d_sigs,
+				       void *d_status, void *hip_stream)
+{
+	if (dbign_sign_args_ok("ec_dbign_sign_batch_dev", ctx, cv, hash_type, n, d_privs, d_inputs, stride, oid, oid_len, t, t_len, d_sigs, d_status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return dbign_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_inputs, stride, oid, oid_len, t, t_len,
+					     (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_dbign_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *inputs,
+				   uint32_t stride, const uint8_t *oid, uint32_t oid_len, const uint8_t *t, uint32_t t_len, uint8_t *sigs,
+				   uint8_t *status)
+{
+	if (dbign_sign_args_ok("ec_dbign_sign_batch", ctx, cv, hash_type, n, privs, inputs, stride, oid, oid_len, t, t_len, sigs, status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {inputs, nullptr, stride}, {nullptr, sigs, (size_t)ecbign::sig_len(cv->qlen)},
+					   {nullptr, status, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return dbign_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], stride, oid, oid_len, t, t_len, op[2], op[3], s);
+	});
+}
+
+// the two tag hashes of the call's hash, as its words
+template <int ALG, typename KT> static void bip0340_tags_of(EcamdBip0340NonceArgs &N, KT Kt)
+{
+	typename ecrfc::Alg<ALG>::W w[8];
+	ecbip::tag_hash<ALG>("BIP0340/aux", 11, w, Kt);
+	for (int t = 0; t < 8; t++) {
+		N.tag_aux[t] = (uint64_t)w[t];
+	}
+	ecbip::tag_hash<ALG>("BIP0340/nonce", 13, w, Kt);
+	for (int t = 0; t < 8; t++) {
+		N.tag_nonce[t] = (uint64_t)w[t];
+	}
+}
+
+static void bip0340_nonce_args(EcamdBip0340NonceArgs &N, const ecamd_curve *cv, int hash_type, uint32_t stride)
+{
+	memset(&N, 0, sizeof(N));
+	N.qlen = (uint32_t)cv->qlen;
+	N.qbits = (uint32_t)cv->qbits;
+	N.clen = (uint32_t)cv->clen;
+	N.stride = stride;
+	for (int w = 0; w < 17; w++) {
+		N.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
+	}
+	switch (hash_type) {
+	case 1: bip0340_tags_of<224>(N, h_sha256_k); break;
+	case 2: bip0340_tags_of<256>(N, h_sha256_k); break;
+	case 3: bip0340_tags_of<384>(N, h_sha512_k); break;
+	default: bip0340_tags_of<512>(N, h_sha512_k); break;
+	}
+}
+
+// Y of one chunk: [x]G into SG_Y, or the caller's keys with their on-curve test; either way SG_STY holds the status.  *keys: where Y lies.
+static int bip0340_keys_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, const uint8_t *d_privs, const uint8_t *d_pubs, const uint8_t **keys,
+			    hipStream_t s)
+{
+	uint8_t **S = ctx->stage;
+	if (d_pubs) {
+		EcamdPtfArgs T;
+		memset(&T, 0, sizeof(T));
+		T.p1 = d_pubs;
+		T.p2 = d_pubs;
+		T.out = S[SG_Y];   // untouched by op 2
+		T.status = S[SG_STY];
+		T.n = m;
+		T.clen = (uint32_t)cv->clen;
+		T.op = 2;
+		T.slot = cv->slot;
+		HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
+		*keys = d_pubs;
+		return 0;
+	}
+	*keys = S[SG_Y];
+	return smul_dev_locked(ctx, cv, m, d_privs, (uint32_t)cv->qlen, nullptr, S[SG_Y], S[SG_STY], s);
+}
+
+// sign = false: the nonces go to d_out (n x qlen); true: into SG_NONCES, and the signatures (n x (clen + qlen)) to d_out
+static int bip0340_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_pubs,
+			      const uint8_t *d_aux, const uint8_t *d_in, uint32_t stride, uint8_t *d_out, uint8_t *d_status, bool sign, hipStream_t s)
+{
+	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen, siglen = cl + ql;
+	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	if (sign && schnorr_item_no_room(cv, ECAMD_SIG_BIP0340, hsize, stride)) {
+		HIPCHK(hipMemsetAsync(d_out, 0, n * siglen, s));
+		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
+		return 0;
+	}
+	const uint32_t chunk = chunk_items(ctx, n);
+	if (stage_need(ctx, {{SG_Y, chunk * plen}, {SG_STY, chunk}}) ||
+	    (sign && stage_need(ctx, {{SG_NONCES, (size_t)chunk * ql}, {SG_KG, chunk * plen}, {SG_STKG, chunk}, {ST_FLAGS, chunk},
+				      {ST_SLOTS, (size_t)chunk * stride}, {ST_DIGESTS, (size_t)chunk * hsize}}))) {
+		return -1;
+	}
+	EcamdBip0340NonceArgs N;
+	bip0340_nonce_args(N, cv, hash_type, stride);
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		const uint8_t *in = d_in + (size_t)off * stride;
+		if (bip0340_keys_dev(ctx, cv, m, d_privs + off * ql, d_pubs ? d_pubs + off * plen : nullptr, &N.keys, s)) {
+			return -1;
+		}
+		N.n = m;
+		N.privs = d_privs + off * ql;
+		N.kst = ctx->stage[SG_STY];
+		N.aux = d_aux + off * ql;
+		N.slots = in;
+		N.nonces = sign ? ctx->stage[SG_NONCES] : d_out + off * ql;
+		N.status = d_status + off;   // signing: replaced by the core's, where a zero nonce is status 1
+		HIPCHK(ecamd_launch_bip0340_nonce(hash_type, N, s));
+		// the core takes Y as a supplied key ([x]G is computed once): derived here, it fails the core's on-curve test only as the point at infinity
+		if (sign && schnorr_item_sign_dev_locked(ctx, cv, ECAMD_SIG_BIP0340, hash_type, m, N.privs, N.keys, N.nonces, in, stride,
+							 d_out + (size_t)off * siglen, d_status + off, s)) {
+			return -1;
+		}
+		return 0;
+	});
+}
+
+static int bip0340_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *privs, const void *aux,
+			   const void *slots, const void *out, const void *status, uint32_t stride)
+{
+	if (schnorr_item_args_ok(fn, ctx, cv, ECAMD_SIG_BIP0340, hash_type, n, privs, aux, slots, out, status, stride)) {
+		return -1;
+	}
+	return det_order_ok(fn, cv);
+}
+
+extern "C" int ec_bip0340_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
+					  const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_nonces,
+					  void *d_status, void *hip_stream)
+{
+	if (bip0340_args_ok("ec_bip0340_nonce_batch_dev", ctx, cv, hash_type, n, d_privs, d_aux, d_hash_slots, d_nonces, d_status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return bip0340_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff, (const uint8_t *)d_aux,
+					  (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_nonces, (uint8_t *)d_status, false, s);
+	});
+}
+
+extern "C" int ec_bip0340_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
+					 const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+					 void *d_status, void *hip_stream)
+{
+	if (bip0340_args_ok("ec_bip0340_sign_batch_dev", ctx, cv, hash_type, n, d_privs, d_aux, d_hash_slots, d_sigs, d_status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return bip0340_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_pubkeys_aff, (const uint8_t *)d_aux,
+					  (const uint8_t *)d_hash_slots, stride, (uint8_t *)d_sigs, (uint8_t *)d_status, true, s);
+	});
+}
+
+static int bip0340_host(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *pubkeys_aff,
+			const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *out, size_t outlen, uint8_t *status, bool sign)
+{
+	const size_t ql = (size_t)cv->qlen, plen = (size_t)2 * cv->clen;
+	std::vector<HostArr> arrs = {{privs, nullptr, ql}, {aux, nullptr, ql}, {hash_slots, nullptr, stride}, {nullptr, out, outlen}, {nullptr, status, 1}};
+	if (pubkeys_aff) {
+		arrs.push_back({pubkeys_aff, nullptr, plen});
+	}
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return bip0340_dev_locked(ctx, cv, hash_type, m, ip[0], pubkeys_aff ? ip[5] : nullptr, ip[1], ip[2], stride, op[3], op[4], sign, s);
+	});
+}
+
+extern "C" int ec_bip0340_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+				      const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *nonces,
+				      uint8_t *status)
+{
+	if (bip0340_args_ok("ec_bip0340_nonce_batch", ctx, cv, hash_type, n, privs, aux, hash_slots, nonces, status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return bip0340_host(ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, nonces, (size_t)cv->qlen, status, false);
+}
+
+extern "C" int ec_bip0340_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+				     const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+				     uint8_t *status)
+{
+	if (bip0340_args_ok("ec_bip0340_sign_batch", ctx, cv, hash_type, n, privs, aux, hash_slots, sigs, status, stride)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return bip0340_host(ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, sigs, (size_t)cv->clen + cv->qlen, status, true);
+}
+
+// ------------------------------------------------------------------------------------------
+// ECGDSA / ECRDSA / SM2 from messages (include/libecc_amd.h: ec_sig_verify_msg_batch, ec_sig_sign_msg_batch, ec_hash_slots_batch): the
+// hashes of ecamd_hash.hip / ecamd_hash2.hip in front of the digest-level cores ecdsa_verify_dev_locked(.., alg) / sig_sign_dev_locked,
+// which run unchanged.  Per chunk of at most max_chunk items:
+//   (signing, SM2)     Y: the caller's keys through the on-curve test, or [x]G (bip0340_keys_dev: SG_Y, SG_STY)
+//   k_sig_msg_bad      SM_BAD: the slot does not fit its stride, is shorter than SM2's blank, or the key did not import
+//   (SM2) k_sm2_z      Z from the prefix midstate into SM_Z; a copy of the slots in ST_SLOTS; k_slot_patch puts Z into the blank
+//   k_*_slots          the digests into ST_DIGESTS
+//   the core           verdicts / signatures and status as for the digest-level call
+//   k_reject_where / k_sig_msg_reject_sign   SM_BAD's items: result 1 / status 1 with zero bytes
+// Frames: SM_ with ST_SLOTS and ST_DIGESTS around the core's own (ST_ / VP_ / SG_).  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static int sig_msg_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t stride, const uint8_t *id,
+			   uint32_t id_len)
+{
+	if (sig_alg_ok(fn, alg)) {
+		return -1;
+	}
+	if (ecamd_hash_digest_len(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224 / 256 / 384 / 512), 11 (SM3), 13 or 14 (Streebog-256 / -512)");
+	}
+	if (stride < 4 || (stride & 3u) || stride > 4096) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	if (!ctx || !cv || cv->ctx != ctx) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	if (alg == ECAMD_SIG_SM2) {
+		if (ecsm2z::hash_size(hash_type) == 0) {
+			return fail(std::string(fn) + ": SM2's Z is computed with SM3 or SHA-2 (hash_type 11 or 1 .. 4)");
+		}
+		if (id_len > (uint32_t)ecsm2z::MAX_ID) {
+			return fail(std::string(fn) + ": id_len must be at most 1024");
+		}
+		if (id_len && !id) {
+			return fail(std::string(fn) + ": id is NULL with a positive id_len");
+		}
+		if (cv->clen > ecsm2z::MAX_CLEN) {
+			return fail(std::string(fn) + ": field not supported");
+		}
+	}
+	return 0;
+}
+
+// the prefix of the call's Z (SM2 only; otherwise left alone)
+static int sig_msg_prefix(const ecamd_curve *cv, int alg, int hash_type, const uint8_t *id, uint32_t id_len, ecsm2z::Prefix &P)
+{
+	if (alg != ECAMD_SIG_SM2) {
+		return 0;
+	}
+	uint8_t a[ecsm2z::MAX_CLEN], b[ecsm2z::MAX_CLEN], gx[ecsm2z::MAX_CLEN], gy[ecsm2z::MAX_CLEN];
+	big_to_be(a, cv->clen, cv->a);
+	big_to_be(b, cv->clen, cv->b);
+	big_to_be(gx, cv->clen, cv->gx);
+	big_to_be(gy, cv->clen, cv->gy);
+	if (ecsm2z::prefix_init(P, hash_type, id, id_len, a, b, gx, gy, (uint32_t)cv->clen, h_sha256_k, h_sha512_k)) {
+		return fail("internal: Z prefix");
+	}
+	return 0;
+}
+
+// SM2: Z of the chunk's keys into the blank of a staged copy of its slots; *hin: the slots to hash
+static int sig_msg_stage_z(ecamd_ctx *ctx, const ecsm2z::Prefix &P, uint32_t m, const uint8_t *d_keys, uint32_t plen, const uint8_t *d_in,
+			   uint32_t stride, uint32_t hl, const uint8_t **hin, hipStream_t s)
+{
+	uint8_t **S = ctx->stage;
+	HIPCHK(ecamd_launch_sm2_z(P, d_keys, plen, S[SM_Z], hl, m, s));
+	HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in, (size_t)m * stride, hipMemcpyDeviceToDevice, s));   // the caller's array is not modified
+	HIPCHK(ecamd_launch_slot_patch(S[ST_SLOTS], stride, 0, S[SM_Z], hl, S[SM_BAD], m, s));
+	*hin = S[ST_SLOTS];
+	return 0;
+}
+
+static int sig_msg_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_pub,
+				     const uint8_t *d_sig, const uint8_t *d_in, uint32_t stride, const ecsm2z::Prefix &P, uint8_t *d_res, hipStream_t s,
+				     const Between *between = nullptr)
+{
+	const size_t plen = (size_t)2 * cv->clen, sl = (size_t)2 * cv->qlen;
+	const uint32_t hl = (uint32_t)ecamd_hash_digest_len(hash_type), blank = alg == ECAMD_SIG_SM2 ? hl : 0u;
+	const bool sm2 = alg == ECAMD_SIG_SM2;
+	if (stride < 4u + blank) {   // no slot can hold the blank: every item is rejected
+		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
+		return 0;
+	}
+	const uint32_t chunk = chunk_items(ctx, n);
+	if (stage_need(ctx, {{ST_DIGESTS, (size_t)chunk * hl}, {SM_BAD, chunk}, {ST_SLOTS, sm2 ? (size_t)chunk * stride : 0}, {SM_Z, sm2 ? (size_t)chunk * hl : 0}})) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		const uint8_t *pub = d_pub + (size_t)off * plen, *in = d_in + (size_t)off * stride, *hin = in;
+		HIPCHK(ecamd_launch_sig_msg_bad(in, stride, blank, nullptr, S[SM_BAD], m, s));
+		if (sm2 && sig_msg_stage_z(ctx, P, m, pub, (uint32_t)plen, in, stride, hl, &hin, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_hash_slots(hash_type, hin, stride, m, S[ST_DIGESTS], hl, s));
+		if (ecdsa_verify_dev_locked(ctx, cv, m, pub, d_sig + (size_t)off * sl, S[ST_DIGESTS], hl, d_res + off, s,
+					    off + m == n ? between : nullptr, alg)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_reject_where(d_res + off, S[SM_BAD], m, s));
+		return 0;
+	});
+}
+
+static int sig_msg_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *d_privs,
+				   const uint8_t *d_pubs, const uint8_t *d_nonces, const uint8_t *d_in, uint32_t stride, const ecsm2z::Prefix &P,
+				   uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
+{
+	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen, sl = 2 * ql;
+	const uint32_t hl = (uint32_t)ecamd_hash_digest_len(hash_type), blank = alg == ECAMD_SIG_SM2 ? hl : 0u;
+	const bool sm2 = alg == ECAMD_SIG_SM2;
+	if (stride < 4u + blank) {
+		HIPCHK(hipMemsetAsync(d_sigs, 0, n * sl, s));
+		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
+		return 0;
+	}
+	const uint32_t chunk = chunk_items(ctx, n);
+	if (stage_need(ctx, {{ST_DIGESTS, (size_t)chunk * hl}, {SM_BAD, chunk}, {ST_SLOTS, sm2 ? (size_t)chunk * stride : 0}, {SM_Z, sm2 ? (size_t)chunk * hl : 0},
+			     {SG_Y, sm2 ? chunk * plen : 0}, {SG_STY, sm2 ? chunk : 0}})) {
+		return -1;
+	}
+	uint8_t **S = ctx->stage;
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		const uint8_t *in = d_in + (size_t)off * stride, *hin = in, *keys = nullptr;
+		// SM2: Y for Z, supplied (with its on-curve test) or [x]G by the fixed-base multiplication in the context's secret-scalar mode
+		if (sm2 && bip0340_keys_dev(ctx, cv, m, d_privs + off * ql, d_pubs ? d_pubs + off * plen : nullptr, &keys, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_sig_msg_bad(in, stride, blank, sm2 ? S[SG_STY] : nullptr, S[SM_BAD], m, s));
+		if (sm2 && sig_msg_stage_z(ctx, P, m, keys, (uint32_t)plen, in, stride, hl, &hin, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_hash_slots(hash_type, hin, stride, m, S[ST_DIGESTS], hl, s));
+		if (sig_sign_dev_locked(ctx, cv, alg, m, d_privs + off * ql, d_nonces + off * ql, S[ST_DIGESTS], hl, d_sigs + off * sl, d_status + off, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_sig_msg_reject_sign(d_sigs + off * sl, (uint32_t)sl, d_status + off, S[SM_BAD], m, s));
+		return 0;
+	});
+}
+
+extern "C" int ec_sig_verify_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
+					   const void *d_sigs, const void *d_msg_slots, uint32_t stride, const uint8_t *id, uint32_t id_len,
+					   void *d_result, void *hip_stream)
+{
+	ecsm2z::Prefix P;
+	if (sig_msg_args_ok("ec_sig_verify_msg_batch_dev", ctx, cv, alg, hash_type, stride, id, id_len)) {
+		return -1;
+	}
+	if (n && (!d_pubkeys || !d_sigs || !d_msg_slots || !d_result)) {
+		return fail("ec_sig_verify_msg_batch_dev: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
+		return -1;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return sig_msg_verify_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, (const uint8_t *)d_msg_slots,
+						 stride, P, (uint8_t *)d_result, s);
+	});
+}
+
+extern "C" int ec_sig_verify_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
+				       const uint8_t *sigs, const uint8_t *msg_slots, uint32_t stride, const uint8_t *id, uint32_t id_len,
+				       uint8_t *result)
+{
+	ecsm2z::Prefix P;
+	if (sig_msg_args_ok("ec_sig_verify_msg_batch", ctx, cv, alg, hash_type, stride, id, id_len)) {
+		return -1;
+	}
+	if (n && (!pubkeys || !sigs || !msg_slots || !result)) {
+		return fail("ec_sig_verify_msg_batch: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
+		return -1;
+	}
+	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, (size_t)2 * cv->qlen}, {msg_slots, nullptr, stride},
+					   {nullptr, result, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &between) {
+		return sig_msg_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, P, op[3], s, &between);
+	});
+}
+
+extern "C" int ec_sig_sign_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+					 const void *d_pubkeys, const void *d_nonces, const void *d_msg_slots, uint32_t stride, const uint8_t *id,
+					 uint32_t id_len, void *d_sigs, void *d_status, void *hip_stream)
+{
+	ecsm2z::Prefix P;
+	if (sig_msg_args_ok("ec_sig_sign_msg_batch_dev", ctx, cv, alg, hash_type, stride, id, id_len)) {
+		return -1;
+	}
+	if (n && (!d_privs || !d_nonces || !d_msg_slots || !d_sigs || !d_status)) {
+		return fail("ec_sig_sign_msg_batch_dev: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
+		return -1;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return sig_msg_sign_dev_locked(ctx, cv, alg, hash_type, n, (const uint8_t *)d_privs, alg == ECAMD_SIG_SM2 ? (const uint8_t *)d_pubkeys : nullptr,
+					       (const uint8_t *)d_nonces, (const uint8_t *)d_msg_slots, stride, P, (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_sig_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+				     const uint8_t *pubkeys, const uint8_t *nonces, const uint8_t *msg_slots, uint32_t stride, const uint8_t *id,
+				     uint32_t id_len, uint8_t *sigs, uint8_t *status)
+{
+	ecsm2z::Prefix P;
+	if (sig_msg_args_ok("ec_sig_sign_msg_batch", ctx, cv, alg, hash_type, stride, id, id_len)) {
+		return -1;
+	}
+	if (n && (!privs || !nonces || !msg_slots || !sigs || !status)) {
+		return fail("ec_sig_sign_msg_batch: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (sig_msg_prefix(cv, alg, hash_type, id, id_len, P)) {
+		return -1;
+	}
+	const size_t ql = (size_t)cv->qlen;
+	const bool with_keys = alg == ECAMD_SIG_SM2 && pubkeys;
+	std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {msg_slots, nullptr, stride}, {nullptr, sigs, 2 * ql}, {nullptr, status, 1}};
+	if (with_keys) {
+		arrs.push_back({pubkeys, nullptr, (size_t)2 * cv->clen});
+	}
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return sig_msg_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], with_keys ? ip[5] : nullptr, ip[1], ip[2], stride, P, op[3], op[4], s);
+	});
+}
+
+static int hash_slots_args_ok(const char *fn, ecamd_ctx *ctx, int hash_type, uint32_t n, const void *slots, uint32_t stride, const void *out)
+{
+	if (ecamd_hash_digest_len(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224 / 256 / 384 / 512), 11 (SM3), 13 or 14 (Streebog-256 / -512)");
+	}
+	if (stride < 4 || (stride & 3u) || stride > 4096) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	if (!ctx || (n && (!slots || !out))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	return 0;
+}
+
+static int hash_slots_dev_locked(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *d_slots, uint32_t stride, uint8_t *d_out, hipStream_t s)
+{
+	const uint32_t hl = (uint32_t)ecamd_hash_digest_len(hash_type);
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		HIPCHK(ecamd_launch_hash_slots(hash_type, d_slots + (size_t)off * stride, stride, m, d_out + (size_t)off * hl, hl, s));
+		return 0;
+	});
+}
+
+extern "C" int ec_hash_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_msg_slots, uint32_t stride, void *d_digests,
+				       void *hip_stream)
+{
+	if (hash_slots_args_ok("ec_hash_slots_batch_dev", ctx, hash_type, n, d_msg_slots, stride, d_digests)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return hash_slots_dev_locked(ctx, hash_type, n, (const uint8_t *)d_msg_slots, stride, (uint8_t *)d_digests, s);
+	});
+}
+
+extern "C" int ec_hash_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *msg_slots, uint32_t stride, uint8_t *digests)
+{
+	if (hash_slots_args_ok("ec_hash_slots_batch", ctx, hash_type, n, msg_slots, stride, digests)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const std::vector<HostArr> arrs = {{msg_slots, nullptr, stride}, {nullptr, digests, (size_t)ecamd_hash_digest_len(hash_type)}};
+	return host_call(ctx, 256, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return hash_slots_dev_locked(ctx, hash_type, m, ip[0], stride, op[1], s);
+	});
+}
+

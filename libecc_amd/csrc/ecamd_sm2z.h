@@ -1,6 +1,6 @@
 // libecc_amd/csrc/ecamd_sm2z.h -- SM2's Z = H(ENTL || ID || a || b || xG || yG || xY || yY) per item (GB/T 32918.2, sig/sm2.c:121-205
 // of libecc), for the message-level SM2 entry points: H is SM3 (ecamd_sm3.h) or SHA-224 / 256 / 384 / 512 (the compression of
-// ecamd_rfc6979.h).  Compiles for the device (k_sm2_z, ecamd_hash2.hip) and for the host (ecamd_host.cpp, tests/sighash2_host_shim.cpp).
+// ecamd_rfc6979.h).  Compiles for the device (k_sm2_z, ecamd_hash2.hip) and for the host (ecamd_host_sigfam.cpp, tests/sighash2_host_shim.cpp).
 //
 // Everything but the key is the same for every item of a call, so the host absorbs the whole blocks of the PREFIX
 // ENTL || ID || a || b || xG || yG once (prefix_init) and hands the kernel the midstate and the octets left over (less than one

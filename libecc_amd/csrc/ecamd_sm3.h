@@ -1,7 +1,7 @@
 // libecc_amd/csrc/ecamd_sm3.h -- SM3 (GB/T 32905-2016), the hash SM2 is specified with, per item: the compression function, the
 // padding, a one-shot over a message held as little-endian words (the slot format of ecamd_hash.hip) and a streamed form (init,
 // absorb whole blocks, finish) for inputs that share a prefix (SM2's Z, ecamd_sm2z.h).  Compiles for the device (ecamd_hash2.hip:
-// one item per lane) and for the host (ecamd_host.cpp: the prefix midstate; tests/sighash2_host_shim.cpp).
+// one item per lane) and for the host (ecamd_host_sigfam.cpp: the prefix midstate; tests/sighash2_host_shim.cpp).
 //
 // Written from the standard's definitions, on 32-bit big-endian words:
 //

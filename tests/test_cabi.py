@@ -39,6 +39,18 @@ def test_fails_loudly_without_gpu():
         libecc_amd.Context(0)
 
 
+def test_host_helpers_stay_out_of_the_dynamic_symbol_table():
+    """what the host units share (namespace ecamd_host, csrc/ecamd_host_internal.h) is hidden: the library exports none of it"""
+    import shutil
+    import subprocess
+    lib = os.path.join(ROOT, "libecc_amd", "lib", "libecc_amd.so")
+    if not os.path.exists(lib) or shutil.which("nm") is None:
+        pytest.skip("the library is not built, or there is no nm")
+    out = subprocess.check_output(["nm", "-D", "--defined-only", lib], text=True)
+    leaked = [ln.split()[-1] for ln in out.splitlines() if ln.split() and "10ecamd_host" in ln.split()[-1]]
+    assert leaked == []
+
+
 def test_product_does_not_touch_the_oracle():
     """the product tree must not reference oracle/ (parity claims are void otherwise)"""
     for dirpath, _, files in os.walk(os.path.join(ROOT, "libecc_amd")):
