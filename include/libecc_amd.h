@@ -318,8 +318,9 @@ int ec_sig_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_
  * ec_hash_slots_batch is the bare hash: n x hsize digests of the slots (for 11, 13, 14 a slot that does not fit its stride gets
  * an all-zero digest; 1 .. 4 run the kernel of ec_ecdsa_verify_msg_batch_fmt, which hashes what fits).
  * Key rules, n = 0, NULL arguments, foreign handles, chunking by ecamd_ctx_set_max_chunk as ec_decdsa_sign_batch; ecamd_ctx_wipe_scratch
- * covers the staged slots.  Not here: SHA-3, SHA-512/t, RIPEMD-160 and BASH on the device, the ecamd_multi_* wrappers, the
- * libecc-typed boundary (libsign_amd), and ECKCDSA's z prefix.
+ * covers the staged slots.  Not here: SHA-3, SHA-512/t, RIPEMD-160 and BASH in these message-level calls (the device hashes them
+ * through ec_digest_slots_batch below, in front of the digest-level _dev forms), the ecamd_multi_* wrappers, the libecc-typed
+ * boundary (libsign_amd), and ECKCDSA's z prefix.
  */
 int ec_sig_verify_msg_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys_aff,
 			    const uint8_t *sigs, const uint8_t *msg_slots, uint32_t stride, const uint8_t *id, uint32_t id_len,
@@ -336,6 +337,35 @@ int ec_sig_sign_msg_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg,
 int ec_hash_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *msg_slots, uint32_t stride, uint8_t *digests);
 int ec_hash_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_msg_slots, uint32_t stride, void *d_digests,
 			    void *hip_stream);
+/*
+ * The bare hash over the WHOLE table: every fixed-length hash of libecc's hash_alg_type except belt-hash, on the device, of the same
+ * message slots (a little-endian u32 length, then the bytes; stride a multiple of 4 in 4 .. 4096).
+ *   hash_type  1 .. 4 (SHA-224 / 256 / 384 / 512), 5 .. 8 (SHA3-224 / 256 / 384 / 512), 9, 10 (SHA-512/224, SHA-512/256), 11 (SM3),
+ *              13, 14 (Streebog-256 / -512), 15 (RIPEMD-160), 17 .. 20 (BASH224 / 256 / 384 / 512, STB 34.101.77).  Not served:
+ *              0, 12 (SHAKE256 is no fixed-length hash here; Ed448's entry points use it), 16 (belt-hash: ec_bign_* hash with it
+ *              themselves) and anything outside 1 .. 20.
+ *   digests    n x ecamd_digest_len(hash_type) octets, the bytes libecc's hfunc_* produce.  ecamd_digest_len: 28 .. 64, 20 for
+ *              RIPEMD-160, 0 for a number that is not served.
+ *   a slot that does not fit its stride (4 + length > stride) gets an all-zero digest, for EVERY served number (ec_hash_slots_batch
+ *              with 1 .. 4 hashes what fits instead).
+ * The older entry points keep the hash sets they accept -- ec_hash_slots_batch, ec_sig_*_msg_batch, ec_bign_*, ec_dbign_*, ec_bip0340_*,
+ * ec_decdsa_*, ec_rfc6979_* and the rest refuse 5 .. 10, 15 and 17 .. 20 as before, a behaviour their callers and tests rely on.  The
+ * new hashes reach the protocols by COMPOSITION on the device: ec_digest_slots_batch_dev into a device buffer, then the digest-level
+ * _dev call on the same stream -- ec_ecdsa_verify_batch_dev / ec_ecdsa_sign_batch_dev, ec_sig_verify_batch_dev / ec_sig_sign_batch_dev
+ * (digest_len = ecamd_digest_len), ec_bign_verify_batch_dev / ec_bign_sign_batch_dev and ec_dbign_sign_batch_dev with hash_type 0 and
+ * stride = the digest length.  The digests never leave device memory.  That is how BIGN runs with BASH384 on bign384v1 and BASH512 on
+ * bign512v1, the standard's configuration, and ECDSA with SHA-3.
+ * Everything hashed is public: nothing differs under ecamd_ctx_set_secret_scalars.  n = 0, NULL arguments, foreign handles, chunking
+ * by ecamd_ctx_set_max_chunk, and the _dev form only enqueueing, as ec_hash_slots_batch[_dev]; any other hash_type or stride is a
+ * call-level error (-1, ecamd_last_error()).
+ * Out of scope: the accepted hash sets of every existing entry point; HMAC / RFC 6979 over the new hashes; SM2's Z, the commitment
+ * hashes of ECSDSA / ECOSDSA / ECKCDSA / BIP0340 / ECFSDSA and EdDSA with the new hashes; SHAKE256 as a fixed-length hash (12); the
+ * ecamd_multi_* wrappers and the libecc-typed layer.
+ */
+int ecamd_digest_len(int hash_type);
+int ec_digest_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *msg_slots, uint32_t stride, uint8_t *digests);
+int ec_digest_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_msg_slots, uint32_t stride, void *d_digests,
+			      void *hip_stream);
 /*
  * ECSDSA, ECOSDSA and ECKCDSA: the schemes of libecc's table that hash AFTER the multiplication.  The verifier computes
  * W' = [u]G + [v]Y, hashes its affine coordinates on the device and compares the digest with the signature's r byte for byte; the

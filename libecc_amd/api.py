@@ -32,6 +32,7 @@ EXPORTED_SYMBOLS = [
     "ec_sig_verify_batch", "ec_sig_verify_batch_dev", "ec_sig_sign_batch", "ec_sig_sign_batch_dev",
     "ec_sig_verify_msg_batch", "ec_sig_verify_msg_batch_dev", "ec_sig_sign_msg_batch", "ec_sig_sign_msg_batch_dev",
     "ec_hash_slots_batch", "ec_hash_slots_batch_dev",
+    "ecamd_digest_len", "ec_digest_slots_batch", "ec_digest_slots_batch_dev",
     "ec_sig_hashed_verify_batch", "ec_sig_hashed_verify_batch_dev", "ec_sig_hashed_sign_batch", "ec_sig_hashed_sign_batch_dev",
     "ec_schnorr_verify_batch", "ec_schnorr_verify_batch_dev", "ec_schnorr_sign_batch", "ec_schnorr_sign_batch_dev",
     "ec_bign_verify_batch", "ec_bign_verify_batch_dev", "ec_bign_sign_batch", "ec_bign_sign_batch_dev",
@@ -57,6 +58,9 @@ HASH_BELT = 16
 HASH_SIZES = {1: 28, 2: 32, 3: 48, 4: 64}          # libecc's hash_alg_type numbers of SHA-224 / 256 / 384 / 512
 HASH_SM3, HASH_STREEBOG256, HASH_STREEBOG512 = 11, 13, 14
 HASH_SLOT_SIZES = {**HASH_SIZES, 11: 32, 13: 32, 14: 64}   # what ec_hash_slots_batch and the message-level ec_sig_* calls hash with
+# what ec_digest_slots_batch hashes with: every fixed-length hash of libecc's table but belt-hash -- beside the seven above SHA3-224 /
+# 256 / 384 / 512 (5 .. 8), SHA-512/224 and /256 (9, 10), RIPEMD-160 (15) and BASH224 / 256 / 384 / 512 (17 .. 20)
+DIGEST_SIZES = {**HASH_SLOT_SIZES, 5: 28, 6: 32, 7: 48, 8: 64, 9: 28, 10: 32, 15: 20, 17: 28, 18: 32, 19: 48, 20: 64}
 
 
 class EcamdError(RuntimeError):
@@ -142,6 +146,9 @@ def load_library():
         L.ec_sig_sign_msg_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, vp, u32, u8p, u32, vp, vp, vp]
         L.ec_hash_slots_batch.argtypes = [vp, C.c_int, u32, u8p, u32, u8p]
         L.ec_hash_slots_batch_dev.argtypes = [vp, C.c_int, u32, vp, u32, vp, vp]
+        L.ecamd_digest_len.argtypes = [C.c_int]
+        L.ec_digest_slots_batch.argtypes = [vp, C.c_int, u32, u8p, u32, u8p]
+        L.ec_digest_slots_batch_dev.argtypes = [vp, C.c_int, u32, vp, u32, vp, vp]
         L.ec_sig_hashed_verify_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p]
         L.ec_sig_hashed_sign_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u8p]
         L.ec_sig_hashed_verify_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, vp, vp]
@@ -243,6 +250,18 @@ class Context:
 
     def hash_slots_dev(self, hash_type, n, d_slots, stride, d_digests, stream=None):
         _chk(self.L, self.L.ec_hash_slots_batch_dev(self.h, hash_type, n, d_slots, stride, d_digests, stream), "ec_hash_slots_batch_dev")
+
+    def digest_slots(self, hash_type, slots, stride):
+        """the bare device hash of message slots over the whole table (DIGEST_SIZES): n x digest size bytes; a slot that does not fit
+        its stride gives zeros"""
+        n = len(slots) // stride
+        dl = DIGEST_SIZES.get(hash_type, 0)
+        out = C.create_string_buffer(max(1, n * dl))
+        _chk(self.L, self.L.ec_digest_slots_batch(self.h, hash_type, n, slots, stride, out), "ec_digest_slots_batch")
+        return out.raw[:n * dl]
+
+    def digest_slots_dev(self, hash_type, n, d_slots, stride, d_digests, stream=None):
+        _chk(self.L, self.L.ec_digest_slots_batch_dev(self.h, hash_type, n, d_slots, stride, d_digests, stream), "ec_digest_slots_batch_dev")
 
     def set_secret_scalars(self, on=True):
         _chk(self.L, self.L.ecamd_ctx_set_secret_scalars(self.h, 1 if on else 0), "ecamd_ctx_set_secret_scalars")

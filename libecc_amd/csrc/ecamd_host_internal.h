@@ -3,7 +3,8 @@
 // The units:
 //   ecamd_host.cpp         errors, host big integers, the context, curve handles, scratch sizing, host_pipeline and the heads of the entry
 //                          points, scalar multiplication and point operations, ECDSA and its relatives, XDH, EdDSA, the whole-batch forms
-//   ecamd_host_sigfam.cpp  ECKCDSA / ECSDSA / ECOSDSA, BIGN / DBIGN, BIP0340 / ECFSDSA, message-level ECGDSA / ECRDSA / SM2, ec_hash_slots_*
+//   ecamd_host_sigfam.cpp  ECKCDSA / ECSDSA / ECOSDSA, BIGN / DBIGN, BIP0340 / ECFSDSA, message-level ECGDSA / ECRDSA / SM2, ec_hash_slots_*,
+//                          ec_digest_slots_*
 // A protocol family lives in exactly one unit.  This header declares only what more than one unit uses; what one unit needs stays
 // `static` in its file.  The shared functions are in namespace ecamd_host with hidden visibility: none of them enters the library's
 // dynamic symbol table.

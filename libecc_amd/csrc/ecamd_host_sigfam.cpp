@@ -1405,3 +1405,60 @@ extern "C" int ec_hash_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, co
 	});
 }
 
+// ec_digest_slots_batch (include/libecc_amd.h): the bare hash over the whole table, ecamd_hash3.hip.  The calls above keep their sets.
+static int digest_slots_args_ok(const char *fn, ecamd_ctx *ctx, int hash_type, uint32_t n, const void *slots, uint32_t stride, const void *out)
+{
+	if (ecamd_digest_len_any(hash_type) == 0) {
+		return fail(std::string(fn) + ": hash_type must be 1 .. 11, 13 .. 15 or 17 .. 20 (every fixed-length hash of libecc's table but belt-hash)");
+	}
+	if (stride < 4 || (stride & 3u) || stride > 4096) {
+		return fail(std::string(fn) + ": stride must be a multiple of 4 in 4 .. 4096");
+	}
+	if (!ctx || (n && (!slots || !out))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	return 0;
+}
+
+static int digest_slots_dev_locked(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *d_slots, uint32_t stride, uint8_t *d_out, hipStream_t s)
+{
+	const uint32_t dl = (uint32_t)ecamd_digest_len_any(hash_type);
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		HIPCHK(ecamd_launch_digest_slots(hash_type, d_slots + (size_t)off * stride, stride, m, d_out + (size_t)off * dl, dl, s));
+		return 0;
+	});
+}
+
+extern "C" int ecamd_digest_len(int hash_type)
+{
+	return ecamd_digest_len_any(hash_type);
+}
+
+extern "C" int ec_digest_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_msg_slots, uint32_t stride, void *d_digests,
+					 void *hip_stream)
+{
+	if (digest_slots_args_ok("ec_digest_slots_batch_dev", ctx, hash_type, n, d_msg_slots, stride, d_digests)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return digest_slots_dev_locked(ctx, hash_type, n, (const uint8_t *)d_msg_slots, stride, (uint8_t *)d_digests, s);
+	});
+}
+
+extern "C" int ec_digest_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *msg_slots, uint32_t stride, uint8_t *digests)
+{
+	if (digest_slots_args_ok("ec_digest_slots_batch", ctx, hash_type, n, msg_slots, stride, digests)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const std::vector<HostArr> arrs = {{msg_slots, nullptr, stride}, {nullptr, digests, (size_t)ecamd_digest_len_any(hash_type)}};
+	return host_call(ctx, 256, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return digest_slots_dev_locked(ctx, hash_type, m, ip[0], stride, op[1], s);
+	});
+}
+

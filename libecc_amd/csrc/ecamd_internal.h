@@ -814,6 +814,11 @@ hipError_t ecamd_launch_streebog_slots(int hash_type, const uint8_t *slots, uint
 // one door to the slot hashes: hash_type 1 .. 4 (SHA-2), 11 (SM3), 13, 14 (Streebog-256 / -512); the digest length is 0 for any other
 int ecamd_hash_digest_len(int hash_type);
 hipError_t ecamd_launch_hash_slots(int hash_type, const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s);
+// the whole table of fixed-length hashes (ecamd_hash3.hip): the seven numbers above through their launchers, and 5 .. 8 (SHA3-224 / 256 /
+// 384 / 512), 9, 10 (SHA-512/224, SHA-512/256), 15 (RIPEMD-160), 17 .. 20 (BASH224 / 256 / 384 / 512); the digest length is 0 for 0, 12,
+// 16 and anything outside 1 .. 20.  Here EVERY number gives an all-zero digest for a slot whose length does not fit its stride.
+int ecamd_digest_len_any(int hash_type);
+hipError_t ecamd_launch_digest_slots(int hash_type, const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s);
 // SM2's Z per item from the call's prefix (ecamd_sm2z.h) and the keys' 2 clen octets, hsize octets each into z
 namespace ecsm2z { struct Prefix; }
 hipError_t ecamd_launch_sm2_z(const ecsm2z::Prefix &P, const uint8_t *keys, uint32_t klen, uint8_t *z, uint32_t hsize, uint32_t n, hipStream_t s);

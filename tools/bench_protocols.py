@@ -6,7 +6,7 @@ torch.distributed.run, weak scaling, contiguous shards, one RCCL all-gather of t
 bytes per step); not the driver's headline bench.  --workload ecdsa_recover is the exception: one GPU, recovery beside the
 verification of the same signatures in alternating windows (recover_row).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|sig_msg_verify|sig_msg_sign|hash_slots [--alg sm2|ecrdsa|ecgdsa --hash 11|13|14|2 --curve C]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..4 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|sig_msg_verify|sig_msg_sign|hash_slots [--alg sm2|ecrdsa|ecgdsa --hash 11|13|14|2 --curve C]|digest_slots [--hash 1..11|13..15|17..20]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..4 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -201,6 +201,54 @@ def sig_family_row(a, ctx, dev, stream, rng, B):
                       "family_over_ecdsa": me / mf, "gate": gate,
                       "config": {"workload": a.workload, "alg": a.alg, "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
     cv.free()
+    ctx.close()
+
+
+def digest_slots_row(a, ctx, dev, stream, rng, B):
+    """--workload digest_slots: the bare slot hash over the whole table (ec_digest_slots_batch_dev, --hash 1 .. 11, 13 .. 15, 17 .. 20)
+    beside SHA-256 of the same slots through the same call, in alternating windows of a.steps calls: ns per item at 32-octet messages,
+    inputs resident in HBM.  Gate: the digests of the first 64 slots equal the host's (hashlib) where hashlib offers the hash.  One
+    GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload digest_slots measures one GPU: run it with --gpus 1, outside torch.distributed.run")
+    ht = a.hash
+    hl = libecc_amd.api.DIGEST_SIZES.get(ht)
+    if hl is None:
+        raise SystemExit("--workload digest_slots: --hash 1 .. 11, 13 .. 15 or 17 .. 20")
+    mlen, stride = 32, 36
+    sl = np.zeros((B, stride), dtype=np.uint8)
+    sl[:, 0] = mlen
+    sl[:, 4:] = rng.integers(0, 256, size=(B, mlen), dtype=np.uint8)
+    d_sl = torch.frombuffer(bytearray(sl.tobytes()), dtype=torch.uint8).to(dev)
+    d_a, d_b = torch.empty(hl * B, dtype=torch.uint8, device=dev), torch.empty(32 * B, dtype=torch.uint8, device=dev)
+    fns = [lambda: ctx.digest_slots_dev(ht, B, d_sl.data_ptr(), stride, d_a.data_ptr(), stream.cuda_stream),
+           lambda: ctx.digest_slots_dev(2, B, d_sl.data_ptr(), stride, d_b.data_ptr(), stream.cuda_stream)]
+    for _ in range(max(1, a.warmup)):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    names = {1: "sha224", 2: "sha256", 3: "sha384", 4: "sha512", 5: "sha3_224", 6: "sha3_256", 7: "sha3_384", 8: "sha3_512", 9: "sha512_224",
+             10: "sha512_256", 11: "sm3", 15: "ripemd160"}
+    gate = "not checked: hashlib does not offer this hash"
+    if names.get(ht) in hashlib.algorithms_available:
+        got = bytes(d_a[:64 * hl].cpu().numpy())
+        if got != b"".join(hashlib.new(names[ht], sl[i, 4:].tobytes()).digest() for i in range(64)):
+            raise SystemExit("PARITY FAILURE: the device's digests differ from hashlib's")
+        gate = "the first 64 digests equal hashlib's"
+    acc = [[], []]
+    for _ in range(3):
+        for fn, ac in zip(fns, acc):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            ac.append((time.perf_counter() - t0) / a.steps)
+    ma, mb = float(np.median(acc[0])), float(np.median(acc[1]))
+    print(json.dumps({"metric": "hash_type %d of 2^%d slots of 32-octet messages, ns per item (device-resident)" % (ht, a.batch_log2),
+                      "value": 1e9 * ma / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[0]],
+                      "sha256_same_run": {"value": 1e9 * mb / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[1]]},
+                      "gate": gate,
+                      "config": {"workload": a.workload, "hash": ht, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
     ctx.close()
 
 
@@ -1015,13 +1063,13 @@ def eddsa_sign_row(a, ctx, dev, stream, rng, B):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_msg_verify", "sig_msg_sign", "hash_slots", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_msg_verify", "sig_msg_sign", "hash_slots", "digest_slots", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
     ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa",
                                                     "ed25519", "ed25519ctx", "ed25519ph", "ed448", "ed448ph"],
                     help="eddsa_sign: ed25519, ed25519ctx, ed25519ph, ed448, ed448ph; sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
-    ap.add_argument("--hash", type=int, default=None, choices=[0, 1, 2, 3, 4, 11, 13, 14, 16],
+    ap.add_argument("--hash", type=int, default=None, choices=[0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 14, 15, 16, 17, 18, 19, 20],
                     help="bign_verify / bign_sign: 0 the caller hashed (SHA-256 digests supplied), 16 (default) belt-hash of message slots on the device; "
-                         "decdsa_sign: 1 .. 4, SHA-224 / 256 (default) / 384 / 512")
+                         "decdsa_sign: 1 .. 4, SHA-224 / 256 (default) / 384 / 512; digest_slots: any of libecc's numbers but 0 and 16 (default 6, SHA3-256)")
     ap.add_argument("--secret", action="store_true", help="dbign_sign / bip0340_sign: the context in secret-scalar mode")
     ap.add_argument("--derive-pub", action="store_true", help="eddsa_sign: pubkeys = NULL, A = encode([a]B) derived on the device (a second comb multiplication per item)")
     ap.add_argument("--gpus", type=int, default=1)
@@ -1038,6 +1086,8 @@ def main():
     a = ap.parse_args()
     if a.hash is None and a.workload in ("sig_msg_verify", "sig_msg_sign", "hash_slots"):
         a.hash = {"sm2": 11, "ecrdsa": 13, "ecgdsa": 2}.get(a.alg, 11)   # the hash each scheme is deployed with
+    if a.hash is None and a.workload == "digest_slots":
+        a.hash = 6
     if a.hash is None:
         a.hash = 2 if a.workload == "decdsa_sign" else 16
     # the option means something to these workloads only; the others ignore it, as they always have
@@ -1083,6 +1133,8 @@ def main():
         return sig_family_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("sig_msg_verify", "sig_msg_sign", "hash_slots"):
         return sig_msg_row(a, ctx, dev, stream, rng, B)
+    if a.workload == "digest_slots":
+        return digest_slots_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("sig_hashed_verify", "sig_hashed_sign"):
         return sig_hashed_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("schnorr_verify", "schnorr_sign"):
