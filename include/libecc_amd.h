@@ -358,7 +358,8 @@ int ec_hash_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const voi
  * Everything hashed is public: nothing differs under ecamd_ctx_set_secret_scalars.  n = 0, NULL arguments, foreign handles, chunking
  * by ecamd_ctx_set_max_chunk, and the _dev form only enqueueing, as ec_hash_slots_batch[_dev]; any other hash_type or stride is a
  * call-level error (-1, ecamd_last_error()).
- * Out of scope: the accepted hash sets of every existing entry point; HMAC / RFC 6979 over the new hashes; SM2's Z, the commitment
+ * Out of scope: the accepted hash sets of every existing entry point (HMAC and RFC 6979 over the whole table have entry points of
+ * their own: ec_hmac_slots_batch, ec_rfc6979_nonce_ht_batch, ec_decdsa_sign_ht_batch); SM2's Z, the commitment
  * hashes of ECSDSA / ECOSDSA / ECKCDSA / BIP0340 / ECFSDSA and EdDSA with the new hashes; SHAKE256 as a fixed-length hash (12); the
  * ecamd_multi_* wrappers and the libecc-typed layer.
  */
@@ -522,6 +523,44 @@ int ec_rfc6979_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_ty
 			   const uint8_t *digests, uint8_t *nonces, uint8_t *status);
 int ec_decdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *in,
 			 uint32_t in_stride, int in_is_digest, uint8_t *sigs, uint8_t *status);
+/* HMAC and deterministic ECDSA over the WHOLE hash table: libecc's hmac() (hash/hmac.c) and _ec_sign(DECDSA) with any fixed-length hash
+ * of hash_alg_type, where the HMAC of __ecdsa_rfc6979_nonce runs through the hash of the message.  Unlike the digest-first schemes this
+ * cannot be composed from ec_digest_slots_batch: the HMAC sits between the private key and the multiplication.
+ *   hash_type  the set of ec_digest_slots_batch: 1 .. 11, 13 .. 15, 17 .. 20.  0, 12 (SHAKE256), 16 (belt-hash) and anything else is a
+ *              call-level error (-1, ecamd_last_error()).  The HMAC's block sizes are libecc's block_size fields: 64 / 64 / 128 / 128
+ *              (SHA-2), 144 / 136 / 104 / 72 (SHA-3), 128 (SHA-512/t), 64 (SM3, Streebog, RIPEMD-160), 136 / 128 / 96 / 64 (BASH).
+ *   ec_hmac_slots_batch   macs[i] = HMAC(key i, message i), n x ecamd_digest_len(hash_type) octets.  Keys and messages are slots in the
+ *              format of ec_digest_slots_batch (a little-endian u32 length, then the bytes), key_stride and stride multiples of 4 in
+ *              4 .. 4096.  A key longer than the block is hashed first, as in hmac_init.  A key slot or a message slot that does not
+ *              fit its stride gets an all-zero MAC (ec_digest_slots_batch's rule).
+ *   ec_rfc6979_nonce_ht_batch, ec_decdsa_sign_ht_batch   ec_rfc6979_nonce_batch and ec_decdsa_sign_batch, argument for argument, for
+ *              every hash_type above: digests n x hsize with hsize = ecamd_digest_len(hash_type) (20 for RIPEMD-160: T then takes
+ *              ceil(qlen / 20) values of V, four on a 521-bit order); in_is_digest with in_stride = hsize; message slots hashed on the
+ *              device by the kernels of ec_digest_slots_batch; a slot that does not fit is status 1 with zero bytes; x = 0 signs,
+ *              x >= q is status 1; the reference's restart conditions are status 1; qlen <= 66; the derived nonces stay in a wiped
+ *              scratch buffer.  hash_type 1 .. 4 run the kernel of the older names: the same bytes at the same speed.  The older
+ *              names keep refusing 5 .. 20.  A signature verifies by the composition documented at ec_digest_slots_batch:
+ *              ec_digest_slots_batch_dev, then ec_ecdsa_verify_batch_dev.
+ * SECRET-SCALAR MODE.  Streebog's table look-ups are indexed by state octets, and in these three calls the state depends on the HMAC
+ * key or the private key.  A scan of a 16 KiB table per look-up is not offered: after ecamd_ctx_set_secret_scalars(ctx, 1) all three
+ * calls (and their _dev forms) refuse hash_type 13 and 14 with a call-level -1, and ecamd_last_error() says why.  Every other served
+ * hash looks nothing up by data; its kernels are the same in both modes.  [k]G honours the mode as in ec_decdsa_sign_batch.
+ * n = 0 (returns 0, touches nothing), NULL arguments, a handle of another context (-1) and chunking by ecamd_ctx_set_max_chunk as for
+ * ec_decdsa_sign_batch; the _dev forms take device pointers and only enqueue on hip_stream (NULL: the context's stream).
+ * Out of scope: the ecamd_multi_* wrappers, the libecc-typed layer (libsign_amd), belt-hash, and the commitment schemes (ECSDSA,
+ * ECOSDSA, ECKCDSA, BIP0340, ECFSDSA) with the new hashes. */
+int ec_hmac_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *key_slots, uint32_t key_stride,
+			const uint8_t *msg_slots, uint32_t stride, uint8_t *macs);
+int ec_hmac_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_key_slots, uint32_t key_stride,
+			    const void *d_msg_slots, uint32_t stride, void *d_macs, void *hip_stream);
+int ec_rfc6979_nonce_ht_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs,
+			      const uint8_t *digests, uint8_t *nonces, uint8_t *status);
+int ec_rfc6979_nonce_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs,
+				  const void *d_digests, void *d_nonces, void *d_status, void *hip_stream);
+int ec_decdsa_sign_ht_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *in,
+			    uint32_t in_stride, int in_is_digest, uint8_t *sigs, uint8_t *status);
+int ec_decdsa_sign_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs, const void *d_in,
+				uint32_t in_stride, int in_is_digest, void *d_sigs, void *d_status, void *hip_stream);
 /* Deterministic BIGN (DBIGN, libecc's ec_alg_type 19) with the nonce of STB 34.101.45 section 6.3.3 derived ON THE DEVICE, as the
  * reference's __bign_determinitic_nonce runs it (sig/bign_common.c:200-342), its non-standard choices included.
  *   ec_dbign_nonce_batch   privs n x qlen big-endian, digests n x digest_len (H(m), digest_len in 1 .. 128); nonces n x qlen big-endian.

@@ -37,6 +37,8 @@ EXPORTED_SYMBOLS = [
     "ec_schnorr_verify_batch", "ec_schnorr_verify_batch_dev", "ec_schnorr_sign_batch", "ec_schnorr_sign_batch_dev",
     "ec_bign_verify_batch", "ec_bign_verify_batch_dev", "ec_bign_sign_batch", "ec_bign_sign_batch_dev",
     "ec_rfc6979_nonce_batch", "ec_rfc6979_nonce_batch_dev", "ec_decdsa_sign_batch", "ec_decdsa_sign_batch_dev",
+    "ec_hmac_slots_batch", "ec_hmac_slots_batch_dev", "ec_rfc6979_nonce_ht_batch", "ec_rfc6979_nonce_ht_batch_dev",
+    "ec_decdsa_sign_ht_batch", "ec_decdsa_sign_ht_batch_dev",
     "ec_eddsa_sign_msg_batch", "ec_eddsa_sign_msg_batch_dev", "ec_eddsa_pub_key_batch", "ec_eddsa_pub_key_batch_dev",
     "ec_dbign_nonce_batch", "ec_dbign_nonce_batch_dev", "ec_dbign_sign_batch", "ec_dbign_sign_batch_dev",
     "ec_bip0340_nonce_batch", "ec_bip0340_nonce_batch_dev", "ec_bip0340_sign_batch", "ec_bip0340_sign_batch_dev",
@@ -171,6 +173,12 @@ def load_library():
         L.ec_rfc6979_nonce_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, vp, vp]
         L.ec_decdsa_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u32, C.c_int, u8p, u8p]
         L.ec_decdsa_sign_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u32, C.c_int, vp, vp, vp]
+        L.ec_hmac_slots_batch.argtypes = [vp, C.c_int, u32, u8p, u32, u8p, u32, u8p]
+        L.ec_hmac_slots_batch_dev.argtypes = [vp, C.c_int, u32, vp, u32, vp, u32, vp, vp]
+        L.ec_rfc6979_nonce_ht_batch.argtypes = L.ec_rfc6979_nonce_batch.argtypes
+        L.ec_rfc6979_nonce_ht_batch_dev.argtypes = L.ec_rfc6979_nonce_batch_dev.argtypes
+        L.ec_decdsa_sign_ht_batch.argtypes = L.ec_decdsa_sign_batch.argtypes
+        L.ec_decdsa_sign_ht_batch_dev.argtypes = L.ec_decdsa_sign_batch_dev.argtypes
         L.ec_dbign_nonce_batch.argtypes = [vp, vp, u32, u8p, u8p, u32, u8p, u32, u8p, u32, u8p, u8p]
         L.ec_dbign_nonce_batch_dev.argtypes = [vp, vp, u32, vp, vp, u32, u8p, u32, u8p, u32, vp, vp, vp]
         L.ec_dbign_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u32, u8p, u32, u8p, u32, u8p, u8p]
@@ -262,6 +270,19 @@ class Context:
 
     def digest_slots_dev(self, hash_type, n, d_slots, stride, d_digests, stream=None):
         _chk(self.L, self.L.ec_digest_slots_batch_dev(self.h, hash_type, n, d_slots, stride, d_digests, stream), "ec_digest_slots_batch_dev")
+
+    def hmac_slots(self, hash_type, key_slots, key_stride, msg_slots, stride):
+        """HMAC over any hash of DIGEST_SIZES of n (key slot, message slot) pairs: n x digest size bytes; a key or a message that does
+        not fit its slot gives zeros"""
+        n = len(msg_slots) // stride
+        dl = DIGEST_SIZES.get(hash_type, 0)
+        out = C.create_string_buffer(max(1, n * dl))
+        _chk(self.L, self.L.ec_hmac_slots_batch(self.h, hash_type, n, key_slots, key_stride, msg_slots, stride, out), "ec_hmac_slots_batch")
+        return out.raw[:n * dl]
+
+    def hmac_slots_dev(self, hash_type, n, d_key_slots, key_stride, d_msg_slots, stride, d_macs, stream=None):
+        _chk(self.L, self.L.ec_hmac_slots_batch_dev(self.h, hash_type, n, d_key_slots, key_stride, d_msg_slots, stride, d_macs, stream),
+             "ec_hmac_slots_batch_dev")
 
     def set_secret_scalars(self, on=True):
         _chk(self.L, self.L.ecamd_ctx_set_secret_scalars(self.h, 1 if on else 0), "ecamd_ctx_set_secret_scalars")
@@ -600,6 +621,21 @@ class Curve:
              "ec_decdsa_sign_batch")
         return sigs.raw[:2 * self.qlen * n], st.raw[:n]
 
+    def rfc6979_nonce_ht(self, hash_type, privs, digests):
+        """rfc6979_nonce with HMAC over any hash of DIGEST_SIZES (digests: n x DIGEST_SIZES[hash_type])"""
+        n = len(privs) // self.qlen
+        out, st = C.create_string_buffer(max(1, self.qlen * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_rfc6979_nonce_ht_batch(self.ctx.h, self.h, hash_type, n, privs, digests, out, st), "ec_rfc6979_nonce_ht_batch")
+        return out.raw[:self.qlen * n], st.raw[:n]
+
+    def decdsa_sign_ht(self, hash_type, privs, inputs, stride, is_digest):
+        """decdsa_sign with any hash of DIGEST_SIZES as the message hash and the HMAC's hash"""
+        n = len(privs) // self.qlen
+        sigs, st = C.create_string_buffer(max(1, 2 * self.qlen * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_decdsa_sign_ht_batch(self.ctx.h, self.h, hash_type, n, privs, inputs, stride, 1 if is_digest else 0, sigs, st),
+             "ec_decdsa_sign_ht_batch")
+        return sigs.raw[:2 * self.qlen * n], st.raw[:n]
+
     def dbign_nonce(self, privs, digests, digest_len, oid, t=b""):
         """the nonces of deterministic BIGN (STB 34.101.45 section 6.3.3) derived on the device from the digests of the messages
         (digest_len octets each), the OID of their hash and the optional additional data t: (n x qlen big-endian, status)"""
@@ -861,6 +897,14 @@ class Curve:
     def decdsa_sign_dev(self, hash_type, n, d_privs, d_in, stride, is_digest, d_sigs, d_status, stream=None):
         _chk(self.L, self.L.ec_decdsa_sign_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_in, stride, 1 if is_digest else 0, d_sigs,
                                                       d_status, stream), "ec_decdsa_sign_batch_dev")
+
+    def rfc6979_nonce_ht_dev(self, hash_type, n, d_privs, d_digests, d_nonces, d_status, stream=None):
+        _chk(self.L, self.L.ec_rfc6979_nonce_ht_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_digests, d_nonces, d_status, stream),
+             "ec_rfc6979_nonce_ht_batch_dev")
+
+    def decdsa_sign_ht_dev(self, hash_type, n, d_privs, d_in, stride, is_digest, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_decdsa_sign_ht_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_in, stride, 1 if is_digest else 0, d_sigs,
+                                                         d_status, stream), "ec_decdsa_sign_ht_batch_dev")
 
     def dbign_nonce_dev(self, n, d_privs, d_digests, digest_len, oid, t, d_nonces, d_status, stream=None):
         _chk(self.L, self.L.ec_dbign_nonce_batch_dev(self.ctx.h, self.h, n, d_privs, d_digests, digest_len, oid, len(oid), t, len(t), d_nonces,

@@ -2607,9 +2607,9 @@ extern "C" int ec_ecdsa_verify_msg_batch_fmt(ecamd_ctx *ctx, const ecamd_curve *
 // batched ECDSA signing with caller-supplied nonces
 // ------------------------------------------------------------------------------------------
 // Device core of ECDSA signing: every pointer a device pointer; kG and its status live in SG_KG, SG_STKG.
-static int ecdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_privs,
-				 const uint8_t *d_nonces, const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs,
-				 uint8_t *d_status, hipStream_t s)
+int ecamd_host::ecdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_privs,
+				      const uint8_t *d_nonces, const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs,
+				      uint8_t *d_status, hipStream_t s)
 {
 	const size_t plen = (size_t)2 * cv->clen, ql = (size_t)cv->qlen;
 	if (n > ctx->max_chunk) {  // bound the scratch: pieces of max_chunk items, in order on the stream

@@ -4,7 +4,7 @@
 //   ecamd_host.cpp         errors, host big integers, the context, curve handles, scratch sizing, host_pipeline and the heads of the entry
 //                          points, scalar multiplication and point operations, ECDSA and its relatives, XDH, EdDSA, the whole-batch forms
 //   ecamd_host_sigfam.cpp  ECKCDSA / ECSDSA / ECOSDSA, BIGN / DBIGN, BIP0340 / ECFSDSA, message-level ECGDSA / ECRDSA / SM2, ec_hash_slots_*,
-//                          ec_digest_slots_*
+//                          ec_digest_slots_*, HMAC and deterministic ECDSA over the whole hash table (ec_hmac_slots_*, ec_*_ht_*)
 // A protocol family lives in exactly one unit.  This header declares only what more than one unit uses; what one unit needs stays
 // `static` in its file.  The shared functions are in namespace ecamd_host with hidden visibility: none of them enters the library's
 // dynamic symbol table.
@@ -65,7 +65,7 @@ int fail(const std::string &m);   // files the thread's error string (ecamd_last
 //   VP_  secp256r1 loop       3..5, 7       ecdsa_verify_dev_locked (ST_U, ST_V and VP_*); its redo pass is the ST_ frame, after it   ST_TARGET, EF_
 //   RC_  recovery             10..14        ecdsa_recover_dev_locked, on top of ST_U .. ST_FLAGS (it has no [q]Y pass and no W' of its own)
 //   SG_  signing              3..5, 7, 20   ecdsa_ / sig_ / hsig_ / bign_ / schnorr_item_sign_dev_locked, ec_ecdsa_sign_msg_batch,
-//                                           decdsa_sign_ / dbign_sign_ / bip0340_dev_locked (SG_NONCES)   ST_FLAGS, ST_SLOTS, ST_DIGESTS, ST_BELT
+//                                           decdsa_sign_ / decdsa_ht_ / dbign_sign_ / bip0340_dev_locked (SG_NONCES)   ST_FLAGS, ST_SLOTS, ST_DIGESTS, ST_BELT
 //   EV_  EdDSA verification   3..15, 18, 19 eddsa_verify_dev_locked, eddsa448_verify_dev_locked, eddsa448_msm_dev_locked   ST_DIGESTS (h), EP_, EB_, MH_
 //   SR_  EdDSA [r]B           3..5          eddsa_sign_R_dev_locked                                ES_ (it runs inside the one-call signing)
 //   EN_  EdDSA point encoding 3, 4          ec_eddsa_encode_point_batch                            nothing
@@ -321,6 +321,9 @@ int verify_sum_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, const uint
 int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_pub,
 			    const uint8_t *d_sig, const uint8_t *d_dig, uint32_t hlen, uint8_t *d_res, hipStream_t s,
 			    const Between *between = nullptr, int alg = SIG_ECDSA);
+// ECDSA signing with given nonces (SG_ frame: [k]G as the context's secret-scalar mode says, then r and s)
+int ecdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
+			  const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s);
 int sig_alg_ok(const char *fn, int alg);
 int sig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
 			const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s);

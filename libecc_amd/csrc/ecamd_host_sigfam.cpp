@@ -1462,3 +1462,234 @@ extern "C" int ec_digest_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, 
 	});
 }
 
+
+// ------------------------------------------------------------------------------------------
+// HMAC and deterministic ECDSA over the whole hash table (include/libecc_amd.h: ec_hmac_slots_batch, ec_rfc6979_nonce_ht_batch,
+// ec_decdsa_sign_ht_batch; ecamd_hmac.hip).  The _ht forms are ec_rfc6979_nonce_batch and ec_decdsa_sign_batch with every hash of
+// ec_digest_slots_batch; 1 .. 4 run the kernel of the older names.  Per chunk of at most max_chunk items signing is
+//   ecamd_launch_digest_slots   in_is_digest = 0: h1 = H(m) into ST_DIGESTS (a slot that does not fit: zeros)
+//   k_rfc6979_nonce[_ht]        k into SG_NONCES (secret: ensure() wipes what it frees, ecamd_ctx_wipe_scratch the rest); a slot whose
+//                               length does not fit gets k = 0
+//   ecdsa_sign_dev_locked       [k]G as the context's secret-scalar mode says, r, s; k = 0 is status 1 with zero bytes
+// Streebog's look-ups are indexed by key-dependent octets: the three calls refuse 13 and 14 in secret-scalar mode.  Only enqueues.
+// ------------------------------------------------------------------------------------------
+static const char *const HT_SET = "hash_type must be 1 .. 11, 13 .. 15 or 17 .. 20 (every fixed-length hash of libecc's table but belt-hash)";
+
+static int ht_hash_ok(const char *fn, const ecamd_ctx *ctx, int hash_type)
+{
+	if (!ecamd_hmac_served(hash_type)) {
+		return fail(std::string(fn) + ": " + HT_SET);
+	}
+	if (ctx && ctx->secret_scalars && (hash_type == 13 || hash_type == 14)) {
+		return fail(std::string(fn) + ": Streebog (hash_type 13, 14) looks its table up by octets that depend on the secret: refused in secret-scalar mode");
+	}
+	return 0;
+}
+
+static int hmac_slots_args_ok(const char *fn, ecamd_ctx *ctx, int hash_type, uint32_t n, const void *keys, uint32_t key_stride, const void *msgs,
+			      uint32_t stride, const void *macs)
+{
+	if (ht_hash_ok(fn, ctx, hash_type)) {
+		return -1;
+	}
+	if (key_stride < 4 || (key_stride & 3u) || key_stride > 4096 || stride < 4 || (stride & 3u) || stride > 4096) {
+		return fail(std::string(fn) + ": key_stride and stride must be multiples of 4 in 4 .. 4096");
+	}
+	if (!ctx || (n && (!keys || !msgs || !macs))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	return 0;
+}
+
+static int hmac_slots_dev_locked(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *d_keys, uint32_t key_stride, const uint8_t *d_msgs,
+				 uint32_t stride, uint8_t *d_macs, hipStream_t s)
+{
+	const uint32_t dl = (uint32_t)ecamd_digest_len_any(hash_type);
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		HIPCHK(ecamd_launch_hmac_slots(hash_type, d_keys + (size_t)off * key_stride, key_stride, d_msgs + (size_t)off * stride, stride, m,
+					       d_macs + (size_t)off * dl, s));
+		return 0;
+	});
+}
+
+extern "C" int ec_hmac_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_key_slots, uint32_t key_stride,
+				       const void *d_msg_slots, uint32_t stride, void *d_macs, void *hip_stream)
+{
+	if (hmac_slots_args_ok("ec_hmac_slots_batch_dev", ctx, hash_type, n, d_key_slots, key_stride, d_msg_slots, stride, d_macs)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return hmac_slots_dev_locked(ctx, hash_type, n, (const uint8_t *)d_key_slots, key_stride, (const uint8_t *)d_msg_slots, stride,
+					     (uint8_t *)d_macs, s);
+	});
+}
+
+extern "C" int ec_hmac_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *key_slots, uint32_t key_stride,
+				   const uint8_t *msg_slots, uint32_t stride, uint8_t *macs)
+{
+	if (hmac_slots_args_ok("ec_hmac_slots_batch", ctx, hash_type, n, key_slots, key_stride, msg_slots, stride, macs)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const std::vector<HostArr> arrs = {{key_slots, nullptr, key_stride}, {msg_slots, nullptr, stride},
+					   {nullptr, macs, (size_t)ecamd_digest_len_any(hash_type)}};
+	return host_call(ctx, 256, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return hmac_slots_dev_locked(ctx, hash_type, m, ip[0], key_stride, ip[1], stride, op[2], s);
+	});
+}
+
+static int rfc6979_ht_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type)
+{
+	if (ht_hash_ok(fn, ctx, hash_type)) {
+		return -1;
+	}
+	if (!ctx || !cv || cv->ctx != ctx) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0 || big_bitlen(cv->q) < 2 || cv->q.size() > 17 || cv->qlen > ecrfc::MAX_QLEN ||
+	    (uint32_t)cv->qlen != ((uint32_t)cv->qbits + 7) / 8) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	return 0;
+}
+
+static int rfc6979_ht_nonce_dev_locked(const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_digests,
+				       const uint8_t *d_slots, uint32_t stride, uint8_t *d_nonces, uint8_t *d_status, hipStream_t s)
+{
+	EcamdRfc6979Args R;
+	memset(&R, 0, sizeof(R));
+	R.privs = d_privs;
+	R.digests = d_digests;
+	R.slots = d_slots;
+	R.stride = stride;
+	R.nonces = d_nonces;
+	R.status = d_status;
+	R.n = n;
+	R.qlen = (uint32_t)cv->qlen;
+	R.qbits = (uint32_t)cv->qbits;
+	for (int w = 0; w < 17; w++) {
+		R.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
+	}
+	HIPCHK(ecamd_launch_rfc6979_nonce_ht(hash_type, R, s));
+	return 0;
+}
+
+extern "C" int ec_rfc6979_nonce_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
+					     const void *d_digests, void *d_nonces, void *d_status, void *hip_stream)
+{
+	if (rfc6979_ht_args_ok("ec_rfc6979_nonce_ht_batch_dev", ctx, cv, hash_type)) {
+		return -1;
+	}
+	if (n && (!d_privs || !d_digests || !d_nonces || !d_status)) {
+		return fail("ec_rfc6979_nonce_ht_batch_dev: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		const size_t ql = (size_t)cv->qlen, dl = (size_t)ecamd_digest_len_any(hash_type);
+		return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+			return rfc6979_ht_nonce_dev_locked(cv, hash_type, m, (const uint8_t *)d_privs + off * ql, (const uint8_t *)d_digests + off * dl, nullptr, 0,
+							   (uint8_t *)d_nonces + off * ql, (uint8_t *)d_status + off, s);
+		});
+	});
+}
+
+extern "C" int ec_rfc6979_nonce_ht_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+					 const uint8_t *digests, uint8_t *nonces, uint8_t *status)
+{
+	if (rfc6979_ht_args_ok("ec_rfc6979_nonce_ht_batch", ctx, cv, hash_type)) {
+		return -1;
+	}
+	if (n && (!privs || !digests || !nonces || !status)) {
+		return fail("ec_rfc6979_nonce_ht_batch: bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t ql = (size_t)cv->qlen, dl = (size_t)ecamd_digest_len_any(hash_type);
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {digests, nullptr, dl}, {nullptr, nonces, ql}, {nullptr, status, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return for_chunks(ctx, m, [&](uint32_t off, uint32_t c) -> int {
+			return rfc6979_ht_nonce_dev_locked(cv, hash_type, c, ip[0] + off * ql, ip[1] + off * dl, nullptr, 0, op[2] + off * ql, op[3] + off, s);
+		});
+	});
+}
+
+static int decdsa_ht_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_in,
+				     uint32_t stride, int in_is_digest, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
+{
+	const size_t ql = (size_t)cv->qlen;
+	const uint32_t hlen = (uint32_t)ecamd_digest_len_any(hash_type);
+	const size_t chunk = chunk_items(ctx, n);
+	if (stage_need(ctx, {{SG_NONCES, chunk * ql}, {ST_DIGESTS, in_is_digest ? 0 : chunk * hlen}})) {
+		return -1;
+	}
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		const uint8_t *in = d_in + (size_t)off * stride, *d_dig = in;
+		if (!in_is_digest) {
+			HIPCHK(ecamd_launch_digest_slots(hash_type, in, stride, m, ctx->stage[ST_DIGESTS], hlen, s));
+			d_dig = ctx->stage[ST_DIGESTS];
+		}
+		// (the nonce kernel's status lands in the caller's status bytes and is replaced by the signing core's: a zero nonce is status 1 there)
+		if (rfc6979_ht_nonce_dev_locked(cv, hash_type, m, d_privs + off * ql, d_dig, in_is_digest ? nullptr : in, stride, ctx->stage[SG_NONCES],
+						d_status + off, s)) {
+			return -1;
+		}
+		return ecdsa_sign_dev_locked(ctx, cv, m, d_privs + off * ql, ctx->stage[SG_NONCES], d_dig, hlen, d_sigs + off * 2 * ql, d_status + off, s);
+	});
+}
+
+static int decdsa_ht_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *a, const void *b,
+			     uint32_t stride, int in_is_digest, const void *c, const void *d)
+{
+	if (rfc6979_ht_args_ok(fn, ctx, cv, hash_type)) {
+		return -1;
+	}
+	if (in_is_digest != 0 && in_is_digest != 1) {
+		return fail(std::string(fn) + ": in_is_digest must be 0 or 1");
+	}
+	if (in_is_digest ? stride != (uint32_t)ecamd_digest_len_any(hash_type) : (stride < 4 || (stride & 3u) || stride > 4096)) {
+		return fail(std::string(fn) + ": in_stride must be the digest length (in_is_digest = 1) or a multiple of 4 in 4 .. 4096 (message slots)");
+	}
+	if (n && (!a || !b || !c || !d)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	return 0;
+}
+
+extern "C" int ec_decdsa_sign_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs, const void *d_in,
+					   uint32_t in_stride, int in_is_digest, void *d_sigs, void *d_status, void *hip_stream)
+{
+	if (decdsa_ht_args_ok("ec_decdsa_sign_ht_batch_dev", ctx, cv, hash_type, n, d_privs, d_in, in_stride, in_is_digest, d_sigs, d_status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return decdsa_ht_sign_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_in, in_stride, in_is_digest,
+						 (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_decdsa_sign_ht_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *in,
+				       uint32_t in_stride, int in_is_digest, uint8_t *sigs, uint8_t *status)
+{
+	if (decdsa_ht_args_ok("ec_decdsa_sign_ht_batch", ctx, cv, hash_type, n, privs, in, in_stride, in_is_digest, sigs, status)) {
+		return -1;
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {in, nullptr, in_stride}, {nullptr, sigs, 2 * ql}, {nullptr, status, 1}};
+	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
+		return decdsa_ht_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], in_stride, in_is_digest, op[2], op[3], s);
+	});
+}

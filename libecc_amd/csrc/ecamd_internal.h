@@ -695,6 +695,14 @@ struct EcamdRfc6979Args {
 	uint32_t q[17];          // the generator's order, little-endian words
 };
 hipError_t ecamd_launch_rfc6979_nonce(int hash_type, const EcamdRfc6979Args &a, hipStream_t s);
+// the same nonce with HMAC over any hash of ecamd_launch_digest_slots (ecamd_hmac.h / ecamd_hmac.hip: k_rfc6979_nonce_ht<ID>); 1 .. 4 launch
+// k_rfc6979_nonce
+hipError_t ecamd_launch_rfc6979_nonce_ht(int hash_type, const EcamdRfc6979Args &a, hipStream_t s);
+// HMAC of n (key slot, message slot) pairs (k_hmac_slots<ID>): both in the slot format of ecamd_launch_digest_slots, macs n x the digest length;
+// a key or a message that does not fit its slot gives an all-zero MAC.  hash_type: what ecamd_digest_len_any serves.
+int ecamd_hmac_served(int hash_type);
+hipError_t ecamd_launch_hmac_slots(int hash_type, const uint8_t *keys, uint32_t kstride, const uint8_t *msgs, uint32_t stride, uint32_t n, uint8_t *macs,
+				   hipStream_t s);
 // the nonce of deterministic BIGN (STB 34.101.45 section 6.3.3, ecamd_dbign_nonce.h / ecamd_detnonce.hip: k_dbign_nonce)
 struct EcamdDbignNonceArgs {
 	const uint8_t *privs;    // n x qlen big-endian

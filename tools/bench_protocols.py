@@ -6,7 +6,7 @@ torch.distributed.run, weak scaling, contiguous shards, one RCCL all-gather of t
 bytes per step); not the driver's headline bench.  --workload ecdsa_recover is the exception: one GPU, recovery beside the
 verification of the same signatures in alternating windows (recover_row).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|sig_msg_verify|sig_msg_sign|hash_slots [--alg sm2|ecrdsa|ecgdsa --hash 11|13|14|2 --curve C]|digest_slots [--hash 1..11|13..15|17..20]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..4 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|sig_msg_verify|sig_msg_sign|hash_slots [--alg sm2|ecrdsa|ecgdsa --hash 11|13|14|2 --curve C]|digest_slots|hmac_slots [--hash 1..11|13..15|17..20]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..11|13..15|17..20 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -247,6 +247,60 @@ def digest_slots_row(a, ctx, dev, stream, rng, B):
     print(json.dumps({"metric": "hash_type %d of 2^%d slots of 32-octet messages, ns per item (device-resident)" % (ht, a.batch_log2),
                       "value": 1e9 * ma / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[0]],
                       "sha256_same_run": {"value": 1e9 * mb / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[1]]},
+                      "gate": gate,
+                      "config": {"workload": a.workload, "hash": ht, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+    ctx.close()
+
+
+def hmac_slots_row(a, ctx, dev, stream, rng, B):
+    """--workload hmac_slots: ec_hmac_slots_batch_dev (--hash 1 .. 11, 13 .. 15, 17 .. 20) of 32-octet keys and 32-octet messages beside
+    the bare hash of the same message slots (ec_digest_slots_batch_dev of the same hash), between HIP events in alternating windows of
+    a.steps calls: ns per item, inputs resident in HBM.  Gate: the first 64 MACs equal hmac.new's where hashlib offers the hash.  One
+    GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload hmac_slots measures one GPU: run it with --gpus 1, outside torch.distributed.run")
+    import hmac
+    ht = a.hash
+    hl = libecc_amd.api.DIGEST_SIZES.get(ht)
+    if hl is None:
+        raise SystemExit("--workload hmac_slots: --hash 1 .. 11, 13 .. 15 or 17 .. 20")
+    stride = 36
+    sls = []
+    for _ in range(2):
+        sl = np.zeros((B, stride), dtype=np.uint8)
+        sl[:, 0] = 32
+        sl[:, 4:] = rng.integers(0, 256, size=(B, 32), dtype=np.uint8)
+        sls.append(sl)
+    d_k, d_m = (torch.frombuffer(bytearray(sl.tobytes()), dtype=torch.uint8).to(dev) for sl in sls)
+    d_a, d_b = torch.empty(hl * B, dtype=torch.uint8, device=dev), torch.empty(hl * B, dtype=torch.uint8, device=dev)
+    fns = [lambda: ctx.hmac_slots_dev(ht, B, d_k.data_ptr(), stride, d_m.data_ptr(), stride, d_a.data_ptr(), stream.cuda_stream),
+           lambda: ctx.digest_slots_dev(ht, B, d_m.data_ptr(), stride, d_b.data_ptr(), stream.cuda_stream)]
+    for _ in range(max(1, a.warmup)):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    names = {1: "sha224", 2: "sha256", 3: "sha384", 4: "sha512", 5: "sha3_224", 6: "sha3_256", 7: "sha3_384", 8: "sha3_512", 9: "sha512_224",
+             10: "sha512_256", 11: "sm3", 15: "ripemd160"}
+    gate = "not checked: hashlib does not offer this hash"
+    if names.get(ht) in hashlib.algorithms_available:
+        got = bytes(d_a[:64 * hl].cpu().numpy())
+        if got != b"".join(hmac.new(sls[0][i, 4:].tobytes(), sls[1][i, 4:].tobytes(), names[ht]).digest() for i in range(64)):
+            raise SystemExit("PARITY FAILURE: the device's MACs differ from hmac.new's")
+        gate = "the first 64 MACs equal hmac.new's"
+    acc = [[], []]
+    for _ in range(3):
+        for fn, ac in zip(fns, acc):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(a.steps):
+                fn()
+            e1.record(stream)
+            torch.cuda.synchronize()
+            ac.append(e0.elapsed_time(e1) / 1e3 / a.steps)
+    ma, mb = float(np.median(acc[0])), float(np.median(acc[1]))
+    print(json.dumps({"metric": "HMAC with hash_type %d of 2^%d pairs of 32-octet keys and messages, ns per item (device-resident)" % (ht, a.batch_log2),
+                      "value": 1e9 * ma / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[0]],
+                      "bare_hash_same_run": {"value": 1e9 * mb / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[1]]},
                       "gate": gate,
                       "config": {"workload": a.workload, "hash": ht, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
     ctx.close()
@@ -752,16 +806,20 @@ def decdsa_row(a, ctx, dev, stream, rng, B):
     """Deterministic ECDSA (ec_decdsa_sign_batch_dev on digests: the nonce of RFC 6979 derived on the device, then the signing core)
     beside ec_ecdsa_sign_batch_dev with SUPPLIED nonces on the same keys and digests, in the same run, in alternating windows of
     a.steps calls; and the nonce kernel by itself (ec_rfc6979_nonce_batch_dev) between HIP events.  --hash 1 .. 4: the SHA-2 of the
-    digests and of the HMAC.  Gates: the nonces the device derives are the Python restatement's on --ref-items random items, the
+    digests and of the HMAC; any other number of ec_digest_slots_batch goes through ec_decdsa_sign_ht_batch_dev and
+    ec_rfc6979_nonce_ht_batch_dev, and the row then also holds the bare hash of 32-octet message slots (ec_digest_slots_batch_dev of the
+    same hash, one block per item) measured in the same windows: the yardstick for the nonce kernel's time per compression.
+    Gates: the nonces the device derives are the Python restatement's on --ref-items random items (where hashlib has the hash), the
     signatures are those of the supplied-nonce call fed with them, and every signature is accepted.  One GPU only."""
     if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
         raise SystemExit("--workload decdsa_sign measures one GPU: run it with --gpus 1, outside torch.distributed.run")
     import oracles as O
-    import decdsa_ref as D
+    import hmac_ht_ref as M
     curve = a.curve
-    hname = {1: "SHA224", 2: "SHA256", 3: "SHA384", 4: "SHA512"}[a.hash]
+    ht = a.hash >= 5
+    hname = {i: name for name, i in M.HASH_IDS.items()}[a.hash]
     cv = ctx.curve(curve)
-    q, ql, hl = O.CURVES[curve]["q"], O.qlen(curve), D.HSIZE[hname]
+    q, ql, hl = O.CURVES[curve]["q"], O.qlen(curve), M.HASH_SIZES[hname]
     raw = rng.integers(0, 256, size=(B, ql + 8), dtype=np.uint8)
     privs = b"".join(((int.from_bytes(raw[i].tobytes(), "big") % (q - 1)) + 1).to_bytes(ql, "big") for i in range(B))
     dgs = rng.integers(0, 256, size=B * hl, dtype=np.uint8).tobytes()       # digests of messages nobody needs to know
@@ -776,11 +834,20 @@ def decdsa_row(a, ctx, dev, stream, rng, B):
     d_st, d_st2, d_res = (torch.empty(B, dtype=torch.uint8, device=dev) for _ in range(3))
     sp = stream.cuda_stream
 
+    sl = np.zeros((B, 36), dtype=np.uint8)
+    sl[:, 0] = 32
+    sl[:, 4:] = rng.integers(0, 256, size=(B, 32), dtype=np.uint8)
+    d_sl, d_bare = t(sl.tobytes()), torch.empty(B * hl, dtype=torch.uint8, device=dev)
+
     def nonces():
-        cv.rfc6979_nonce_dev(a.hash, B, d_x.data_ptr(), d_dg.data_ptr(), d_k.data_ptr(), d_st.data_ptr(), sp)
+        (cv.rfc6979_nonce_ht_dev if ht else cv.rfc6979_nonce_dev)(a.hash, B, d_x.data_ptr(), d_dg.data_ptr(), d_k.data_ptr(), d_st.data_ptr(), sp)
 
     def decdsa():
-        cv.decdsa_sign_dev(a.hash, B, d_x.data_ptr(), d_dg.data_ptr(), hl, True, d_sig.data_ptr(), d_st.data_ptr(), sp)
+        (cv.decdsa_sign_ht_dev if ht else cv.decdsa_sign_dev)(a.hash, B, d_x.data_ptr(), d_dg.data_ptr(), hl, True, d_sig.data_ptr(),
+                                                              d_st.data_ptr(), sp)
+
+    def bare():
+        ctx.digest_slots_dev(a.hash, B, d_sl.data_ptr(), 36, d_bare.data_ptr(), sp)
 
     def supplied():
         cv.ecdsa_sign_dev(B, d_x.data_ptr(), d_k.data_ptr(), d_dg.data_ptr(), hl, d_sig2.data_ptr(), d_st2.data_ptr(), sp)
@@ -792,8 +859,10 @@ def decdsa_row(a, ctx, dev, stream, rng, B):
         raise SystemExit("PARITY FAILURE: a nonce was not derived")
     idx = [int(i) for i in np.sort(np.random.default_rng(2).choice(B, size=min(B, max(1, a.ref_items)), replace=False))]
     retries = 0
+    if not M.have_hashlib(hname):
+        idx = []
     for i in idx:
-        k, r = D.nonce_from_digest(curve, hname, privs[ql * i:ql * (i + 1)], dgs[hl * i:hl * (i + 1)])
+        k, r = M.py_nonce(curve, hname, privs[ql * i:ql * (i + 1)], dgs[hl * i:hl * (i + 1)])
         retries += r
         if k.to_bytes(ql, "big") != ks[ql * i:ql * (i + 1)]:
             raise SystemExit("PARITY FAILURE: item %d's nonce is not the restatement's" % i)
@@ -811,9 +880,17 @@ def decdsa_row(a, ctx, dev, stream, rng, B):
         supplied()
         decdsa()
         nonces()
+        bare()
     torch.cuda.synchronize()
-    ts, td, tn = [], [], []
+    ts, td, tn, tb = [], [], [], []
     for _ in range(3):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(stream)
+        for _ in range(a.steps):
+            bare()
+        e1.record(stream)
+        torch.cuda.synchronize()
+        tb.append(e0.elapsed_time(e1) / 1e3 / a.steps)
         for fn, acc in ((supplied, ts), (decdsa, td)):
             t0 = time.perf_counter()
             for _ in range(a.steps):
@@ -834,6 +911,7 @@ def decdsa_row(a, ctx, dev, stream, rng, B):
                       "supplied_nonces_same_run": {"value": B / ms, "unit": "signatures/s", "ms": [1e3 * x for x in ts]},
                       "decdsa_over_supplied": ms / md,
                       "nonce_kernel": {"ms": [1e3 * x for x in tn], "ns_per_item": 1e9 * mn / B, "items_per_s": B / mn},
+                      "bare_hash_one_block": {"ms": [1e3 * x for x in tb], "ns_per_item": 1e9 * float(np.median(tb)) / B},
                       "gate": gate,
                       "config": {"workload": a.workload, "hash": a.hash, "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
     cv.free()
@@ -1063,13 +1141,13 @@ def eddsa_sign_row(a, ctx, dev, stream, rng, B):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_msg_verify", "sig_msg_sign", "hash_slots", "digest_slots", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_msg_verify", "sig_msg_sign", "hash_slots", "digest_slots", "hmac_slots", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
     ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa",
                                                     "ed25519", "ed25519ctx", "ed25519ph", "ed448", "ed448ph"],
                     help="eddsa_sign: ed25519, ed25519ctx, ed25519ph, ed448, ed448ph; sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
     ap.add_argument("--hash", type=int, default=None, choices=[0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 14, 15, 16, 17, 18, 19, 20],
                     help="bign_verify / bign_sign: 0 the caller hashed (SHA-256 digests supplied), 16 (default) belt-hash of message slots on the device; "
-                         "decdsa_sign: 1 .. 4, SHA-224 / 256 (default) / 384 / 512; digest_slots: any of libecc's numbers but 0 and 16 (default 6, SHA3-256)")
+                         "decdsa_sign: SHA-256 by default, 1 .. 4 through ec_decdsa_sign_batch, the rest through ec_decdsa_sign_ht_batch; digest_slots, hmac_slots: any of libecc's numbers but 0 and 16 (default 6, SHA3-256)")
     ap.add_argument("--secret", action="store_true", help="dbign_sign / bip0340_sign: the context in secret-scalar mode")
     ap.add_argument("--derive-pub", action="store_true", help="eddsa_sign: pubkeys = NULL, A = encode([a]B) derived on the device (a second comb multiplication per item)")
     ap.add_argument("--gpus", type=int, default=1)
@@ -1086,13 +1164,13 @@ def main():
     a = ap.parse_args()
     if a.hash is None and a.workload in ("sig_msg_verify", "sig_msg_sign", "hash_slots"):
         a.hash = {"sm2": 11, "ecrdsa": 13, "ecgdsa": 2}.get(a.alg, 11)   # the hash each scheme is deployed with
-    if a.hash is None and a.workload == "digest_slots":
+    if a.hash is None and a.workload in ("digest_slots", "hmac_slots"):
         a.hash = 6
     if a.hash is None:
         a.hash = 2 if a.workload == "decdsa_sign" else 16
     # the option means something to these workloads only; the others ignore it, as they always have
-    if a.workload == "decdsa_sign" and a.hash not in (1, 2, 3, 4):
-        raise SystemExit("--workload decdsa_sign: --hash 1 .. 4")
+    if a.workload == "decdsa_sign" and a.hash in (0, 16):
+        raise SystemExit("--workload decdsa_sign: --hash 1 .. 11, 13 .. 15 or 17 .. 20")
     if a.workload in ("bign_verify", "bign_sign") and a.hash not in (0, 16):
         raise SystemExit("--workload %s: --hash 0 or 16" % a.workload)
     rank = int(os.environ.get("RANK", "0"))
@@ -1135,6 +1213,8 @@ def main():
         return sig_msg_row(a, ctx, dev, stream, rng, B)
     if a.workload == "digest_slots":
         return digest_slots_row(a, ctx, dev, stream, rng, B)
+    if a.workload == "hmac_slots":
+        return hmac_slots_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("sig_hashed_verify", "sig_hashed_sign"):
         return sig_hashed_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("schnorr_verify", "schnorr_sign"):
