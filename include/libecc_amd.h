@@ -547,8 +547,8 @@ int ec_decdsa_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type
  * hash looks nothing up by data; its kernels are the same in both modes.  [k]G honours the mode as in ec_decdsa_sign_batch.
  * n = 0 (returns 0, touches nothing), NULL arguments, a handle of another context (-1) and chunking by ecamd_ctx_set_max_chunk as for
  * ec_decdsa_sign_batch; the _dev forms take device pointers and only enqueue on hip_stream (NULL: the context's stream).
- * Out of scope: the ecamd_multi_* wrappers, the libecc-typed layer (libsign_amd), belt-hash, and the commitment schemes (ECSDSA,
- * ECOSDSA, ECKCDSA, BIP0340, ECFSDSA) with the new hashes. */
+ * Out of scope: the ecamd_multi_* wrappers, the libecc-typed layer (libsign_amd) and belt-hash; the commitment schemes (ECSDSA,
+ * ECOSDSA, ECKCDSA, BIP0340, ECFSDSA) have their own _ht names below. */
 int ec_hmac_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *key_slots, uint32_t key_stride,
 			const uint8_t *msg_slots, uint32_t stride, uint8_t *macs);
 int ec_hmac_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_key_slots, uint32_t key_stride,
@@ -605,6 +605,67 @@ int ec_bip0340_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_ty
 int ec_bip0340_sign_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs,
 			  const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
 			  uint8_t *status);
+/* ECKCDSA / ECSDSA / ECOSDSA / ECFSDSA / BIP0340 OVER THE WHOLE HASH TABLE.  These five schemes hash AFTER their multiplication: the
+ * hash input holds the commitment (r = H(Wx || Wy || m), H(Wx || m), H(FE2OS(Wx)); e = H(Wx || Wy || m); e = H(H(tag) || H(tag) || r ||
+ * Yx || m) and the two tagged hashes of BIP0340's nonce), which exists only inside the call, so they cannot be composed from
+ * ec_digest_slots_batch the way ECDSA, BIGN, ECGDSA, ECRDSA and SM2 can.  The reference sets no limit on the hash beyond
+ * digest_size <= MAX_DIGEST_SIZE and block_size <= MAX_BLOCK_SIZE (sig/ecsdsa_common.c:79, sig/eckcdsa.c:90, sig/ecfsdsa.c:68,
+ * sig/bip0340.c:143).  Each name below is the name without _ht, argument for argument: slot formats, blanks, status and result rules,
+ * chunking, n = 0, NULL and foreign-handle behaviour are those documented there.  What differs:
+ *   hash_type  the set of ec_digest_slots_batch: 1 .. 11, 13 .. 15, 17 .. 20.  0, 12 (SHAKE256), 16 (belt-hash) and anything else is a
+ *              call-level error (-1, ecamd_last_error()).
+ *   lengths    hsize = ecamd_digest_len(hash_type), 20 for RIPEMD-160.  ECSDSA / ECOSDSA: r_len = hsize; ECKCDSA: r_len = min(hsize,
+ *              qlen) -- with hsize < qlen (RIPEMD-160 on every curve here, any 64-octet hash on a 521-bit order) r is the whole digest
+ *              and nothing is truncated.  Signatures are r_len + qlen octets.  ECKCDSA's inputs are digests h = H(z || m) of hsize
+ *              octets (stride = hsize).  BIP0340's slot carries 2 hsize octets of tag hashes in front of r.  e is the WHOLE digest mod q
+ *              for every hsize beside every qlen.
+ *   1 .. 4     run the kernels the names without _ht run: the same bytes at the same speed.  Those names keep refusing 5 .. 20.
+ *   ec_bip0340_nonce_ht_batch, ec_bip0340_sign_ht_batch   t = (d || 0 ..) ^ (mask || 0 ..) over max(qlen, hsize) octets (hsize 20 beside
+ *              qlen 66 at the extreme); both tagged hashes and the challenge use hash_type.
+ * ECKCDSA from messages without leaving the device.  z is the first BLOCK octets (libecc's block_size of the hash: 64 / 64 / 128 / 128
+ * SHA-2, 144 / 136 / 104 / 72 SHA-3, 128 SHA-512/t, 64 SM3, Streebog, RIPEMD-160, 136 / 128 / 96 / 64 BASH) of the caller's own
+ * public-key octets Yx || Yy, zero-padded when 2 clen < BLOCK.  The caller lays out slots `u32 length | z | m`, runs
+ * ec_digest_slots_batch_dev(ctx, hash_type, n, d_slots, stride, d_h, stream) and hands d_h to
+ * ec_sig_hashed_verify_ht_batch_dev(ctx, curve, ECAMD_SIG_ECKCDSA, hash_type, n, d_pubkeys, d_sigs, d_h, hsize, d_result, stream) (or to
+ * the signing call) on the same stream: h never leaves device memory.
+ * SECRET-SCALAR MODE.  ec_bip0340_nonce_ht_batch and ec_bip0340_sign_ht_batch (and their _dev forms) refuse Streebog (hash_type 13, 14)
+ * after ecamd_ctx_set_secret_scalars(ctx, 1), with a call-level -1 and a message: the nonce hash absorbs t, which depends on the private
+ * key, and Streebog indexes its table by state octets.  Every other call here accepts Streebog in either mode and gives the same bytes
+ * in both: it hashes commitments and messages only, which a verifier recomputes.  No other served hash looks anything up by data.
+ * [k]G and [x]G honour the mode as in the names without _ht.
+ * Out of scope: the whole-batch forms ec_schnorr_verify_all_batch / ec_schnorr_verify_msg_all_batch (SHA-2 only; they answer "valid" or
+ * "not decided", and the item form here gives the verdict), the ecamd_multi_* wrappers, the libecc-typed layer (libsign_amd), belt-hash
+ * and SHAKE256 as commitment hashes. */
+int ec_sig_hashed_verify_ht_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n,
+				  const uint8_t *pubkeys, const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, uint8_t *result);
+int ec_sig_hashed_sign_ht_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+				const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, uint8_t *sigs, uint8_t *status);
+int ec_schnorr_verify_ht_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *keys, int key_fmt,
+			       const uint8_t *sigs, const uint8_t *hash_slots, uint32_t stride, uint8_t *result);
+int ec_schnorr_sign_ht_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+			     const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+			     uint8_t *status);
+int ec_bip0340_nonce_ht_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs,
+			      const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *nonces,
+			      uint8_t *status);
+int ec_bip0340_sign_ht_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs,
+			     const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+			     uint8_t *status);
+int ec_sig_hashed_verify_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
+				      const void *d_sigs, const void *d_inputs, uint32_t stride, void *d_result, void *hip_stream);
+int ec_sig_hashed_sign_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_privs,
+				    const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs, void *d_status, void *hip_stream);
+int ec_schnorr_verify_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_keys, int key_fmt,
+				   const void *d_sigs, const void *d_hash_slots, uint32_t stride, void *d_result, void *hip_stream);
+int ec_schnorr_sign_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, int hash_type, uint32_t n, const void *d_privs,
+				 const void *d_pubkeys_aff, const void *d_nonces, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+				 void *d_status, void *hip_stream);
+int ec_bip0340_nonce_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs,
+				  const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_nonces,
+				  void *d_status, void *hip_stream);
+int ec_bip0340_sign_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs,
+				 const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+				 void *d_status, void *hip_stream);
 /* ec_key_pair_gen's generic rule (sig/ec_key.c:594-610): x = nn_get_random_mod(q) from the item's 2*qlen random bytes, Y = [x]G.
  * priv_out: n x qlen big-endian; pub_out: n x 2*clen affine X || Y; status as ec_prj_pt_mul_batch.  (Secret scalars: see
  * ecamd_ctx_set_secret_scalars; the private keys cross the bus on their way back, as supplied ones do on their way in.) */

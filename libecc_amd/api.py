@@ -42,6 +42,9 @@ EXPORTED_SYMBOLS = [
     "ec_eddsa_sign_msg_batch", "ec_eddsa_sign_msg_batch_dev", "ec_eddsa_pub_key_batch", "ec_eddsa_pub_key_batch_dev",
     "ec_dbign_nonce_batch", "ec_dbign_nonce_batch_dev", "ec_dbign_sign_batch", "ec_dbign_sign_batch_dev",
     "ec_bip0340_nonce_batch", "ec_bip0340_nonce_batch_dev", "ec_bip0340_sign_batch", "ec_bip0340_sign_batch_dev",
+    "ec_sig_hashed_verify_ht_batch", "ec_sig_hashed_verify_ht_batch_dev", "ec_sig_hashed_sign_ht_batch", "ec_sig_hashed_sign_ht_batch_dev",
+    "ec_schnorr_verify_ht_batch", "ec_schnorr_verify_ht_batch_dev", "ec_schnorr_sign_ht_batch", "ec_schnorr_sign_ht_batch_dev",
+    "ec_bip0340_nonce_ht_batch", "ec_bip0340_nonce_ht_batch_dev", "ec_bip0340_sign_ht_batch", "ec_bip0340_sign_ht_batch_dev",
 ]
 
 # libecc's ec_alg_type numbers of the EdDSA variants ec_eddsa_sign_msg_batch serves (lib_ecc_types.h:49-55)
@@ -187,6 +190,10 @@ def load_library():
         L.ec_bip0340_nonce_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, vp, u32, vp, vp, vp]
         L.ec_bip0340_sign_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u8p, u32, u8p, u8p]
         L.ec_bip0340_sign_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, vp, u32, vp, vp, vp]
+        # the _ht forms: the same arguments, hash_type from DIGEST_SIZES
+        for base in ("ec_sig_hashed_verify", "ec_sig_hashed_sign", "ec_schnorr_verify", "ec_schnorr_sign", "ec_bip0340_nonce", "ec_bip0340_sign"):
+            for tail in ("_batch", "_batch_dev"):
+                getattr(L, base + "_ht" + tail).argtypes = getattr(L, base + tail).argtypes
         L.ec_eddsa_sign_msg_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u32, u8p, u8p, u8p]
         L.ec_eddsa_sign_msg_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u8p, u32, vp, u32, vp, vp, vp, vp]
         L.ec_eddsa_pub_key_batch.argtypes = [vp, vp, u32, u8p, u8p, u8p]
@@ -673,6 +680,68 @@ class Curve:
              "ec_bip0340_sign_batch")
         return sigs.raw[:sl * n], st.raw[:n]
 
+    def sig_hashed_rlen_ht(self, alg, hash_type):
+        """Over the whole hash table (hash_type from DIGEST_SIZES): bytes of r in a signature of ECSDSA / ECOSDSA (the digest size) or ECKCDSA (min(digest size, qlen))"""
+        hs = DIGEST_SIZES.get(hash_type, 0)
+        return min(hs, self.qlen) if alg == SIG_ECKCDSA else hs
+
+    def sig_hashed_verify_ht(self, alg, hash_type, pubs, sigs, inputs, stride):
+        """Over the whole hash table (hash_type from DIGEST_SIZES): ECSDSA / ECOSDSA / ECKCDSA verification: 0 accept / 1 reject per item.  inputs: message slots of `stride` bytes with the blank
+        for the commitment in front of the message (ECSDSA, ECOSDSA), or the digests H(z || m) with stride = digest size (ECKCDSA)"""
+        n = len(pubs) // (2 * self.clen)
+        res = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_sig_hashed_verify_ht_batch(self.ctx.h, self.h, alg, hash_type, n, pubs, sigs, inputs, stride, res),
+             "ec_sig_hashed_verify_ht_batch")
+        return res.raw[:n]
+
+    def sig_hashed_sign_ht(self, alg, hash_type, privs, nonces, inputs, stride):
+        """Over the whole hash table (hash_type from DIGEST_SIZES): ECSDSA / ECOSDSA / ECKCDSA signatures (r || s) with caller-supplied nonces, and a status byte per item"""
+        n = len(privs) // self.qlen
+        sl = self.sig_hashed_rlen_ht(alg, hash_type) + self.qlen
+        sigs = C.create_string_buffer(max(1, sl * n))
+        st = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_sig_hashed_sign_ht_batch(self.ctx.h, self.h, alg, hash_type, n, privs, nonces, inputs, stride, sigs, st),
+             "ec_sig_hashed_sign_ht_batch")
+        return sigs.raw[:sl * n], st.raw[:n]
+
+    def schnorr_verify_ht(self, alg, hash_type, keys, key_fmt, sigs, slots, stride):
+        """Over the whole hash table (hash_type from DIGEST_SIZES): BIP0340 / ECFSDSA verification item by item (alg: SIG_BIP0340, SIG_ECFSDSA): 0 accept / 1 reject per item.
+        keys: X || Y (key_fmt 0) or X || Y || Z (1); slots: the hash inputs of ec_schnorr_verify_msg_all_batch"""
+        n = len(sigs) // (self.schnorr_rlen(alg) + self.qlen)
+        res = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_schnorr_verify_ht_batch(self.ctx.h, self.h, alg, hash_type, n, keys, key_fmt, sigs, slots, stride, res),
+             "ec_schnorr_verify_ht_batch")
+        return res.raw[:n]
+
+    def schnorr_sign_ht(self, alg, hash_type, privs, pubs, nonces, slots, stride):
+        """Over the whole hash table (hash_type from DIGEST_SIZES): BIP0340 / ECFSDSA signatures (r || s) with caller-supplied nonces, and a status byte per item; pubs: X || Y per item, or None
+        (BIP0340 derives Y = [x]G on the device; ECFSDSA ignores it)"""
+        n = len(privs) // self.qlen
+        sl = self.schnorr_rlen(alg) + self.qlen
+        sigs = C.create_string_buffer(max(1, sl * n))
+        st = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_schnorr_sign_ht_batch(self.ctx.h, self.h, alg, hash_type, n, privs, pubs, nonces, slots, stride, sigs, st),
+             "ec_schnorr_sign_ht_batch")
+        return sigs.raw[:sl * n], st.raw[:n]
+
+    def bip0340_nonce_ht(self, hash_type, privs, pubs, aux, slots, stride):
+        """Over the whole hash table (hash_type from DIGEST_SIZES): BIP0340's nonces derived on the device from the keys, the aux values (n x qlen big-endian) and the signing slots of
+        schnorr_sign; pubs: X || Y per item, or None (Y = [x]G on the device): (n x qlen big-endian, status)"""
+        n = len(privs) // self.qlen
+        out, st = C.create_string_buffer(max(1, self.qlen * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_bip0340_nonce_ht_batch(self.ctx.h, self.h, hash_type, n, privs, pubs, aux, slots, stride, out, st),
+             "ec_bip0340_nonce_ht_batch")
+        return out.raw[:self.qlen * n], st.raw[:n]
+
+    def bip0340_sign_ht(self, hash_type, privs, pubs, aux, slots, stride):
+        """Over the whole hash table (hash_type from DIGEST_SIZES): BIP0340 signatures (r || s) and a status byte per item, the nonce derived on the device from the aux values"""
+        n = len(privs) // self.qlen
+        sl = self.clen + self.qlen
+        sigs, st = C.create_string_buffer(max(1, sl * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_bip0340_sign_ht_batch(self.ctx.h, self.h, hash_type, n, privs, pubs, aux, slots, stride, sigs, st),
+             "ec_bip0340_sign_ht_batch")
+        return sigs.raw[:sl * n], st.raw[:n]
+
     def key_pair_gen_raw(self, raw):
         """x = nn_get_random_mod value of the item's 2 * qlen random bytes, Y = [x]G: (privs, pubs affine, status)"""
         n = len(raw) // (2 * self.qlen)
@@ -921,6 +990,30 @@ class Curve:
     def bip0340_sign_dev(self, hash_type, n, d_privs, d_pubs, d_aux, d_slots, stride, d_sigs, d_status, stream=None):
         _chk(self.L, self.L.ec_bip0340_sign_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_pubs, d_aux, d_slots, stride, d_sigs,
                                                        d_status, stream), "ec_bip0340_sign_batch_dev")
+
+    def sig_hashed_verify_ht_dev(self, alg, hash_type, n, d_pubs, d_sigs, d_inputs, stride, d_result, stream=None):
+        _chk(self.L, self.L.ec_sig_hashed_verify_ht_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_pubs, d_sigs, d_inputs, stride, d_result,
+                                                            stream), "ec_sig_hashed_verify_ht_batch_dev")
+
+    def sig_hashed_sign_ht_dev(self, alg, hash_type, n, d_privs, d_nonces, d_inputs, stride, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_sig_hashed_sign_ht_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_privs, d_nonces, d_inputs, stride, d_sigs,
+                                                          d_status, stream), "ec_sig_hashed_sign_ht_batch_dev")
+
+    def schnorr_verify_ht_dev(self, alg, hash_type, n, d_keys, key_fmt, d_sigs, d_slots, stride, d_result, stream=None):
+        _chk(self.L, self.L.ec_schnorr_verify_ht_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_keys, key_fmt, d_sigs, d_slots, stride, d_result,
+                                                         stream), "ec_schnorr_verify_ht_batch_dev")
+
+    def schnorr_sign_ht_dev(self, alg, hash_type, n, d_privs, d_pubs, d_nonces, d_slots, stride, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_schnorr_sign_ht_batch_dev(self.ctx.h, self.h, alg, hash_type, n, d_privs, d_pubs, d_nonces, d_slots, stride, d_sigs,
+                                                       d_status, stream), "ec_schnorr_sign_ht_batch_dev")
+
+    def bip0340_nonce_ht_dev(self, hash_type, n, d_privs, d_pubs, d_aux, d_slots, stride, d_nonces, d_status, stream=None):
+        _chk(self.L, self.L.ec_bip0340_nonce_ht_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_pubs, d_aux, d_slots, stride, d_nonces,
+                                                        d_status, stream), "ec_bip0340_nonce_ht_batch_dev")
+
+    def bip0340_sign_ht_dev(self, hash_type, n, d_privs, d_pubs, d_aux, d_slots, stride, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_bip0340_sign_ht_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_pubs, d_aux, d_slots, stride, d_sigs,
+                                                       d_status, stream), "ec_bip0340_sign_ht_batch_dev")
 
     def ecccdh_dev(self, n, d_privs, d_peers, d_secrets, d_status, stream=None):
         _chk(self.L, self.L.ec_ecccdh_derive_batch_dev(self.ctx.h, self.h, n, d_privs, d_peers, d_secrets, d_status,

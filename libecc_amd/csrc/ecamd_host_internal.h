@@ -5,6 +5,7 @@
 //                          points, scalar multiplication and point operations, ECDSA and its relatives, XDH, EdDSA, the whole-batch forms
 //   ecamd_host_sigfam.cpp  ECKCDSA / ECSDSA / ECOSDSA, BIGN / DBIGN, BIP0340 / ECFSDSA, message-level ECGDSA / ECRDSA / SM2, ec_hash_slots_*,
 //                          ec_digest_slots_*, HMAC and deterministic ECDSA over the whole hash table (ec_hmac_slots_*, ec_*_ht_*)
+//                          and the _ht names of the three commitment-hashing families (ec_sig_hashed_*_ht_*, ec_schnorr_*_ht_*, ec_bip0340_*_ht_*)
 // A protocol family lives in exactly one unit.  This header declares only what more than one unit uses; what one unit needs stays
 // `static` in its file.  The shared functions are in namespace ecamd_host with hidden visibility: none of them enters the library's
 // dynamic symbol table.

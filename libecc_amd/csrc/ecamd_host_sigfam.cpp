@@ -7,9 +7,41 @@
 #include "ecamd_rfc6979.h"
 #include "ecamd_dbign_nonce.h"
 #include "ecamd_bip0340_nonce.h"
+#include "ecamd_bip0340_nonce_ht.h"
 #include "ecamd_sm2z.h"
+#include <mutex>
 
 using namespace ecamd_host;
+
+// ------------------------------------------------------------------------------------------
+// The commitment hash of the five schemes that hash AFTER their multiplication (ECKCDSA / ECSDSA / ECOSDSA, ECFSDSA / BIP0340).  The
+// older names (ec_sig_hashed_*, ec_schnorr_*_batch, ec_bip0340_*_batch) take hash_type 1 .. 4; their _ht forms take every hash of
+// ec_digest_slots_batch.  Both run the cores below: `ht` only widens the set the argument check admits.  1 .. 4 launch k_sha2_slots
+// alone whichever name was called (the same kernels, bytes and speed); the others go through ecamd_hash3.hip's launcher, which gives
+// a slot that does not fit its stride an all-zero digest -- such an item is flagged by the fill kernels before its digest is read.
+// ------------------------------------------------------------------------------------------
+static const char *const HT_SET = "hash_type must be 1 .. 11, 13 .. 15 or 17 .. 20 (every fixed-length hash of libecc's table but belt-hash)";
+
+static uint32_t commit_hsize(int hash_type)
+{
+	return (uint32_t)ecamd_digest_len_any(hash_type);   // 1 .. 4: echsig::hash_size's values; 20 for RIPEMD-160
+}
+
+static int commit_hash_ok(const char *fn, bool ht, int hash_type)
+{
+	if (ht ? commit_hsize(hash_type) == 0 : echsig::hash_size(hash_type) == 0) {
+		return fail(std::string(fn) + ": " + (ht ? HT_SET : "hash_type must be 1 .. 4 (SHA-224, SHA-256, SHA-384, SHA-512)"));
+	}
+	return 0;
+}
+
+static hipError_t commit_hash_launch(int hash_type, const uint8_t *slots, uint32_t stride, uint32_t m, uint8_t *out, uint32_t hsize, hipStream_t s)
+{
+	if (hash_type >= 1 && hash_type <= 4) {
+		return ecamd_launch_sha2_slots(hash_type, slots, stride, m, out, hsize, s);
+	}
+	return ecamd_launch_digest_slots(hash_type, slots, stride, m, out, hsize, s);
+}
 
 // ------------------------------------------------------------------------------------------
 // batched ECSDSA / ECOSDSA / ECKCDSA (include/libecc_amd.h: ec_sig_hashed_*): the schemes that hash the commitment.  Per chunk of
@@ -46,7 +78,7 @@ static int hsig_stage_hash(ecamd_ctx *ctx, int hash_type, uint32_t m, EcamdHsigA
 	H.slots = S[ST_SLOTS];
 	H.dg = S[ST_DIGESTS];
 	HIPCHK(ecamd_launch_hsig_fill(H, s));
-	HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], H.sstride, m, S[ST_DIGESTS], H.hsize, s));
+	HIPCHK(commit_hash_launch(hash_type, S[ST_SLOTS], H.sstride, m, S[ST_DIGESTS], H.hsize, s));
 	return 0;
 }
 
@@ -55,7 +87,7 @@ static int hsig_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg
 {
 	PublicScalars pub_scope(ctx);   // u, v and the group order are public
 	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
-	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	const uint32_t hsize = commit_hsize(hash_type);
 	if (hsig_no_room(cv, alg, stride)) {
 		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
 		return 0;
@@ -99,7 +131,7 @@ static int hsig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, 
 				const uint8_t *d_nonces, const uint8_t *d_in, uint32_t stride, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
 {
 	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
-	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	const uint32_t hsize = commit_hsize(hash_type);
 	const size_t siglen = (size_t)echsig::r_len(alg, (int)hsize, (int)ql) + ql;
 	const uint32_t sstride = hsig_staged_stride(cv, alg, stride);
 	if (hsig_no_room(cv, alg, stride)) {
@@ -145,14 +177,14 @@ static int hsig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, 
 	});
 }
 
-static int hsig_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a, const void *b,
+static int hsig_args_ok(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a, const void *b,
 			const void *c, const void *d, const void *e, uint32_t stride)
 {
 	if (!echsig::alg_known(alg)) {
 		return fail(std::string(fn) + ": alg must be ECAMD_SIG_ECKCDSA, ECAMD_SIG_ECSDSA or ECAMD_SIG_ECOSDSA");
 	}
-	if (echsig::hash_size(hash_type) == 0) {
-		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224, SHA-256, SHA-384, SHA-512)");
+	if (commit_hash_ok(fn, ht, hash_type)) {
+		return -1;
 	}
 	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
 		return fail(std::string(fn) + ": bad argument");
@@ -161,7 +193,7 @@ static int hsig_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, i
 		return fail(std::string(fn) + ": generator order not supported for this curve");
 	}
 	if (alg == ECAMD_SIG_ECKCDSA) {
-		if (stride != (uint32_t)echsig::hash_size(hash_type)) {
+		if (stride != commit_hsize(hash_type)) {
 			return fail(std::string(fn) + ": ECKCDSA takes digests h = H(z || m): stride must be the hash's digest size");
 		}
 	} else if ((stride & 3u) || stride > 4096 || stride < 4) {
@@ -170,10 +202,11 @@ static int hsig_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, i
 	return 0;
 }
 
-extern "C" int ec_sig_hashed_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
-					      const void *d_sigs, const void *d_inputs, uint32_t stride, void *d_result, void *hip_stream)
+static int ec_sig_hashed_verify_batch_dev_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n,
+					       const void *d_pubkeys, const void *d_sigs, const void *d_inputs, uint32_t stride, void *d_result,
+					       void *hip_stream)
 {
-	if (hsig_args_ok("ec_sig_hashed_verify_batch_dev", ctx, cv, alg, hash_type, n, d_pubkeys, d_sigs, d_inputs, d_result, d_result, stride)) {
+	if (hsig_args_ok(fn, ht, ctx, cv, alg, hash_type, n, d_pubkeys, d_sigs, d_inputs, d_result, d_result, stride)) {
 		return -1;
 	}
 	if (n == 0) {
@@ -185,26 +218,27 @@ extern "C" int ec_sig_hashed_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve 
 	});
 }
 
-extern "C" int ec_sig_hashed_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
-					  const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, uint8_t *result)
+static int ec_sig_hashed_verify_batch_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n,
+					   const uint8_t *pubkeys, const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, uint8_t *result)
 {
-	if (hsig_args_ok("ec_sig_hashed_verify_batch", ctx, cv, alg, hash_type, n, pubkeys, sigs, inputs, result, result, stride)) {
+	if (hsig_args_ok(fn, ht, ctx, cv, alg, hash_type, n, pubkeys, sigs, inputs, result, result, stride)) {
 		return -1;
 	}
 	if (n == 0) {
 		return 0;
 	}
-	const size_t siglen = (size_t)echsig::r_len(alg, echsig::hash_size(hash_type), cv->qlen) + cv->qlen;
+	const size_t siglen = (size_t)echsig::r_len(alg, (int)commit_hsize(hash_type), cv->qlen) + cv->qlen;
 	const std::vector<HostArr> arrs = {{pubkeys, nullptr, (size_t)2 * cv->clen}, {sigs, nullptr, siglen}, {inputs, nullptr, stride}, {nullptr, result, 1}};
 	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return hsig_verify_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], s);
 	});
 }
 
-extern "C" int ec_sig_hashed_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
-					    const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs, void *d_status, void *hip_stream)
+static int ec_sig_hashed_sign_batch_dev_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n,
+					     const void *d_privs, const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs,
+					     void *d_status, void *hip_stream)
 {
-	if (hsig_args_ok("ec_sig_hashed_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_inputs, d_sigs, d_status, stride)) {
+	if (hsig_args_ok(fn, ht, ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_inputs, d_sigs, d_status, stride)) {
 		return -1;
 	}
 	if (n == 0) {
@@ -216,17 +250,18 @@ extern "C" int ec_sig_hashed_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *c
 	});
 }
 
-extern "C" int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
-					const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, uint8_t *sigs, uint8_t *status)
+static int ec_sig_hashed_sign_batch_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n,
+					 const uint8_t *privs, const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, uint8_t *sigs,
+					 uint8_t *status)
 {
-	if (hsig_args_ok("ec_sig_hashed_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, inputs, sigs, status, stride)) {
+	if (hsig_args_ok(fn, ht, ctx, cv, alg, hash_type, n, privs, nonces, inputs, sigs, status, stride)) {
 		return -1;
 	}
 	if (n == 0) {
 		return 0;
 	}
 	const size_t ql = (size_t)cv->qlen;
-	const size_t siglen = (size_t)echsig::r_len(alg, echsig::hash_size(hash_type), cv->qlen) + ql;
+	const size_t siglen = (size_t)echsig::r_len(alg, (int)commit_hsize(hash_type), cv->qlen) + ql;
 	const std::vector<HostArr> arrs = {{privs, nullptr, ql}, {nonces, nullptr, ql}, {inputs, nullptr, stride}, {nullptr, sigs, siglen}, {nullptr, status, 1}};
 	return host_call(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return hsig_sign_dev_locked(ctx, cv, alg, hash_type, m, ip[0], ip[1], ip[2], stride, op[3], op[4], s);
@@ -494,7 +529,7 @@ static int schnorr_item_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv,
 {
 	PublicScalars pub_scope(ctx);   // s, q - e and the group order are public
 	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
-	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	const uint32_t hsize = commit_hsize(hash_type);
 	if (schnorr_item_no_room(cv, alg, hsize, stride)) {
 		HIPCHK(hipMemsetAsync(d_res, 1, n, s));
 		return 0;
@@ -562,7 +597,7 @@ static int schnorr_item_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv,
 			T.slot = cv->slot;
 			HIPCHK(ecamd_launch_ptf(cv->nw, T, s));
 		}
-		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], stride, m, S[ST_DIGESTS], hsize, s));
+		HIPCHK(commit_hash_launch(hash_type, S[ST_SLOTS], stride, m, S[ST_DIGESTS], hsize, s));
 		N.dig = S[ST_DIGESTS];
 		N.ne = S[ST_V];
 		N.n = m;
@@ -584,7 +619,7 @@ static int schnorr_item_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, i
 					uint8_t *d_status, hipStream_t s)
 {
 	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen;
-	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	const uint32_t hsize = commit_hsize(hash_type);
 	const size_t siglen = (size_t)ecschnorr::r_len(alg, (int)cl) + ql;
 	if (schnorr_item_no_room(cv, alg, hsize, stride)) {
 		HIPCHK(hipMemsetAsync(d_sigs, 0, n * siglen, s));
@@ -638,20 +673,20 @@ static int schnorr_item_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, i
 		H.status = d_status + off;
 		HIPCHK(hipMemcpyAsync(S[ST_SLOTS], d_in + (size_t)off * stride, (size_t)m * stride, hipMemcpyDeviceToDevice, s));
 		HIPCHK(ecamd_launch_schnorr_item_fill(H, s));
-		HIPCHK(ecamd_launch_sha2_slots(hash_type, S[ST_SLOTS], stride, m, S[ST_DIGESTS], hsize, s));
+		HIPCHK(commit_hash_launch(hash_type, S[ST_SLOTS], stride, m, S[ST_DIGESTS], hsize, s));
 		HIPCHK(ecamd_launch_schnorr_item_sign(cv->qnw, H, s));
 		return 0;
 	});
 }
 
-static int schnorr_item_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a,
+static int schnorr_item_args_ok(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *a,
 				const void *b, const void *c, const void *d, const void *e, uint32_t stride)
 {
 	if (!ecschnorr::alg_known(alg)) {
 		return fail(std::string(fn) + ": alg must be ECAMD_SIG_BIP0340 or ECAMD_SIG_ECFSDSA");
 	}
-	if (echsig::hash_size(hash_type) == 0) {
-		return fail(std::string(fn) + ": hash_type must be 1 .. 4 (SHA-224, SHA-256, SHA-384, SHA-512)");
+	if (commit_hash_ok(fn, ht, hash_type)) {
+		return -1;
 	}
 	if (!ctx || !cv || cv->ctx != ctx || (n && (!a || !b || !c || !d || !e))) {
 		return fail(std::string(fn) + ": bad argument");
@@ -673,12 +708,12 @@ static int schnorr_item_fmt_ok(const char *fn, int key_fmt)
 	return 0;
 }
 
-extern "C" int ec_schnorr_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_keys,
-					   int key_fmt, const void *d_sigs, const void *d_hash_slots, uint32_t stride, void *d_result,
-					   void *hip_stream)
+static int ec_schnorr_verify_batch_dev_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n,
+					    const void *d_keys, int key_fmt, const void *d_sigs, const void *d_hash_slots, uint32_t stride,
+					    void *d_result, void *hip_stream)
 {
-	if (schnorr_item_args_ok("ec_schnorr_verify_batch_dev", ctx, cv, alg, hash_type, n, d_keys, d_sigs, d_hash_slots, d_result, d_result, stride) ||
-	    schnorr_item_fmt_ok("ec_schnorr_verify_batch_dev", key_fmt)) {
+	if (schnorr_item_args_ok(fn, ht, ctx, cv, alg, hash_type, n, d_keys, d_sigs, d_hash_slots, d_result, d_result, stride) ||
+	    schnorr_item_fmt_ok(fn, key_fmt)) {
 		return -1;
 	}
 	if (n == 0) {
@@ -690,11 +725,12 @@ extern "C" int ec_schnorr_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv
 	});
 }
 
-extern "C" int ec_schnorr_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *keys, int key_fmt,
-				       const uint8_t *sigs, const uint8_t *hash_slots, uint32_t stride, uint8_t *result)
+static int ec_schnorr_verify_batch_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n,
+					const uint8_t *keys, int key_fmt, const uint8_t *sigs, const uint8_t *hash_slots, uint32_t stride,
+					uint8_t *result)
 {
-	if (schnorr_item_args_ok("ec_schnorr_verify_batch", ctx, cv, alg, hash_type, n, keys, sigs, hash_slots, result, result, stride) ||
-	    schnorr_item_fmt_ok("ec_schnorr_verify_batch", key_fmt)) {
+	if (schnorr_item_args_ok(fn, ht, ctx, cv, alg, hash_type, n, keys, sigs, hash_slots, result, result, stride) ||
+	    schnorr_item_fmt_ok(fn, key_fmt)) {
 		return -1;
 	}
 	if (n == 0) {
@@ -708,11 +744,11 @@ extern "C" int ec_schnorr_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, in
 	});
 }
 
-extern "C" int ec_schnorr_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
-					 const void *d_pubkeys_aff, const void *d_nonces, const void *d_hash_slots, uint32_t stride, void *d_sigs,
-					 void *d_status, void *hip_stream)
+static int ec_schnorr_sign_batch_dev_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n,
+					  const void *d_privs, const void *d_pubkeys_aff, const void *d_nonces, const void *d_hash_slots,
+					  uint32_t stride, void *d_sigs, void *d_status, void *hip_stream)
 {
-	if (schnorr_item_args_ok("ec_schnorr_sign_batch_dev", ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_hash_slots, d_sigs, d_status, stride)) {
+	if (schnorr_item_args_ok(fn, ht, ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_hash_slots, d_sigs, d_status, stride)) {
 		return -1;
 	}
 	if (n == 0) {
@@ -724,11 +760,11 @@ extern "C" int ec_schnorr_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, 
 	});
 }
 
-extern "C" int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
-				     const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
-				     uint8_t *status)
+static int ec_schnorr_sign_batch_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n,
+				      const uint8_t *privs, const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *hash_slots,
+				      uint32_t stride, uint8_t *sigs, uint8_t *status)
 {
-	if (schnorr_item_args_ok("ec_schnorr_sign_batch", ctx, cv, alg, hash_type, n, privs, nonces, hash_slots, sigs, status, stride)) {
+	if (schnorr_item_args_ok(fn, ht, ctx, cv, alg, hash_type, n, privs, nonces, hash_slots, sigs, status, stride)) {
 		return -1;
 	}
 	if (n == 0) {
@@ -966,6 +1002,55 @@ static void bip0340_nonce_args(EcamdBip0340NonceArgs &N, const ecamd_curve *cv, 
 	}
 }
 
+// ---- the hashes k_bip0340_nonce does not have: the hash trait of ecamd_hmac.h, on the host for the two tag hashes of a call ----
+static const uint64_t h_keccak_rc[24] = {ECAMD_KECCAK_RC};
+static const uint64_t h_bash_rc[24] = {ECAMD_BASH_RC};
+static const uint8_t h_sb_pi[256] = {ECAMD_STREEBOG_PI};
+static const uint64_t h_sb_a[64] = {ECAMD_STREEBOG_A};
+static const uint64_t h_sb_c[96] = {ECAMD_STREEBOG_C};
+static uint64_t h_sb_T[ecsb::TABLE_WORDS];   // Streebog's combined table, built on first use
+
+// what echm::Hash<ID>::hash reads its constants through
+struct HostHashEnv {
+	const uint32_t *k256;
+	const uint64_t *k512, *keccak_rc, *bash_rc, *sb_T, *sb_C;
+	void tick() const {}
+};
+
+static HostHashEnv host_hash_env()
+{
+	static std::once_flag once;
+	std::call_once(once, [] {
+		for (uint32_t e = 0; e < (uint32_t)ecsb::TABLE_WORDS; e++) {
+			h_sb_T[e] = ecsb::table_entry(h_sb_pi, h_sb_a, e >> 8, e & 255u);
+		}
+	});
+	return HostHashEnv{h_sha256_k, h_sha512_k, h_keccak_rc, h_bash_rc, h_sb_T, h_sb_c};
+}
+
+static void bip0340_nonce_ht_args(EcamdBip0340NonceHtArgs &N, const ecamd_curve *cv, int hash_type, uint32_t stride)
+{
+	memset(&N, 0, sizeof(N));
+	N.qlen = (uint32_t)cv->qlen;
+	N.qbits = (uint32_t)cv->qbits;
+	N.clen = (uint32_t)cv->clen;
+	N.stride = stride;
+	for (int w = 0; w < 17; w++) {
+		N.q[w] = (size_t)w < cv->q.size() ? cv->q[(size_t)w] : 0;
+	}
+	const HostHashEnv env = host_hash_env();
+	switch (hash_type) {
+#define BIP_TAGS(ID) \
+	case ID: \
+		ecbipht::tag_hash<echm::Hash<ID>>(env, "BIP0340/aux", 11, N.tag_aux); \
+		ecbipht::tag_hash<echm::Hash<ID>>(env, "BIP0340/nonce", 13, N.tag_nonce); \
+		break;
+		ECHM_FOR_EACH_HASH(BIP_TAGS)
+#undef BIP_TAGS
+	default: break;
+	}
+}
+
 // Y of one chunk: [x]G into SG_Y, or the caller's keys with their on-curve test; either way SG_STY holds the status.  *keys: where Y lies.
 static int bip0340_keys_dev(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t m, const uint8_t *d_privs, const uint8_t *d_pubs, const uint8_t **keys,
 			    hipStream_t s)
@@ -995,7 +1080,7 @@ static int bip0340_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_ty
 			      const uint8_t *d_aux, const uint8_t *d_in, uint32_t stride, uint8_t *d_out, uint8_t *d_status, bool sign, hipStream_t s)
 {
 	const size_t cl = (size_t)cv->clen, plen = 2 * cl, ql = (size_t)cv->qlen, siglen = cl + ql;
-	const uint32_t hsize = (uint32_t)echsig::hash_size(hash_type);
+	const uint32_t hsize = commit_hsize(hash_type);
 	if (sign && schnorr_item_no_room(cv, ECAMD_SIG_BIP0340, hsize, stride)) {
 		HIPCHK(hipMemsetAsync(d_out, 0, n * siglen, s));
 		HIPCHK(hipMemsetAsync(d_status, 1, n, s));
@@ -1007,23 +1092,45 @@ static int bip0340_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_ty
 				      {ST_SLOTS, (size_t)chunk * stride}, {ST_DIGESTS, (size_t)chunk * hsize}}))) {
 		return -1;
 	}
+	// 1 .. 4: k_bip0340_nonce, whichever name was called; the others: k_bip0340_nonce_ht<ID>
+	const bool old_hash = hash_type >= 1 && hash_type <= 4;
 	EcamdBip0340NonceArgs N;
-	bip0340_nonce_args(N, cv, hash_type, stride);
+	EcamdBip0340NonceHtArgs T;
+	if (old_hash) {
+		bip0340_nonce_args(N, cv, hash_type, stride);
+	} else {
+		bip0340_nonce_ht_args(T, cv, hash_type, stride);
+	}
 	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
-		const uint8_t *in = d_in + (size_t)off * stride;
-		if (bip0340_keys_dev(ctx, cv, m, d_privs + off * ql, d_pubs ? d_pubs + off * plen : nullptr, &N.keys, s)) {
+		const uint8_t *in = d_in + (size_t)off * stride, *privs = d_privs + off * ql, *keys = nullptr;
+		uint8_t *nonces = sign ? ctx->stage[SG_NONCES] : d_out + off * ql;
+		if (bip0340_keys_dev(ctx, cv, m, privs, d_pubs ? d_pubs + off * plen : nullptr, &keys, s)) {
 			return -1;
 		}
-		N.n = m;
-		N.privs = d_privs + off * ql;
-		N.kst = ctx->stage[SG_STY];
-		N.aux = d_aux + off * ql;
-		N.slots = in;
-		N.nonces = sign ? ctx->stage[SG_NONCES] : d_out + off * ql;
-		N.status = d_status + off;   // signing: replaced by the core's, where a zero nonce is status 1
-		HIPCHK(ecamd_launch_bip0340_nonce(hash_type, N, s));
+		// the status: when signing it is replaced by the core's, where a zero nonce is status 1
+		if (old_hash) {
+			N.n = m;
+			N.privs = privs;
+			N.keys = keys;
+			N.kst = ctx->stage[SG_STY];
+			N.aux = d_aux + off * ql;
+			N.slots = in;
+			N.nonces = nonces;
+			N.status = d_status + off;
+			HIPCHK(ecamd_launch_bip0340_nonce(hash_type, N, s));
+		} else {
+			T.n = m;
+			T.privs = privs;
+			T.keys = keys;
+			T.kst = ctx->stage[SG_STY];
+			T.aux = d_aux + off * ql;
+			T.slots = in;
+			T.nonces = nonces;
+			T.status = d_status + off;
+			HIPCHK(ecamd_launch_bip0340_nonce_ht(hash_type, T, s));
+		}
 		// the core takes Y as a supplied key ([x]G is computed once): derived here, it fails the core's on-curve test only as the point at infinity
-		if (sign && schnorr_item_sign_dev_locked(ctx, cv, ECAMD_SIG_BIP0340, hash_type, m, N.privs, N.keys, N.nonces, in, stride,
+		if (sign && schnorr_item_sign_dev_locked(ctx, cv, ECAMD_SIG_BIP0340, hash_type, m, privs, keys, nonces, in, stride,
 							 d_out + (size_t)off * siglen, d_status + off, s)) {
 			return -1;
 		}
@@ -1031,20 +1138,24 @@ static int bip0340_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_ty
 	});
 }
 
-static int bip0340_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *privs, const void *aux,
+static int bip0340_args_ok(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *privs, const void *aux,
 			   const void *slots, const void *out, const void *status, uint32_t stride)
 {
-	if (schnorr_item_args_ok(fn, ctx, cv, ECAMD_SIG_BIP0340, hash_type, n, privs, aux, slots, out, status, stride)) {
+	if (schnorr_item_args_ok(fn, ht, ctx, cv, ECAMD_SIG_BIP0340, hash_type, n, privs, aux, slots, out, status, stride)) {
 		return -1;
+	}
+	// the nonce hash absorbs t = d ^ mask: Streebog would look its table up by octets of it
+	if (ctx->secret_scalars && (hash_type == 13 || hash_type == 14)) {
+		return fail(std::string(fn) + ": Streebog (hash_type 13, 14) looks its table up by octets that depend on the secret: refused in secret-scalar mode");
 	}
 	return det_order_ok(fn, cv);
 }
 
-extern "C" int ec_bip0340_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
-					  const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_nonces,
-					  void *d_status, void *hip_stream)
+static int ec_bip0340_nonce_batch_dev_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n,
+					   const void *d_privs, const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots,
+					   uint32_t stride, void *d_nonces, void *d_status, void *hip_stream)
 {
-	if (bip0340_args_ok("ec_bip0340_nonce_batch_dev", ctx, cv, hash_type, n, d_privs, d_aux, d_hash_slots, d_nonces, d_status, stride)) {
+	if (bip0340_args_ok(fn, ht, ctx, cv, hash_type, n, d_privs, d_aux, d_hash_slots, d_nonces, d_status, stride)) {
 		return -1;
 	}
 	if (n == 0) {
@@ -1056,11 +1167,11 @@ extern "C" int ec_bip0340_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv,
 	});
 }
 
-extern "C" int ec_bip0340_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
-					 const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_sigs,
-					 void *d_status, void *hip_stream)
+static int ec_bip0340_sign_batch_dev_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n,
+					  const void *d_privs, const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots,
+					  uint32_t stride, void *d_sigs, void *d_status, void *hip_stream)
 {
-	if (bip0340_args_ok("ec_bip0340_sign_batch_dev", ctx, cv, hash_type, n, d_privs, d_aux, d_hash_slots, d_sigs, d_status, stride)) {
+	if (bip0340_args_ok(fn, ht, ctx, cv, hash_type, n, d_privs, d_aux, d_hash_slots, d_sigs, d_status, stride)) {
 		return -1;
 	}
 	if (n == 0) {
@@ -1085,11 +1196,11 @@ static int bip0340_host(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, ui
 	});
 }
 
-extern "C" int ec_bip0340_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
-				      const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *nonces,
-				      uint8_t *status)
+static int ec_bip0340_nonce_batch_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n,
+				       const uint8_t *privs, const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots,
+				       uint32_t stride, uint8_t *nonces, uint8_t *status)
 {
-	if (bip0340_args_ok("ec_bip0340_nonce_batch", ctx, cv, hash_type, n, privs, aux, hash_slots, nonces, status, stride)) {
+	if (bip0340_args_ok(fn, ht, ctx, cv, hash_type, n, privs, aux, hash_slots, nonces, status, stride)) {
 		return -1;
 	}
 	if (n == 0) {
@@ -1098,17 +1209,202 @@ extern "C" int ec_bip0340_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int
 	return bip0340_host(ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, nonces, (size_t)cv->qlen, status, false);
 }
 
-extern "C" int ec_bip0340_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
-				     const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
-				     uint8_t *status)
+static int ec_bip0340_sign_batch_impl(const char *fn, bool ht, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+				      const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+				      uint8_t *status)
 {
-	if (bip0340_args_ok("ec_bip0340_sign_batch", ctx, cv, hash_type, n, privs, aux, hash_slots, sigs, status, stride)) {
+	if (bip0340_args_ok(fn, ht, ctx, cv, hash_type, n, privs, aux, hash_slots, sigs, status, stride)) {
 		return -1;
 	}
 	if (n == 0) {
 		return 0;
 	}
 	return bip0340_host(ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, sigs, (size_t)cv->clen + cv->qlen, status, true);
+}
+
+// The public names of the three families above.  name_batch: hash_type 1 .. 4; name_ht_batch: every hash of ec_digest_slots_batch
+// (include/libecc_amd.h).  Each pair shares one implementation.
+extern "C" int ec_sig_hashed_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
+					      const void *d_sigs, const void *d_inputs, uint32_t stride, void *d_result, void *hip_stream)
+{
+	return ec_sig_hashed_verify_batch_dev_impl("ec_sig_hashed_verify_batch_dev", false, ctx, cv, alg, hash_type, n, d_pubkeys, d_sigs, d_inputs,
+						   stride, d_result, hip_stream);
+}
+
+extern "C" int ec_sig_hashed_verify_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_pubkeys,
+						 const void *d_sigs, const void *d_inputs, uint32_t stride, void *d_result, void *hip_stream)
+{
+	return ec_sig_hashed_verify_batch_dev_impl("ec_sig_hashed_verify_ht_batch_dev", true, ctx, cv, alg, hash_type, n, d_pubkeys, d_sigs, d_inputs,
+						   stride, d_result, hip_stream);
+}
+
+extern "C" int ec_sig_hashed_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
+					  const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, uint8_t *result)
+{
+	return ec_sig_hashed_verify_batch_impl("ec_sig_hashed_verify_batch", false, ctx, cv, alg, hash_type, n, pubkeys, sigs, inputs, stride,
+					       result);
+}
+
+extern "C" int ec_sig_hashed_verify_ht_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *pubkeys,
+					     const uint8_t *sigs, const uint8_t *inputs, uint32_t stride, uint8_t *result)
+{
+	return ec_sig_hashed_verify_batch_impl("ec_sig_hashed_verify_ht_batch", true, ctx, cv, alg, hash_type, n, pubkeys, sigs, inputs, stride,
+					       result);
+}
+
+extern "C" int ec_sig_hashed_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+					    const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs, void *d_status,
+					    void *hip_stream)
+{
+	return ec_sig_hashed_sign_batch_dev_impl("ec_sig_hashed_sign_batch_dev", false, ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_inputs,
+						 stride, d_sigs, d_status, hip_stream);
+}
+
+extern "C" int ec_sig_hashed_sign_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+					       const void *d_nonces, const void *d_inputs, uint32_t stride, void *d_sigs, void *d_status,
+					       void *hip_stream)
+{
+	return ec_sig_hashed_sign_batch_dev_impl("ec_sig_hashed_sign_ht_batch_dev", true, ctx, cv, alg, hash_type, n, d_privs, d_nonces, d_inputs,
+						 stride, d_sigs, d_status, hip_stream);
+}
+
+extern "C" int ec_sig_hashed_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+					const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, uint8_t *sigs, uint8_t *status)
+{
+	return ec_sig_hashed_sign_batch_impl("ec_sig_hashed_sign_batch", false, ctx, cv, alg, hash_type, n, privs, nonces, inputs, stride, sigs,
+					     status);
+}
+
+extern "C" int ec_sig_hashed_sign_ht_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+					   const uint8_t *nonces, const uint8_t *inputs, uint32_t stride, uint8_t *sigs, uint8_t *status)
+{
+	return ec_sig_hashed_sign_batch_impl("ec_sig_hashed_sign_ht_batch", true, ctx, cv, alg, hash_type, n, privs, nonces, inputs, stride, sigs,
+					     status);
+}
+
+extern "C" int ec_schnorr_verify_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_keys, int key_fmt,
+					   const void *d_sigs, const void *d_hash_slots, uint32_t stride, void *d_result, void *hip_stream)
+{
+	return ec_schnorr_verify_batch_dev_impl("ec_schnorr_verify_batch_dev", false, ctx, cv, alg, hash_type, n, d_keys, key_fmt, d_sigs,
+						d_hash_slots, stride, d_result, hip_stream);
+}
+
+extern "C" int ec_schnorr_verify_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_keys,
+					      int key_fmt, const void *d_sigs, const void *d_hash_slots, uint32_t stride, void *d_result,
+					      void *hip_stream)
+{
+	return ec_schnorr_verify_batch_dev_impl("ec_schnorr_verify_ht_batch_dev", true, ctx, cv, alg, hash_type, n, d_keys, key_fmt, d_sigs,
+						d_hash_slots, stride, d_result, hip_stream);
+}
+
+extern "C" int ec_schnorr_verify_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *keys, int key_fmt,
+				       const uint8_t *sigs, const uint8_t *hash_slots, uint32_t stride, uint8_t *result)
+{
+	return ec_schnorr_verify_batch_impl("ec_schnorr_verify_batch", false, ctx, cv, alg, hash_type, n, keys, key_fmt, sigs, hash_slots, stride,
+					    result);
+}
+
+extern "C" int ec_schnorr_verify_ht_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *keys, int key_fmt,
+					  const uint8_t *sigs, const uint8_t *hash_slots, uint32_t stride, uint8_t *result)
+{
+	return ec_schnorr_verify_batch_impl("ec_schnorr_verify_ht_batch", true, ctx, cv, alg, hash_type, n, keys, key_fmt, sigs, hash_slots, stride,
+					    result);
+}
+
+extern "C" int ec_schnorr_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+					 const void *d_pubkeys_aff, const void *d_nonces, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+					 void *d_status, void *hip_stream)
+{
+	return ec_schnorr_sign_batch_dev_impl("ec_schnorr_sign_batch_dev", false, ctx, cv, alg, hash_type, n, d_privs, d_pubkeys_aff, d_nonces,
+					      d_hash_slots, stride, d_sigs, d_status, hip_stream);
+}
+
+extern "C" int ec_schnorr_sign_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const void *d_privs,
+					    const void *d_pubkeys_aff, const void *d_nonces, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+					    void *d_status, void *hip_stream)
+{
+	return ec_schnorr_sign_batch_dev_impl("ec_schnorr_sign_ht_batch_dev", true, ctx, cv, alg, hash_type, n, d_privs, d_pubkeys_aff, d_nonces,
+					      d_hash_slots, stride, d_sigs, d_status, hip_stream);
+}
+
+extern "C" int ec_schnorr_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+				     const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+				     uint8_t *status)
+{
+	return ec_schnorr_sign_batch_impl("ec_schnorr_sign_batch", false, ctx, cv, alg, hash_type, n, privs, pubkeys_aff, nonces, hash_slots, stride,
+					  sigs, status);
+}
+
+extern "C" int ec_schnorr_sign_ht_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, int hash_type, uint32_t n, const uint8_t *privs,
+					const uint8_t *pubkeys_aff, const uint8_t *nonces, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+					uint8_t *status)
+{
+	return ec_schnorr_sign_batch_impl("ec_schnorr_sign_ht_batch", true, ctx, cv, alg, hash_type, n, privs, pubkeys_aff, nonces, hash_slots,
+					  stride, sigs, status);
+}
+
+extern "C" int ec_bip0340_nonce_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
+					  const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_nonces,
+					  void *d_status, void *hip_stream)
+{
+	return ec_bip0340_nonce_batch_dev_impl("ec_bip0340_nonce_batch_dev", false, ctx, cv, hash_type, n, d_privs, d_pubkeys_aff, d_aux,
+					       d_hash_slots, stride, d_nonces, d_status, hip_stream);
+}
+
+extern "C" int ec_bip0340_nonce_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
+					     const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_nonces,
+					     void *d_status, void *hip_stream)
+{
+	return ec_bip0340_nonce_batch_dev_impl("ec_bip0340_nonce_ht_batch_dev", true, ctx, cv, hash_type, n, d_privs, d_pubkeys_aff, d_aux,
+					       d_hash_slots, stride, d_nonces, d_status, hip_stream);
+}
+
+extern "C" int ec_bip0340_sign_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
+					 const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+					 void *d_status, void *hip_stream)
+{
+	return ec_bip0340_sign_batch_dev_impl("ec_bip0340_sign_batch_dev", false, ctx, cv, hash_type, n, d_privs, d_pubkeys_aff, d_aux, d_hash_slots,
+					      stride, d_sigs, d_status, hip_stream);
+}
+
+extern "C" int ec_bip0340_sign_ht_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs,
+					    const void *d_pubkeys_aff, const void *d_aux, const void *d_hash_slots, uint32_t stride, void *d_sigs,
+					    void *d_status, void *hip_stream)
+{
+	return ec_bip0340_sign_batch_dev_impl("ec_bip0340_sign_ht_batch_dev", true, ctx, cv, hash_type, n, d_privs, d_pubkeys_aff, d_aux,
+					      d_hash_slots, stride, d_sigs, d_status, hip_stream);
+}
+
+extern "C" int ec_bip0340_nonce_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+				      const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *nonces,
+				      uint8_t *status)
+{
+	return ec_bip0340_nonce_batch_impl("ec_bip0340_nonce_batch", false, ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride,
+					   nonces, status);
+}
+
+extern "C" int ec_bip0340_nonce_ht_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+					 const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *nonces,
+					 uint8_t *status)
+{
+	return ec_bip0340_nonce_batch_impl("ec_bip0340_nonce_ht_batch", true, ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride,
+					   nonces, status);
+}
+
+extern "C" int ec_bip0340_sign_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+				     const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+				     uint8_t *status)
+{
+	return ec_bip0340_sign_batch_impl("ec_bip0340_sign_batch", false, ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, sigs,
+					  status);
+}
+
+extern "C" int ec_bip0340_sign_ht_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs,
+					const uint8_t *pubkeys_aff, const uint8_t *aux, const uint8_t *hash_slots, uint32_t stride, uint8_t *sigs,
+					uint8_t *status)
+{
+	return ec_bip0340_sign_batch_impl("ec_bip0340_sign_ht_batch", true, ctx, cv, hash_type, n, privs, pubkeys_aff, aux, hash_slots, stride, sigs,
+					  status);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1473,8 +1769,6 @@ extern "C" int ec_digest_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, 
 //   ecdsa_sign_dev_locked       [k]G as the context's secret-scalar mode says, r, s; k = 0 is status 1 with zero bytes
 // Streebog's look-ups are indexed by key-dependent octets: the three calls refuse 13 and 14 in secret-scalar mode.  Only enqueues.
 // ------------------------------------------------------------------------------------------
-static const char *const HT_SET = "hash_type must be 1 .. 11, 13 .. 15 or 17 .. 20 (every fixed-length hash of libecc's table but belt-hash)";
-
 static int ht_hash_ok(const char *fn, const ecamd_ctx *ctx, int hash_type)
 {
 	if (!ecamd_hmac_served(hash_type)) {

@@ -729,6 +729,21 @@ struct EcamdBip0340NonceArgs {
 	uint64_t tag_aux[8], tag_nonce[8];   // H("BIP0340/aux"), H("BIP0340/nonce") as the hash's words (a 32-bit word in the low half)
 };
 hipError_t ecamd_launch_bip0340_nonce(int hash_type, const EcamdBip0340NonceArgs &a, hipStream_t s);
+// the same nonce over the hashes of ecamd_launch_digest_slots that k_bip0340_nonce does not have (ecamd_bip0340_nonce_ht.h /
+// ecamd_bip0340_nonce_ht.hip: k_bip0340_nonce_ht<ID>); hash_type 5 .. 11, 13 .. 15, 17 .. 20 -- 1 .. 4 stay with the launcher above
+struct EcamdBip0340NonceHtArgs {
+	const uint8_t *privs;    // n x qlen big-endian
+	const uint8_t *keys;     // n x 2*clen: the public keys, affine
+	const uint8_t *kst;      // n: a non-zero byte fails the item (the key did not import, or [x]G is the point at infinity)
+	const uint8_t *aux;      // n x qlen big-endian
+	const uint8_t *slots;    // n x stride: BIP0340 signing slots (u32 length, the fixed fields, the message)
+	uint8_t *nonces;         // n x qlen big-endian (secret)
+	uint8_t *status;         // n: 0, or 1 with a zero nonce
+	uint32_t n, qlen, qbits, clen, stride;
+	uint32_t q[17];          // the generator's order, little-endian words
+	uint32_t tag_aux[16], tag_nonce[16];   // H("BIP0340/aux"), H("BIP0340/nonce"): the digest's octets, four per word in memory order
+};
+hipError_t ecamd_launch_bip0340_nonce_ht(int hash_type, const EcamdBip0340NonceHtArgs &a, hipStream_t s);
 // the hashing front end of one-call EdDSA signing (ecamd_eddsa_sign.h / ecamd_eddsa_sign.hip); alg: libecc's ec_alg_type 9 .. 13,
 // klen = 32 / 57, hlen = 64 / 114.  Three steps share the structure:
 //   expand  (k_eddsa_expand_r)  sk, slots -> a, r_hash, a_wide (unless NULL), ph (PH variants), bad; slots == NULL: the key

@@ -154,7 +154,7 @@ template <int NW> __global__ __launch_bounds__(64) void k_schnorr_item_sign(Ecam
 // every byte the kernels write into a staged slot lies inside it: the fixed fields fit the stride
 static bool schnorr_item_args_sane(const EcamdSchnorrItemArgs &a)
 {
-	return ecschnorr::alg_known(a.alg) && a.hsize >= 28 && a.hsize <= 64 && a.clen >= 1 && a.clen <= 72 && (a.sstride & 3u) == 0 &&
+	return ecschnorr::alg_known(a.alg) && a.hsize >= 20 && a.hsize <= 64 && a.clen >= 1 && a.clen <= 72 && (a.sstride & 3u) == 0 &&   // 20: RIPEMD-160
 	       a.sstride >= 4u + (uint32_t)ecschnorr::fixed_len(a.alg, (int)a.hsize, (int)a.clen);
 }
 

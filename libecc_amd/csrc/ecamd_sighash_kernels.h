@@ -111,7 +111,7 @@ template <int NW> __global__ __launch_bounds__(64) void k_hsig_sign(EcamdHsigArg
 
 static bool hsig_args_sane(const EcamdHsigArgs &a)
 {
-	return echsig::alg_known(a.alg) && a.hsize >= 28 && a.hsize <= 64 && a.clen >= 1 && a.clen <= 72;
+	return echsig::alg_known(a.alg) && a.hsize >= 20 && a.hsize <= 64 && a.clen >= 1 && a.clen <= 72;   // 20: RIPEMD-160
 }
 
 hipError_t ecamd_launch_hsig_prep(int nw, const EcamdHsigArgs &a, hipStream_t s)

@@ -4,7 +4,8 @@ BASELINE.json configs[3] (secp256r1 ECDSA batch verification) and configs[4] (Ed
 X25519).  Same launch contract and JSON line as bench.py (one process per GPU under
 torch.distributed.run, weak scaling, contiguous shards, one RCCL all-gather of the per-rank result
 bytes per step); not the driver's headline bench.  --workload ecdsa_recover is the exception: one GPU, recovery beside the
-verification of the same signatures in alternating windows (recover_row).
+verification of the same signatures in alternating windows (recover_row).  sig_hashed_verify / sig_hashed_sign / schnorr_verify /
+schnorr_sign / bip0340_sign with --hash 5 .. 11, 13 .. 15, 17 .. 20 or --hashes LIST|new go through the _ht entry points (commit_ht_rows).
 
     python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|sig_msg_verify|sig_msg_sign|hash_slots [--alg sm2|ecrdsa|ecgdsa --hash 11|13|14|2 --curve C]|digest_slots|hmac_slots [--hash 1..11|13..15|17..20]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..11|13..15|17..20 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
@@ -1139,6 +1140,154 @@ def eddsa_sign_row(a, ctx, dev, stream, rng, B):
     ctx.close()
 
 
+NEW_COMMIT_HASHES = [5, 6, 7, 8, 9, 10, 11, 13, 14, 15, 17, 18, 19, 20]
+HASH_BLOCKS = {1: 64, 2: 64, 3: 128, 4: 128, 5: 144, 6: 136, 7: 104, 8: 72, 9: 128, 10: 128, 11: 64, 13: 64, 14: 64, 15: 64, 17: 136, 18: 128, 19: 96,
+               20: 64}
+
+
+def commit_ht_rows(a, ctx, dev, stream, rng, B, hashes):
+    """sig_hashed_verify / sig_hashed_sign / schnorr_verify / schnorr_sign / bip0340_sign with a hash of ec_digest_slots_batch that the
+    older names refuse (--hash 5 .. 11, 13 .. 15, 17 .. 20, or --hashes): the _ht entry point under that hash beside its SHA-256 twin
+    through the OLD name on the same keys, and beside the bare ec_digest_slots_batch_dev of both hashes at the length of each one's
+    commitment hash input, in alternating windows of a.steps calls in one run.  bip0340_sign also times the nonce call by itself
+    (keys supplied, so it is the on-curve test and the nonce kernel).  32-octet messages, device-resident inputs, 4096 distinct keys
+    tiled over the batch.  ECKCDSA's h = H(z || m) is made by ec_digest_slots_batch_dev before the timed region, as the header's
+    composition does it.  Gates per hash: every item signs, every device-made signature is accepted, none for its neighbour's input.
+    One JSON line per hash.  expected_ms = twin + (bare_new - bare_twin)."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload %s measures one GPU: run it with --gpus 1, outside torch.distributed.run" % a.workload)
+    import oracles as O
+    from libecc_amd.api import DIGEST_SIZES
+    wl = a.workload
+    if wl.startswith("sig_hashed"):
+        alg = {"eckcdsa": 2, "ecsdsa": 3, "ecosdsa": 4}.get(a.alg)
+    elif wl.startswith("schnorr"):
+        alg = {"bip0340": 20, "ecfsdsa": 5}.get(a.alg)
+    else:
+        alg = 20
+    if alg is None:
+        raise SystemExit("--workload %s: --alg does not name one of its schemes" % wl)
+    sign, derive, hsig, bip, kcdsa = wl.endswith("_sign"), wl == "bip0340_sign", alg in (2, 3, 4), alg == 20, alg == 2
+    curve = a.curve
+    cv = ctx.curve(curve)
+    q, ql, cl, mlen = O.CURVES[curve]["q"], O.qlen(curve), O.clen(curve), 32
+    if q.bit_length() <= 8 * ql - 8:
+        raise SystemExit("--workload %s: the order must fill its top octet's neighbour (nonces are drawn below 2^(8 qlen - 8))" % wl)
+    K = min(B, 4096)
+    xs = [1 + int.from_bytes(rng.integers(0, 256, size=ql + 8, dtype=np.uint8).tobytes(), "big") % (q - 1) for _ in range(K)]
+    pubs_k, st = cv.scalar_mult(b"".join((pow(x, -1, q) if kcdsa else x).to_bytes(ql, "big") for x in xs))
+    assert set(st) == {0}
+    tile = lambda bs, w: np.tile(np.frombuffer(bs, dtype=np.uint8).reshape(K, w), (B // K, 1))
+    privs, pubs = tile(b"".join(x.to_bytes(ql, "big") for x in xs), ql), tile(pubs_k, 2 * cl)
+    vals = rng.integers(0, 256, size=(B, ql), dtype=np.uint8)      # nonces (below 2^(8 qlen - 8) < q, odd) or BIP0340's aux values
+    if not derive:
+        vals[:, 0] = 0
+        vals[:, -1] |= 1
+    msgs = rng.integers(0, 256, size=(B, mlen), dtype=np.uint8)
+    S = stream.cuda_stream
+    tt = lambda arr: torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
+    d_priv, d_pub, d_val = tt(privs), tt(pubs), tt(vals)
+    d_st, d_res = torch.empty(B, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+
+    def slots_of(fixed, length):
+        stride = (4 + length + 3) & ~3
+        sl = np.zeros((B, stride), dtype=np.uint8)
+        sl[:, :4] = np.frombuffer(np.uint32(length).tobytes(), dtype=np.uint8)
+        sl[:, 4:4 + len(fixed)] = np.frombuffer(fixed, dtype=np.uint8) if fixed else 0
+        return sl, stride
+
+    def setup(ht, new):
+        """the device inputs of one hash, its signatures (made by the device, all status 0) and the four timed calls"""
+        hs, blk = DIGEST_SIZES[ht], HASH_BLOCKS[ht]
+        sfx = "_ht" if new else ""
+        if kcdsa:
+            z = np.zeros((B, blk), dtype=np.uint8)
+            z[:, :min(blk, 2 * cl)] = pubs[:, :min(blk, 2 * cl)]
+            zs, zstride = slots_of(b"", blk + mlen)
+            zs[:, 4:4 + blk], zs[:, 4 + blk:4 + blk + mlen] = z, msgs
+            d_in, stride = torch.empty(B * hs, dtype=torch.uint8, device=dev), hs
+            ctx.digest_slots_dev(ht, B, tt(zs).data_ptr(), zstride, d_in.data_ptr(), S)
+            hin = cl                                                   # the device hashes FE2OS(W.x)
+        else:
+            if bip:
+                tag = ctx.digest_slots(ht, (17).to_bytes(4, "little") + b"BIP0340/challenge" + bytes(3), 24)
+                fixed = tag + tag + bytes(2 * cl)
+            else:
+                fixed = bytes(cl if alg == 4 else 2 * cl)
+            hin = len(fixed) + mlen
+            sl, stride = slots_of(fixed, hin)
+            sl[:, 4 + len(fixed):4 + hin] = msgs
+            d_in = tt(sl)
+        siglen = ((min(hs, ql) if kcdsa else hs) if hsig else (cl if bip else 2 * cl)) + ql
+        d_sig = torch.empty(B * siglen, dtype=torch.uint8, device=dev)
+        P = lambda x: x.data_ptr()
+        if hsig:
+            do_sign = lambda: getattr(cv, "sig_hashed_sign%s_dev" % sfx)(alg, ht, B, P(d_priv), P(d_val), P(d_in), stride, P(d_sig), P(d_st), S)
+            do_ver = lambda inp: getattr(cv, "sig_hashed_verify%s_dev" % sfx)(alg, ht, B, P(d_pub), P(d_sig), P(inp), stride, P(d_res), S)
+        else:
+            if derive:
+                do_sign = lambda: getattr(cv, "bip0340_sign%s_dev" % sfx)(ht, B, P(d_priv), None, P(d_val), P(d_in), stride, P(d_sig), P(d_st), S)
+            else:
+                do_sign = lambda: getattr(cv, "schnorr_sign%s_dev" % sfx)(alg, ht, B, P(d_priv), None, P(d_val), P(d_in), stride, P(d_sig), P(d_st), S)
+            do_ver = lambda inp: getattr(cv, "schnorr_verify%s_dev" % sfx)(alg, ht, B, P(d_pub), 0, P(d_sig), P(inp), stride, P(d_res), S)
+        do_sign()
+        torch.cuda.synchronize()
+        if bytes(d_st.cpu().numpy()) != bytes(B):
+            raise SystemExit("PARITY FAILURE: hash %d: an item did not sign" % ht)
+        do_ver(d_in)
+        torch.cuda.synchronize()
+        if bytes(d_res.cpu().numpy()) != bytes(B):
+            raise SystemExit("PARITY FAILURE: hash %d: a signature the device made was rejected" % ht)
+        do_ver(torch.roll(d_in, stride))
+        torch.cuda.synchronize()
+        if bytes(d_res.cpu().numpy()) != b"\1" * B:
+            raise SystemExit("PARITY FAILURE: hash %d: a signature was accepted for another item's input" % ht)
+        bs, bstride = slots_of(b"", hin)
+        bs[:, 4:4 + hin] = rng.integers(0, 256, size=(B, hin), dtype=np.uint8)
+        d_bare, d_dg = tt(bs), torch.empty(B * hs, dtype=torch.uint8, device=dev)
+        bare = lambda: ctx.digest_slots_dev(ht, B, P(d_bare), bstride, P(d_dg), S)
+        nonce = None
+        if derive:
+            d_k = torch.empty(B * ql, dtype=torch.uint8, device=dev)
+            nonce = lambda: getattr(cv, "bip0340_nonce%s_dev" % sfx)(ht, B, P(d_priv), P(d_pub), P(d_val), P(d_in), stride, P(d_k), P(d_st), S)
+        keep = (d_in, d_sig, d_bare, d_dg)
+        return (do_sign if sign else (lambda: do_ver(d_in))), bare, nonce, hin, keep
+
+    twin = setup(2, False)
+    for ht in hashes:
+        new = setup(ht, True)
+        fns = [("twin", twin[0]), ("new", new[0]), ("bare_new", new[1]), ("bare_twin", twin[1])]
+        if derive:
+            fns += [("nonce_new", new[2]), ("nonce_twin", twin[2])]
+        for _ in range(a.warmup):
+            for _, fn in fns:
+                fn()
+        torch.cuda.synchronize()
+        acc = {name: [] for name, _ in fns}
+        for _ in range(3):
+            for name, fn in fns:
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    fn()
+                torch.cuda.synchronize()
+                acc[name].append(1e3 * (time.perf_counter() - t0) / a.steps)
+        med = {name: float(np.median(v)) for name, v in acc.items()}
+        expected = med["twin"] + med["bare_new"] - med["bare_twin"]
+        kind = "signatures" if sign else "verifications"
+        rec = {"metric": "%s %s/sec (%s, hash %d through the _ht name, batch=2^%d, device-resident)" % (a.alg.upper() if not derive else "BIP0340", kind,
+                                                                                                         curve.lower(), ht, a.batch_log2),
+               "value": B / (1e-3 * med["new"]), "unit": kind + "/s", "hash": ht, "ms": med, "windows_ms": acc, "hash_input_octets": {"new": new[3], "twin": twin[3]},
+               "expected_ms": expected, "new_over_expected": med["new"] / expected,
+               "gate": "all 2^%d items sign, all device-made signatures accepted, none for its neighbour's input" % a.batch_log2,
+               "config": {"workload": wl, "alg": a.alg, "curve": curve, "steps": a.steps, "warmup": a.warmup, "windows": 3}}
+        if derive:
+            rec["nonce_over_bare"] = {"new": med["nonce_new"] / med["bare_new"], "twin": med["nonce_twin"] / med["bare_twin"]}
+        print(json.dumps(rec), flush=True)
+        del new
+    cv.free()
+    ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_msg_verify", "sig_msg_sign", "hash_slots", "digest_slots", "hmac_slots", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
@@ -1148,6 +1297,8 @@ def main():
     ap.add_argument("--hash", type=int, default=None, choices=[0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 14, 15, 16, 17, 18, 19, 20],
                     help="bign_verify / bign_sign: 0 the caller hashed (SHA-256 digests supplied), 16 (default) belt-hash of message slots on the device; "
                          "decdsa_sign: SHA-256 by default, 1 .. 4 through ec_decdsa_sign_batch, the rest through ec_decdsa_sign_ht_batch; digest_slots, hmac_slots: any of libecc's numbers but 0 and 16 (default 6, SHA3-256)")
+    ap.add_argument("--hashes", default=None, help="sig_hashed_verify / sig_hashed_sign / schnorr_verify / schnorr_sign / bip0340_sign: a comma-separated list of the "
+                    "hash numbers 5 .. 11, 13 .. 15, 17 .. 20, or 'new' for all fourteen, measured in one run through the _ht names (--hash N: one of them)")
     ap.add_argument("--secret", action="store_true", help="dbign_sign / bip0340_sign: the context in secret-scalar mode")
     ap.add_argument("--derive-pub", action="store_true", help="eddsa_sign: pubkeys = NULL, A = encode([a]B) derived on the device (a second comb multiplication per item)")
     ap.add_argument("--gpus", type=int, default=1)
@@ -1162,6 +1313,14 @@ def main():
     ap.add_argument("--mad-peak", type=float, default=0.0, help="lane-MADs/s of the v_mad_u64_u32 streams measured by ubench (VGPR multiplier); 0: measure now")
     ap.add_argument("--mad-peak-sgpr", type=float, default=0.0, help="the same with an SGPR multiplier")
     a = ap.parse_args()
+    commit_hashes = None
+    if a.workload in ("sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bip0340_sign"):
+        if a.hashes is not None:
+            commit_hashes = NEW_COMMIT_HASHES if a.hashes == "new" else [int(h) for h in a.hashes.split(",")]
+        elif a.hash in NEW_COMMIT_HASHES:
+            commit_hashes = [a.hash]
+        if commit_hashes is not None and not set(commit_hashes) <= set(NEW_COMMIT_HASHES):
+            raise SystemExit("--workload %s: --hash / --hashes 5 .. 11, 13 .. 15 or 17 .. 20 (1 .. 4 are the workload without --hash)" % a.workload)
     if a.hash is None and a.workload in ("sig_msg_verify", "sig_msg_sign", "hash_slots"):
         a.hash = {"sm2": 11, "ecrdsa": 13, "ecgdsa": 2}.get(a.alg, 11)   # the hash each scheme is deployed with
     if a.hash is None and a.workload in ("digest_slots", "hmac_slots"):
@@ -1215,6 +1374,8 @@ def main():
         return digest_slots_row(a, ctx, dev, stream, rng, B)
     if a.workload == "hmac_slots":
         return hmac_slots_row(a, ctx, dev, stream, rng, B)
+    if commit_hashes is not None:
+        return commit_ht_rows(a, ctx, dev, stream, rng, B, commit_hashes)
     if a.workload in ("sig_hashed_verify", "sig_hashed_sign"):
         return sig_hashed_row(a, ctx, dev, stream, rng, B)
     if a.workload in ("schnorr_verify", "schnorr_sign"):
