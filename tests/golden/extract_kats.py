@@ -13,6 +13,12 @@ Sources (data only -- byte arrays and the record fields that bind them):
   src/tests/ed25519ctx_test_vectors.h, ed25519ph_test_vectors.h   RFC 8032 vectors
   src/tests/ed448_test_vectors.h, ed448ph_test_vectors.h   RFC 8032 vectors
 Writes tests/golden/ecccdh_kats.json, ecdsa_kats.json, xdh_kats.json, eddsa_kats.json and eddsa448_kats.json.
+
+The reference's known answers of the other signature families have generators of their own, which read the headers the same way:
+  make_sig_msg_fixture.py    SM2 and ECRDSA                                            -> sig_msg.json
+  make_det_sign_fixture.py   DBIGN 1 - 3 and BIP0340 (signing)                         -> det_sign.json
+  make_sig_kats_fixture.py   ECKCDSA, ECSDSA, ECOSDSA, ECFSDSA, ECGDSA (ec_self_tests_core.h), BIGN (bign_test_vectors.h) and
+                             DBIGN 4 - 7 (dbign_test_vectors.h), with the reference's verdicts on damaged variants -> sig_kats.json
 """
 import json, os, re, sys
 
