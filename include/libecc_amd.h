@@ -368,6 +368,65 @@ int ec_digest_slots_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8
 int ec_digest_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_msg_slots, uint32_t stride, void *d_digests,
 			      void *hip_stream);
 /*
+ * The same hashes over VARIABLE-LENGTH messages: one packed array of octets and n + 1 offsets in place of fixed-stride slots, so a message
+ * may have any length (up to 2^28 octets), a batch of unequal messages uploads its octets and nothing else, and the prefixes libecc's
+ * schemes put in front of a message are given once, not copied into every item.  Item i hashes
+ *     call_prefix || item_prefixes[i] || msgs[offsets[i] .. offsets[i + 1])
+ *   hash_type    the set of ec_digest_slots_batch: 1 .. 11, 13 .. 15, 17 .. 20; anything else is a call-level error.
+ *   msgs         the messages one behind the other.  offsets: n + 1 uint64_t in host byte order (little-endian), offsets[n] the
+ *                array's length in the host form.  Offsets need not be contiguous or increasing from item to item: each item stands
+ *                alone.
+ *   call_prefix  0 .. 256 octets, the same for every item; a HOST pointer in both forms (as SM2's id is).  NULL with length 0.
+ *   item_prefixes  item_prefix_len octets (0 .. 256, one length per call) at item_prefixes + i * item_prefix_stride
+ *                (item_prefix_stride >= item_prefix_len; any alignment).  NULL with length 0.
+ *   digests      n x ecamd_digest_len(hash_type) octets.  status (n octets, may be NULL): 0, or 1 with an ALL-ZERO digest for an item
+ *                that is unusable: offsets[i] > offsets[i + 1], offsets[i + 1] > the array's length, or an input (both prefixes
+ *                and the message) above 2^28 octets.  Nothing of msgs is read for such an item.
+ * A prefix length above 256, a NULL pointer with a positive length or a stride below the length is a call-level error (-1,
+ * ecamd_last_error()).  n = 0 (returns 0, touches nothing), NULL arguments, a foreign context as for ec_digest_slots_batch; everything
+ * hashed is public and nothing differs under ecamd_ctx_set_secret_scalars.
+ * _dev form: d_msgs must be 4-byte aligned and readable up to round_up(msgs_len, 4) (the kernel reads aligned 32-bit words, and only
+ * words that hold an octet of the item's own message); d_offsets 8-byte aligned; the kernel validates every item against msgs_len
+ * itself.  It only enqueues, in pieces of at most ecamd_ctx_set_max_chunk items.
+ * Host form: a piece of the batch ends at ecamd_ctx_set_max_chunk items or when the messages of its usable items span more than
+ * 2^28 octets of the array (MSGS_CHUNK_BYTES in ecamd_host_sigfam.cpp), whichever comes first; a single longer message is a piece of
+ * its own.  Each piece is staged with offsets rebased to it; ecamd_ctx_wipe_scratch covers the staging.
+ *
+ * COMPOSITION, as above: every digest-level _dev call takes these digests on the same stream, and the two prefixes are what libecc's
+ * schemes hash in front of the message --
+ *   ECKCDSA   item_prefix = z (the key's certificate data, BLOCK octets of the hash), then ec_sig_hashed_verify_ht_batch_dev /
+ *             ec_sig_hashed_sign_ht_batch_dev with the digests as their input
+ *   SM2       item_prefix = Z, then ec_sig_verify_batch_dev / ec_sig_sign_batch_dev
+ *   Ed25519   call_prefix = dom2 (empty for pure Ed25519), item_prefix = R || A, hash_type 4, then ec_eddsa_verify_batch
+ * Out of scope: the slot formats of ECSDSA, ECOSDSA, ECFSDSA and BIP0340 (their message sits behind a point that exists only inside
+ * the call), SHAKE256 and belt-hash, HMAC over this format, the ecamd_multi_* wrappers and the libecc-typed layer.
+ */
+int ec_digest_msgs_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *msgs, const uint64_t *offsets, const uint8_t *call_prefix,
+			 uint32_t call_prefix_len, const uint8_t *item_prefixes, uint32_t item_prefix_len, uint32_t item_prefix_stride,
+			 uint8_t *digests, uint8_t *status);
+int ec_digest_msgs_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_msgs, uint64_t msgs_len, const void *d_offsets,
+			     const uint8_t *call_prefix, uint32_t call_prefix_len, const void *d_item_prefixes, uint32_t item_prefix_len,
+			     uint32_t item_prefix_stride, void *d_digests, void *d_status, void *hip_stream);
+/*
+ * Two protocols straight from that format (no prefixes), so that a signature is reached without the caller handling digests:
+ *   ec_ecdsa_verify_msgs_batch   ec_pub_key_import_from_aff_buf + ec_verify(ECDSA) per item with any hash of ec_digest_msgs_batch: the
+ *              verdicts of ec_ecdsa_verify_batch fed with libecc's digests; an unusable item (see status above) is result 1.
+ *   ec_decdsa_sign_msgs_batch    ec_decdsa_sign_ht_batch with msgs / offsets in place of slots: key rules, the restart rule, the wiped
+ *              nonce scratch and the refusal of Streebog (13, 14) in secret-scalar mode unchanged; an unusable item is status 1 with
+ *              zero bytes.
+ * Layouts of keys, signatures, result and status as for ec_ecdsa_verify_batch and ec_decdsa_sign_ht_batch; msgs, offsets, msgs_len,
+ * alignment, pieces and n = 0 as for ec_digest_msgs_batch[_dev].  The _dev forms only enqueue.
+ */
+int ec_ecdsa_verify_msgs_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *pubkeys_aff,
+			       const uint8_t *sigs, const uint8_t *msgs, const uint64_t *offsets, uint8_t *result);
+int ec_ecdsa_verify_msgs_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_pubkeys_aff,
+				   const void *d_sigs, const void *d_msgs, uint64_t msgs_len, const void *d_offsets, void *d_result,
+				   void *hip_stream);
+int ec_decdsa_sign_msgs_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *msgs,
+			      const uint64_t *offsets, uint8_t *sigs, uint8_t *status);
+int ec_decdsa_sign_msgs_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int hash_type, uint32_t n, const void *d_privs, const void *d_msgs,
+				  uint64_t msgs_len, const void *d_offsets, void *d_sigs, void *d_status, void *hip_stream);
+/*
  * ECSDSA, ECOSDSA and ECKCDSA: the schemes of libecc's table that hash AFTER the multiplication.  The verifier computes
  * W' = [u]G + [v]Y, hashes its affine coordinates on the device and compares the digest with the signature's r byte for byte; the
  * signer hashes W = [k]G and derives e = digest mod q.  alg: libecc's ec_alg_type numbers; hash_type: libecc's hash_alg_type

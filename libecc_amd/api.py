@@ -45,6 +45,8 @@ EXPORTED_SYMBOLS = [
     "ec_sig_hashed_verify_ht_batch", "ec_sig_hashed_verify_ht_batch_dev", "ec_sig_hashed_sign_ht_batch", "ec_sig_hashed_sign_ht_batch_dev",
     "ec_schnorr_verify_ht_batch", "ec_schnorr_verify_ht_batch_dev", "ec_schnorr_sign_ht_batch", "ec_schnorr_sign_ht_batch_dev",
     "ec_bip0340_nonce_ht_batch", "ec_bip0340_nonce_ht_batch_dev", "ec_bip0340_sign_ht_batch", "ec_bip0340_sign_ht_batch_dev",
+    "ec_digest_msgs_batch", "ec_digest_msgs_batch_dev", "ec_ecdsa_verify_msgs_batch", "ec_ecdsa_verify_msgs_batch_dev",
+    "ec_decdsa_sign_msgs_batch", "ec_decdsa_sign_msgs_batch_dev",
 ]
 
 # libecc's ec_alg_type numbers of the EdDSA variants ec_eddsa_sign_msg_batch serves (lib_ecc_types.h:49-55)
@@ -70,6 +72,15 @@ DIGEST_SIZES = {**HASH_SLOT_SIZES, 5: 28, 6: 32, 7: 48, 8: 64, 9: 28, 10: 32, 15
 
 class EcamdError(RuntimeError):
     pass
+
+
+def pack_msgs(msgs):
+    """a list of `bytes` as the packed array and the n + 1 u64 offsets of the ec_*_msgs_batch calls"""
+    offs, pos = (C.c_uint64 * (len(msgs) + 1))(), 0
+    for i, m in enumerate(msgs):
+        pos += len(m)
+        offs[i + 1] = pos
+    return b"".join(msgs), offs
 
 
 def lib_path():
@@ -154,6 +165,13 @@ def load_library():
         L.ecamd_digest_len.argtypes = [C.c_int]
         L.ec_digest_slots_batch.argtypes = [vp, C.c_int, u32, u8p, u32, u8p]
         L.ec_digest_slots_batch_dev.argtypes = [vp, C.c_int, u32, vp, u32, vp, vp]
+        u64 = C.c_uint64
+        L.ec_digest_msgs_batch.argtypes = [vp, C.c_int, u32, u8p, vp, u8p, u32, u8p, u32, u32, u8p, u8p]
+        L.ec_digest_msgs_batch_dev.argtypes = [vp, C.c_int, u32, vp, u64, vp, u8p, u32, vp, u32, u32, vp, vp, vp]
+        L.ec_ecdsa_verify_msgs_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, vp, u8p]
+        L.ec_ecdsa_verify_msgs_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, vp, u64, vp, vp, vp]
+        L.ec_decdsa_sign_msgs_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, vp, u8p, u8p]
+        L.ec_decdsa_sign_msgs_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u64, vp, vp, vp, vp]
         L.ec_sig_hashed_verify_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p]
         L.ec_sig_hashed_sign_batch.argtypes = [vp, vp, C.c_int, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u8p]
         L.ec_sig_hashed_verify_batch_dev.argtypes = [vp, vp, C.c_int, C.c_int, u32, vp, vp, vp, u32, vp, vp]
@@ -277,6 +295,26 @@ class Context:
 
     def digest_slots_dev(self, hash_type, n, d_slots, stride, d_digests, stream=None):
         _chk(self.L, self.L.ec_digest_slots_batch_dev(self.h, hash_type, n, d_slots, stride, d_digests, stream), "ec_digest_slots_batch_dev")
+
+    def digest_msgs(self, hash_type, msgs, call_prefix=b"", item_prefixes=None):
+        """the device hash over the whole table (DIGEST_SIZES) of call_prefix || item_prefixes[i] || msgs[i] for a list of `bytes` of any
+        lengths, through the packed array and its offsets: (n x digest size bytes, n status bytes -- 1 with a zero digest where the
+        input exceeds 2^28 octets).  item_prefixes: a list of n `bytes` of one length (at most 256), or None"""
+        n = len(msgs)
+        packed, offs = pack_msgs(msgs)
+        ipl = len(item_prefixes[0]) if item_prefixes else 0
+        assert item_prefixes is None or (len(item_prefixes) == n and all(len(p) == ipl for p in item_prefixes))
+        dl = DIGEST_SIZES.get(hash_type, 0)
+        out, st = C.create_string_buffer(max(1, n * dl)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_digest_msgs_batch(self.h, hash_type, n, packed, offs, call_prefix, len(call_prefix),
+                                                 b"".join(item_prefixes) if ipl else None, ipl, ipl, out, st), "ec_digest_msgs_batch")
+        return out.raw[:n * dl], st.raw[:n]
+
+    def digest_msgs_dev(self, hash_type, n, d_msgs, msgs_len, d_offsets, d_digests, d_status=None, call_prefix=b"", d_item_prefixes=None,
+                        item_prefix_len=0, item_prefix_stride=0, stream=None):
+        """the same on device pointers (d_msgs 4-byte aligned and readable up to round_up(msgs_len, 4); d_offsets n + 1 u64); only enqueues"""
+        _chk(self.L, self.L.ec_digest_msgs_batch_dev(self.h, hash_type, n, d_msgs, msgs_len, d_offsets, call_prefix, len(call_prefix), d_item_prefixes,
+                                                     item_prefix_len, item_prefix_stride, d_digests, d_status, stream), "ec_digest_msgs_batch_dev")
 
     def hmac_slots(self, hash_type, key_slots, key_stride, msg_slots, stride):
         """HMAC over any hash of DIGEST_SIZES of n (key slot, message slot) pairs: n x digest size bytes; a key or a message that does
@@ -628,6 +666,22 @@ class Curve:
              "ec_decdsa_sign_batch")
         return sigs.raw[:2 * self.qlen * n], st.raw[:n]
 
+    def ecdsa_verify_msg_list(self, hash_type, pubs, sigs, msgs):
+        """(ecdsa_verify_msgs is the older call over equal-length messages in slots and keeps its name.)  ECDSA verification of a list of `bytes` of any lengths, hashed on the device with any hash of DIGEST_SIZES: n result bytes"""
+        n = len(msgs)
+        packed, offs = pack_msgs(msgs)
+        res = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_ecdsa_verify_msgs_batch(self.ctx.h, self.h, hash_type, n, pubs, sigs, packed, offs, res), "ec_ecdsa_verify_msgs_batch")
+        return res.raw[:n]
+
+    def decdsa_sign_msgs(self, hash_type, privs, msgs):
+        """decdsa_sign_ht over a list of `bytes` of any lengths: (n x 2 qlen signature bytes, n status bytes)"""
+        n = len(msgs)
+        packed, offs = pack_msgs(msgs)
+        sigs, st = C.create_string_buffer(max(1, 2 * self.qlen * n)), C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_decdsa_sign_msgs_batch(self.ctx.h, self.h, hash_type, n, privs, packed, offs, sigs, st), "ec_decdsa_sign_msgs_batch")
+        return sigs.raw[:2 * self.qlen * n], st.raw[:n]
+
     def rfc6979_nonce_ht(self, hash_type, privs, digests):
         """rfc6979_nonce with HMAC over any hash of DIGEST_SIZES (digests: n x DIGEST_SIZES[hash_type])"""
         n = len(privs) // self.qlen
@@ -970,6 +1024,14 @@ class Curve:
     def rfc6979_nonce_ht_dev(self, hash_type, n, d_privs, d_digests, d_nonces, d_status, stream=None):
         _chk(self.L, self.L.ec_rfc6979_nonce_ht_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_digests, d_nonces, d_status, stream),
              "ec_rfc6979_nonce_ht_batch_dev")
+
+    def ecdsa_verify_msgs_dev(self, hash_type, n, d_pubs, d_sigs, d_msgs, msgs_len, d_offsets, d_result, stream=None):
+        _chk(self.L, self.L.ec_ecdsa_verify_msgs_batch_dev(self.ctx.h, self.h, hash_type, n, d_pubs, d_sigs, d_msgs, msgs_len, d_offsets, d_result,
+                                                           stream), "ec_ecdsa_verify_msgs_batch_dev")
+
+    def decdsa_sign_msgs_dev(self, hash_type, n, d_privs, d_msgs, msgs_len, d_offsets, d_sigs, d_status, stream=None):
+        _chk(self.L, self.L.ec_decdsa_sign_msgs_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_msgs, msgs_len, d_offsets, d_sigs, d_status,
+                                                          stream), "ec_decdsa_sign_msgs_batch_dev")
 
     def decdsa_sign_ht_dev(self, hash_type, n, d_privs, d_in, stride, is_digest, d_sigs, d_status, stream=None):
         _chk(self.L, self.L.ec_decdsa_sign_ht_batch_dev(self.ctx.h, self.h, hash_type, n, d_privs, d_in, stride, 1 if is_digest else 0, d_sigs,

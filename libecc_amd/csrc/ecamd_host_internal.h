@@ -4,7 +4,8 @@
 //   ecamd_host.cpp         errors, host big integers, the context, curve handles, scratch sizing, host_pipeline and the heads of the entry
 //                          points, scalar multiplication and point operations, ECDSA and its relatives, XDH, EdDSA, the whole-batch forms
 //   ecamd_host_sigfam.cpp  ECKCDSA / ECSDSA / ECOSDSA, BIGN / DBIGN, BIP0340 / ECFSDSA, message-level ECGDSA / ECRDSA / SM2, ec_hash_slots_*,
-//                          ec_digest_slots_*, HMAC and deterministic ECDSA over the whole hash table (ec_hmac_slots_*, ec_*_ht_*)
+//                          ec_digest_slots_*, HMAC and deterministic ECDSA over the whole hash table (ec_hmac_slots_*, ec_*_ht_*),
+//                          the ragged message array (ec_digest_msgs_*, ec_ecdsa_verify_msgs_*, ec_decdsa_sign_msgs_*)
 //                          and the _ht names of the three commitment-hashing families (ec_sig_hashed_*_ht_*, ec_schnorr_*_ht_*, ec_bip0340_*_ht_*)
 // A protocol family lives in exactly one unit.  This header declares only what more than one unit uses; what one unit needs stays
 // `static` in its file.  The shared functions are in namespace ecamd_host with hidden visibility: none of them enters the library's
@@ -81,6 +82,8 @@ int fail(const std::string &m);   // files the thread's error string (ecamd_last
 //        sig_target           29            ST_TARGET: the comparison target of ECGDSA / ECRDSA / SM2, beside ST_ and VP_
 //   ES_  one-call EdDSA sign  30..40        eddsa_sign_msg_dev_locked, eddsa_pub_key_dev_locked    SR_
 //   SM_  sig from messages    41, 42        sig_msg_verify_ / sig_msg_sign_dev_locked, which outlive the digest-level core they call   ST_, VP_, SG_, ST_SLOTS, ST_DIGESTS, ST_TARGET
+//   DM_  ragged messages      43..45        msgs_host_call (the staged piece of the message array and its rebased offsets), ecdsa_verify_msgs_ /
+//                                           decdsa_sign_msgs_dev_locked (DM_BAD), which outlive the core they call   ST_, VP_, SG_, ST_DIGESTS
 //
 // smul_dev_locked itself takes no slot (ctx->tbl, ctx->tbl_fast); host_pipeline stages in ctx->hbuf.
 // ------------------------------------------------------------------------------------------
@@ -115,9 +118,10 @@ enum StageSlot {
 	ST_TARGET = 29,
 	ES_A = 30, ES_RHASH = 31, ES_AWIDE = 32, ES_HRAM = 33, ES_R = 34, ES_S = 35, ES_BAD = 36, ES_STR = 37, ES_STA = 38, ES_AENC = 39, ES_PH = 40,
 	SM_BAD = 41, SM_Z = 42,   // the items a message-level ECGDSA / ECRDSA / SM2 call rejects itself; SM2's Z
+	DM_MSGS = 43, DM_OFFS = 44, DM_BAD = 45,   // the items whose offsets are unusable
 	ECAMD_NSTAGE
 };
-static_assert(ECAMD_NSTAGE == SM_Z + 1, "ECAMD_NSTAGE counts the slots: the last frame ends the array");
+static_assert(ECAMD_NSTAGE == DM_BAD + 1, "ECAMD_NSTAGE counts the slots: the last frame ends the array");
 
 struct ecamd_ctx {
 	int device;

@@ -1987,3 +1987,373 @@ extern "C" int ec_decdsa_sign_ht_batch(ecamd_ctx *ctx, const ecamd_curve *cv, in
 		return decdsa_ht_sign_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], in_stride, in_is_digest, op[2], op[3], s);
 	});
 }
+
+
+// ------------------------------------------------------------------------------------------
+// The ragged message array (include/libecc_amd.h: ec_digest_msgs_batch, ec_ecdsa_verify_msgs_batch, ec_decdsa_sign_msgs_batch;
+// ecamd_digest_msgs.hip).  k_digest_msgs<ID> validates every item against the array's length itself, so the _dev forms only enqueue:
+//   ecamd_launch_digest_msgs    the digests, and 0 / 1 per item
+// and the two protocol calls put that launch in front of the cores that exist, per chunk of at most max_chunk items:
+//   ec_ecdsa_verify_msgs_*      digests into ST_DIGESTS, status into DM_BAD; ecdsa_verify_dev_locked; k_reject_where: DM_BAD's items are result 1
+//   ec_decdsa_sign_msgs_*       the same two; decdsa_ht_sign_dev_locked on the digests; k_sig_msg_reject_sign: status 1 with zero bytes
+// The host forms (msgs_host_call) stage PIECES of the array: a run of items whose messages span at most MSGS_CHUNK_BYTES octets and
+// that has at most max_chunk items, with offsets rebased to the piece.  The per-item arrays go through ctx->hbuf[0], the piece and its
+// offsets through DM_MSGS / DM_OFFS; ecamd_ctx_wipe_scratch covers both.  One piece at a time: copy in, core, copy out, synchronise.
+// ------------------------------------------------------------------------------------------
+static const uint64_t MSGS_CHUNK_BYTES = 1ull << 28;   // octets of the message array staged per piece (a longer single message: a piece of its own)
+
+// $ECAMD_MSGS_CHUNK_BYTES: a smaller cap (tests, measurements), read per call like $ECAMD_HOST_SCHEDULE
+static uint64_t msgs_chunk_bytes()
+{
+	if (const char *e = getenv("ECAMD_MSGS_CHUNK_BYTES")) {
+		const uint64_t v = strtoull(e, nullptr, 10);
+		if (v >= 1 && v < MSGS_CHUNK_BYTES) {
+			return v;
+		}
+	}
+	return MSGS_CHUNK_BYTES;
+}
+
+static int msgs_hash_ok(const char *fn, int hash_type)
+{
+	if (ecamd_digest_len_any(hash_type) == 0 || !ecamd_hmac_served(hash_type)) {
+		return fail(std::string(fn) + ": " + HT_SET);
+	}
+	return 0;
+}
+
+// the launch: items [off, off + m) of an array of msgs_len octets
+static int digest_msgs_launch(int hash_type, EcamdDigestMsgsArgs A, uint32_t off, uint32_t m, uint8_t *d_digests, uint8_t *d_status, hipStream_t s)
+{
+	A.offsets += off;
+	if (A.item_prefix_len) {
+		A.item_prefixes += (size_t)off * A.item_prefix_stride;
+	}
+	A.n = m;
+	A.digests = d_digests;
+	A.status = d_status;
+	HIPCHK(ecamd_launch_digest_msgs(hash_type, A, s));
+	return 0;
+}
+
+static EcamdDigestMsgsArgs digest_msgs_args(const void *d_msgs, uint64_t msgs_len, const void *d_offsets, const uint8_t *call_prefix, uint32_t cpl,
+					    const void *d_item_prefixes, uint32_t ipl, uint32_t ips)
+{
+	EcamdDigestMsgsArgs A;
+	memset(&A, 0, sizeof(A));
+	A.msgs = (const uint32_t *)d_msgs;
+	A.msgs_len = msgs_len;
+	A.offsets = (const uint64_t *)d_offsets;
+	A.item_prefixes = ipl ? (const uint8_t *)d_item_prefixes : nullptr;
+	A.item_prefix_len = ipl;
+	A.item_prefix_stride = ipl ? ips : 0;
+	A.call_prefix_len = cpl;
+	if (cpl) {
+		memcpy(A.call_prefix, call_prefix, cpl);
+	}
+	return A;
+}
+
+static int msgs_prefix_ok(const char *fn, uint32_t n, const uint8_t *call_prefix, uint32_t cpl, const void *item_prefixes, uint32_t ipl, uint32_t ips)
+{
+	if (cpl > 256 || ipl > 256) {
+		return fail(std::string(fn) + ": call_prefix_len and item_prefix_len must be at most 256");
+	}
+	if ((cpl && !call_prefix) || (n && ipl && !item_prefixes)) {
+		return fail(std::string(fn) + ": a prefix is NULL with a positive length");
+	}
+	if (ipl && ips < ipl) {
+		return fail(std::string(fn) + ": item_prefix_stride must be at least item_prefix_len");
+	}
+	return 0;
+}
+
+static int msgs_dev_ptr_ok(const char *fn, const void *d_msgs, uint64_t msgs_len, const void *d_offsets)
+{
+	if (((uintptr_t)d_msgs & 3u) || ((uintptr_t)d_offsets & 7u)) {
+		return fail(std::string(fn) + ": d_msgs must be 4-byte aligned and d_offsets 8-byte aligned");
+	}
+	if (msgs_len && !d_msgs) {
+		return fail(std::string(fn) + ": d_msgs is NULL with a positive msgs_len");
+	}
+	return 0;
+}
+
+// a per-item array of a host form: `stride` octets from item to item, `len` octets used per item (the last item's stride is not read)
+struct MsgsArr {
+	const uint8_t *in;
+	uint8_t *out;
+	size_t stride, len;
+};
+using MsgsCore = std::function<int(uint32_t m, const uint8_t *d_msgs, uint64_t msgs_len, const uint64_t *d_offsets, const DevIn &ip, const DevOut &op, hipStream_t s)>;
+
+static int msgs_host_call(const char *fn, ecamd_ctx *ctx, uint32_t n, const uint8_t *msgs, const uint64_t *offsets, const std::vector<MsgsArr> &arrs,
+			  const MsgsCore &core)
+{
+	const size_t na = arrs.size();
+	if (na > 6) {
+		return fail("internal: too many host arrays");
+	}
+	const uint64_t total = offsets[n], cap = msgs_chunk_bytes();
+	if (total && !msgs) {
+		return fail(std::string(fn) + ": msgs is NULL with a positive offsets[n]");
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	HIPCHK(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->stream;
+	StreamScope scope(ctx, s);
+	std::vector<uint64_t> reb;
+	for (uint32_t off = 0; off < n;) {
+		// the piece: items are added while the span [lo, hi) of the usable ones (off0 <= off1 <= offsets[n]) stays within the cap
+		uint64_t lo = 0, hi = 0;
+		bool any = false;
+		uint32_t m = 0;
+		while (off + m < n && m < ctx->max_chunk) {
+			const uint64_t a = offsets[off + m], b = offsets[off + m + 1];
+			if (a <= b && b <= total) {
+				const uint64_t nlo = any && lo < a ? lo : a, nhi = any && hi > b ? hi : b;
+				if (m > 0 && nhi - nlo > cap) {
+					break;
+				}
+				lo = nlo;
+				hi = nhi;
+				any = true;
+			}
+			m++;
+		}
+		// offsets rebased to the piece; a value outside it belongs to unusable items only and stays unusable
+		const uint64_t len = hi - lo;
+		reb.resize((size_t)m + 1);
+		for (uint32_t j = 0; j <= m; j++) {
+			const uint64_t v = offsets[off + j];
+			reb[j] = (any && v >= lo && v <= hi) ? v - lo : ~0ull;
+		}
+		if (stage_need(ctx, {{DM_MSGS, (size_t)((len + 3) & ~3ull)}, {DM_OFFS, ((size_t)m + 1) * 8}})) {
+			return -1;
+		}
+		for (size_t k = 0; k < na; k++) {
+			if (ensure(&ctx->hbuf[0][k], &ctx->hbuf_bytes[0][k], (size_t)m * arrs[k].stride)) {
+				return -1;
+			}
+		}
+		if (len) {
+			HIPCHK(hipMemcpyAsync(ctx->stage[DM_MSGS], msgs + lo, (size_t)len, hipMemcpyHostToDevice, s));
+		}
+		HIPCHK(hipMemcpyAsync(ctx->stage[DM_OFFS], reb.data(), ((size_t)m + 1) * 8, hipMemcpyHostToDevice, s));
+		DevIn ip(na, nullptr);
+		DevOut op(na, nullptr);
+		for (size_t k = 0; k < na; k++) {
+			const size_t bytes = (size_t)(m - 1) * arrs[k].stride + arrs[k].len;
+			if (arrs[k].in && arrs[k].len) {
+				HIPCHK(hipMemcpyAsync(ctx->hbuf[0][k], arrs[k].in + (size_t)off * arrs[k].stride, bytes, hipMemcpyHostToDevice, s));
+				ip[k] = ctx->hbuf[0][k];
+			}
+			op[k] = arrs[k].out ? ctx->hbuf[0][k] : nullptr;
+		}
+		if (core(m, ctx->stage[DM_MSGS], len, (const uint64_t *)ctx->stage[DM_OFFS], ip, op, s)) {
+			(void)hipStreamSynchronize(s);
+			return -1;
+		}
+		for (size_t k = 0; k < na; k++) {
+			if (arrs[k].out) {
+				HIPCHK(hipMemcpyAsync(arrs[k].out + (size_t)off * arrs[k].stride, ctx->hbuf[0][k], (size_t)m * arrs[k].stride, hipMemcpyDeviceToHost, s));
+			}
+		}
+		HIPCHK(hipStreamSynchronize(s));
+		off += m;
+	}
+	return 0;
+}
+
+extern "C" int ec_digest_msgs_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const void *d_msgs, uint64_t msgs_len, const void *d_offsets,
+					const uint8_t *call_prefix, uint32_t call_prefix_len, const void *d_item_prefixes, uint32_t item_prefix_len,
+					uint32_t item_prefix_stride, void *d_digests, void *d_status, void *hip_stream)
+{
+	const char *fn = "ec_digest_msgs_batch_dev";
+	if (msgs_hash_ok(fn, hash_type) || msgs_prefix_ok(fn, n, call_prefix, call_prefix_len, d_item_prefixes, item_prefix_len, item_prefix_stride)) {
+		return -1;
+	}
+	if (!ctx || (n && (!d_offsets || !d_digests))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (msgs_dev_ptr_ok(fn, d_msgs, msgs_len, d_offsets)) {
+		return -1;
+	}
+	const EcamdDigestMsgsArgs A = digest_msgs_args(d_msgs, msgs_len, d_offsets, call_prefix, call_prefix_len, d_item_prefixes, item_prefix_len, item_prefix_stride);
+	const size_t dl = (size_t)ecamd_digest_len_any(hash_type);
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+			return digest_msgs_launch(hash_type, A, off, m, (uint8_t *)d_digests + off * dl, d_status ? (uint8_t *)d_status + off : nullptr, s);
+		});
+	});
+}
+
+extern "C" int ec_digest_msgs_batch(ecamd_ctx *ctx, int hash_type, uint32_t n, const uint8_t *msgs, const uint64_t *offsets, const uint8_t *call_prefix,
+				    uint32_t call_prefix_len, const uint8_t *item_prefixes, uint32_t item_prefix_len, uint32_t item_prefix_stride,
+				    uint8_t *digests, uint8_t *status)
+{
+	const char *fn = "ec_digest_msgs_batch";
+	if (msgs_hash_ok(fn, hash_type) || msgs_prefix_ok(fn, n, call_prefix, call_prefix_len, item_prefixes, item_prefix_len, item_prefix_stride)) {
+		return -1;
+	}
+	if (!ctx || (n && (!offsets || !digests))) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t dl = (size_t)ecamd_digest_len_any(hash_type);
+	const std::vector<MsgsArr> arrs = {{item_prefix_len ? item_prefixes : nullptr, nullptr, item_prefix_len ? item_prefix_stride : 0, item_prefix_len},
+					   {nullptr, digests, dl, dl}, {nullptr, status, 1, 1}};
+	return msgs_host_call(fn, ctx, n, msgs, offsets, arrs,
+			      [&](uint32_t m, const uint8_t *d_msgs, uint64_t len, const uint64_t *d_offs, const DevIn &ip, const DevOut &op, hipStream_t s) {
+		const EcamdDigestMsgsArgs A = digest_msgs_args(d_msgs, len, d_offs, call_prefix, call_prefix_len, ip[0], item_prefix_len, item_prefix_stride);
+		return digest_msgs_launch(hash_type, A, 0, m, op[1], op[2], s);
+	});
+}
+
+// ---- ECDSA verification and deterministic ECDSA signing from the ragged array ----
+static int msgs_curve_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type)
+{
+	if (msgs_hash_ok(fn, hash_type)) {
+		return -1;
+	}
+	if (!ctx || !cv || cv->ctx != ctx) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (cv->qslot < 0) {
+		return fail(std::string(fn) + ": generator order not supported for this curve");
+	}
+	return 0;
+}
+
+static int ecdsa_verify_msgs_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_pub, const uint8_t *d_sig,
+					const uint8_t *d_msgs, uint64_t msgs_len, const uint64_t *d_offsets, uint8_t *d_res, hipStream_t s)
+{
+	const size_t plen = (size_t)2 * cv->clen, sl = (size_t)2 * cv->qlen;
+	const uint32_t hl = (uint32_t)ecamd_digest_len_any(hash_type), chunk = chunk_items(ctx, n);
+	if (stage_need(ctx, {{ST_DIGESTS, (size_t)chunk * hl}, {DM_BAD, chunk}})) {
+		return -1;
+	}
+	const EcamdDigestMsgsArgs A = digest_msgs_args(d_msgs, msgs_len, d_offsets, nullptr, 0, nullptr, 0, 0);
+	uint8_t **S = ctx->stage;
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		if (digest_msgs_launch(hash_type, A, off, m, S[ST_DIGESTS], S[DM_BAD], s) ||
+		    ecdsa_verify_dev_locked(ctx, cv, m, d_pub + off * plen, d_sig + off * sl, S[ST_DIGESTS], hl, d_res + off, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_reject_where(d_res + off, S[DM_BAD], m, s));
+		return 0;
+	});
+}
+
+extern "C" int ec_ecdsa_verify_msgs_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_pubkeys_aff,
+					      const void *d_sigs, const void *d_msgs, uint64_t msgs_len, const void *d_offsets, void *d_result,
+					      void *hip_stream)
+{
+	const char *fn = "ec_ecdsa_verify_msgs_batch_dev";
+	if (msgs_curve_ok(fn, ctx, cv, hash_type)) {
+		return -1;
+	}
+	if (n && (!d_pubkeys_aff || !d_sigs || !d_offsets || !d_result)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (msgs_dev_ptr_ok(fn, d_msgs, msgs_len, d_offsets)) {
+		return -1;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return ecdsa_verify_msgs_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_pubkeys_aff, (const uint8_t *)d_sigs, (const uint8_t *)d_msgs, msgs_len,
+						    (const uint64_t *)d_offsets, (uint8_t *)d_result, s);
+	});
+}
+
+extern "C" int ec_ecdsa_verify_msgs_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *pubkeys_aff, const uint8_t *sigs,
+					  const uint8_t *msgs, const uint64_t *offsets, uint8_t *result)
+{
+	const char *fn = "ec_ecdsa_verify_msgs_batch";
+	if (msgs_curve_ok(fn, ctx, cv, hash_type)) {
+		return -1;
+	}
+	if (n && (!pubkeys_aff || !sigs || !offsets || !result)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t plen = (size_t)2 * cv->clen, sl = (size_t)2 * cv->qlen;
+	const std::vector<MsgsArr> arrs = {{pubkeys_aff, nullptr, plen, plen}, {sigs, nullptr, sl, sl}, {nullptr, result, 1, 1}};
+	return msgs_host_call(fn, ctx, n, msgs, offsets, arrs,
+			      [&](uint32_t m, const uint8_t *d_msgs, uint64_t len, const uint64_t *d_offs, const DevIn &ip, const DevOut &op, hipStream_t s) {
+		return ecdsa_verify_msgs_dev_locked(ctx, cv, hash_type, m, ip[0], ip[1], d_msgs, len, d_offs, op[2], s);
+	});
+}
+
+static int decdsa_sign_msgs_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *d_privs, const uint8_t *d_msgs,
+				       uint64_t msgs_len, const uint64_t *d_offsets, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s)
+{
+	const size_t ql = (size_t)cv->qlen, sl = 2 * ql;
+	const uint32_t hl = (uint32_t)ecamd_digest_len_any(hash_type), chunk = chunk_items(ctx, n);
+	if (stage_need(ctx, {{ST_DIGESTS, (size_t)chunk * hl}, {DM_BAD, chunk}})) {
+		return -1;
+	}
+	const EcamdDigestMsgsArgs A = digest_msgs_args(d_msgs, msgs_len, d_offsets, nullptr, 0, nullptr, 0, 0);
+	uint8_t **S = ctx->stage;
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		// (an unusable item's digest is zero: it is signed like any other and then replaced)
+		if (digest_msgs_launch(hash_type, A, off, m, S[ST_DIGESTS], S[DM_BAD], s) ||
+		    decdsa_ht_sign_dev_locked(ctx, cv, hash_type, m, d_privs + off * ql, S[ST_DIGESTS], hl, 1, d_sigs + off * sl, d_status + off, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_sig_msg_reject_sign(d_sigs + off * sl, (uint32_t)sl, d_status + off, S[DM_BAD], m, s));
+		return 0;
+	});
+}
+
+extern "C" int ec_decdsa_sign_msgs_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const void *d_privs, const void *d_msgs,
+					     uint64_t msgs_len, const void *d_offsets, void *d_sigs, void *d_status, void *hip_stream)
+{
+	const char *fn = "ec_decdsa_sign_msgs_batch_dev";
+	if (rfc6979_ht_args_ok(fn, ctx, cv, hash_type)) {
+		return -1;
+	}
+	if (n && (!d_privs || !d_offsets || !d_sigs || !d_status)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (msgs_dev_ptr_ok(fn, d_msgs, msgs_len, d_offsets)) {
+		return -1;
+	}
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return decdsa_sign_msgs_dev_locked(ctx, cv, hash_type, n, (const uint8_t *)d_privs, (const uint8_t *)d_msgs, msgs_len, (const uint64_t *)d_offsets,
+						   (uint8_t *)d_sigs, (uint8_t *)d_status, s);
+	});
+}
+
+extern "C" int ec_decdsa_sign_msgs_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int hash_type, uint32_t n, const uint8_t *privs, const uint8_t *msgs,
+					 const uint64_t *offsets, uint8_t *sigs, uint8_t *status)
+{
+	const char *fn = "ec_decdsa_sign_msgs_batch";
+	if (rfc6979_ht_args_ok(fn, ctx, cv, hash_type)) {
+		return -1;
+	}
+	if (n && (!privs || !offsets || !sigs || !status)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t ql = (size_t)cv->qlen;
+	const std::vector<MsgsArr> arrs = {{privs, nullptr, ql, ql}, {nullptr, sigs, 2 * ql, 2 * ql}, {nullptr, status, 1, 1}};
+	return msgs_host_call(fn, ctx, n, msgs, offsets, arrs,
+			      [&](uint32_t m, const uint8_t *d_msgs, uint64_t len, const uint64_t *d_offs, const DevIn &ip, const DevOut &op, hipStream_t s) {
+		return decdsa_sign_msgs_dev_locked(ctx, cv, hash_type, m, ip[0], d_msgs, len, d_offs, op[1], op[2], s);
+	});
+}

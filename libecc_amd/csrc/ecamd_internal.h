@@ -842,6 +842,22 @@ hipError_t ecamd_launch_hash_slots(int hash_type, const uint8_t *slots, uint32_t
 // 16 and anything outside 1 .. 20.  Here EVERY number gives an all-zero digest for a slot whose length does not fit its stride.
 int ecamd_digest_len_any(int hash_type);
 hipError_t ecamd_launch_digest_slots(int hash_type, const uint8_t *slots, uint32_t stride, uint32_t n, uint8_t *out, uint32_t out_stride, hipStream_t s);
+// the same hashes over a packed, ragged message array (ecamd_digest_msgs.h / ecamd_digest_msgs.hip: k_digest_msgs<ID>): item i hashes
+// call_prefix || item_prefixes[i] || msgs[offsets[i] .. offsets[i + 1]).  An item whose offsets decrease, end behind msgs_len or
+// make an input above 2^28 octets gets an all-zero digest and status 1, and nothing of msgs is read for it.
+struct EcamdDigestMsgsArgs {
+	const uint32_t *msgs;          // 4-byte aligned, readable up to round_up(msgs_len, 4)
+	uint64_t msgs_len;
+	const uint64_t *offsets;       // n + 1
+	const uint8_t *item_prefixes;  // item i at i * item_prefix_stride (not read when item_prefix_len = 0)
+	uint32_t item_prefix_len, item_prefix_stride;   // <= 256
+	uint32_t call_prefix_len;      // <= 256
+	uint32_t n;
+	uint8_t *digests;              // n x the digest length
+	uint8_t *status;               // n: 0 / 1, or NULL
+	uint32_t call_prefix[64];      // zero behind its last octet
+};
+hipError_t ecamd_launch_digest_msgs(int hash_type, const EcamdDigestMsgsArgs &a, hipStream_t s);
 // SM2's Z per item from the call's prefix (ecamd_sm2z.h) and the keys' 2 clen octets, hsize octets each into z
 namespace ecsm2z { struct Prefix; }
 hipError_t ecamd_launch_sm2_z(const ecsm2z::Prefix &P, const uint8_t *keys, uint32_t klen, uint8_t *z, uint32_t hsize, uint32_t n, hipStream_t s);

@@ -7,7 +7,7 @@ bytes per step); not the driver's headline bench.  --workload ecdsa_recover is t
 verification of the same signatures in alternating windows (recover_row).  sig_hashed_verify / sig_hashed_sign / schnorr_verify /
 schnorr_sign / bip0340_sign with --hash 5 .. 11, 13 .. 15, 17 .. 20 or --hashes LIST|new go through the _ht entry points (commit_ht_rows).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|sig_msg_verify|sig_msg_sign|hash_slots [--alg sm2|ecrdsa|ecgdsa --hash 11|13|14|2 --curve C]|digest_slots|hmac_slots [--hash 1..11|13..15|17..20]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..11|13..15|17..20 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|sig_msg_verify|sig_msg_sign|hash_slots [--alg sm2|ecrdsa|ecgdsa --hash 11|13|14|2 --curve C]|digest_msgs [--hash N --lens 32|1024|mixed]|digest_slots|hmac_slots [--hash 1..11|13..15|17..20]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..11|13..15|17..20 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -250,6 +250,82 @@ def digest_slots_row(a, ctx, dev, stream, rng, B):
                       "sha256_same_run": {"value": 1e9 * mb / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[1]]},
                       "gate": gate,
                       "config": {"workload": a.workload, "hash": ht, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
+    ctx.close()
+
+
+def digest_msgs_lens(kind, B):
+    """the message lengths of --workload digest_msgs.  "32" and "1024": every message that long.  "mixed": a fixed distribution from
+    numpy's default_rng(20): 97 % of the messages uniform in 16 .. 256 octets, 2.9 % uniform in 257 .. 2048, 0.1 % uniform in 2049 .. 4092,
+    and item 0 exactly 4092 octets, the longest a slot holds -- so the slot path runs at stride 4096 whatever the draw."""
+    if kind != "mixed":
+        return np.full(B, int(kind), dtype=np.int64)
+    r = np.random.default_rng(20)
+    u = r.random(B)
+    lens = np.where(u < 0.97, r.integers(16, 257, size=B), np.where(u < 0.999, r.integers(257, 2049, size=B), r.integers(2049, 4093, size=B)))
+    lens[0] = 4092
+    return lens.astype(np.int64)
+
+
+def digest_msgs_row(a, ctx, dev, stream, rng, B):
+    """--workload digest_msgs: ec_digest_msgs_batch_dev (--hash 1 .. 11, 13 .. 15, 17 .. 20; --lens 32 | 1024 | mixed, digest_msgs_lens) over
+    a packed array beside ec_digest_slots_batch_dev on the SAME content at the stride the longest message forces, in alternating windows
+    of a.steps calls, inputs resident in HBM: ns per item, GB/s of message octets, and the octets each format uploads.  Gate: the two
+    paths give the same digests for the whole batch, and the first 64 equal hashlib's where hashlib offers the hash.  One GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload digest_msgs measures one GPU: run it with --gpus 1, outside torch.distributed.run")
+    ht = a.hash
+    hl = libecc_amd.api.DIGEST_SIZES.get(ht)
+    if hl is None:
+        raise SystemExit("--workload digest_msgs: --hash 1 .. 11, 13 .. 15 or 17 .. 20")
+    lens = digest_msgs_lens(a.lens, B)
+    offs = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(lens, out=offs[1:])
+    total = int(offs[B])
+    stride = (4 + int(lens.max()) + 3) & ~3
+    content = rng.integers(0, 256, size=(total + 3) & ~3, dtype=np.uint8)
+    d_msgs = torch.from_numpy(content).to(dev)
+    d_offs = torch.from_numpy(offs).to(dev)
+    # the slots of the same content, laid out on the device: a u32 length, then the message
+    d_lens = torch.from_numpy(lens).to(dev)
+    d_sl = torch.zeros(B * stride, dtype=torch.uint8, device=dev)
+    d_sl.view(B, stride)[:, :4] = torch.stack([(d_lens >> (8 * k)) & 255 for k in range(4)], dim=1).to(torch.uint8)
+    item = torch.repeat_interleave(torch.arange(B, device=dev), d_lens)
+    d_sl[item * stride + 4 + (torch.arange(total, device=dev) - d_offs[item])] = d_msgs[:total]
+    del item
+    d_a, d_b, d_st = torch.empty(hl * B, dtype=torch.uint8, device=dev), torch.empty(hl * B, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    fns = [lambda: ctx.digest_msgs_dev(ht, B, d_msgs.data_ptr(), total, d_offs.data_ptr(), d_a.data_ptr(), d_st.data_ptr(), stream=stream.cuda_stream),
+           lambda: ctx.digest_slots_dev(ht, B, d_sl.data_ptr(), stride, d_b.data_ptr(), stream.cuda_stream)]
+    torch.cuda.synchronize()
+    for _ in range(max(1, a.warmup)):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    if not torch.equal(d_a, d_b) or int(d_st.max()) != 0:
+        raise SystemExit("PARITY FAILURE: ec_digest_msgs_batch_dev and ec_digest_slots_batch_dev differ on the same content")
+    gate = "both paths give the same %d digests" % B
+    names = {1: "sha224", 2: "sha256", 3: "sha384", 4: "sha512", 5: "sha3_224", 6: "sha3_256", 7: "sha3_384", 8: "sha3_512", 9: "sha512_224",
+             10: "sha512_256", 11: "sm3", 15: "ripemd160"}
+    if names.get(ht) in hashlib.algorithms_available:
+        got = bytes(d_a[:64 * hl].cpu().numpy())
+        if got != b"".join(hashlib.new(names[ht], content[offs[i]:offs[i + 1]].tobytes()).digest() for i in range(64)):
+            raise SystemExit("PARITY FAILURE: the device's digests differ from hashlib's")
+        gate += "; the first 64 equal hashlib's"
+    acc = [[], []]
+    for _ in range(3):
+        for fn, ac in zip(fns, acc):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            ac.append((time.perf_counter() - t0) / a.steps)
+    ma, mb = float(np.median(acc[0])), float(np.median(acc[1]))
+    print(json.dumps({"metric": "hash_type %d of 2^%d messages (--lens %s) from the packed array, ns per item (device-resident)" % (ht, a.batch_log2, a.lens),
+                      "value": 1e9 * ma / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[0]], "gb_per_s_of_message_octets": total / ma / 1e9,
+                      "octets_uploaded": total + 8 * (B + 1),
+                      "digest_slots_same_run": {"value": 1e9 * mb / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[1]], "stride": stride,
+                                                "gb_per_s_of_message_octets": total / mb / 1e9, "octets_uploaded": B * stride},
+                      "ratio_msgs_over_slots_time": ma / mb, "message_octets": total, "gate": gate,
+                      "config": {"workload": a.workload, "hash": ht, "lens": a.lens, "steps": a.steps, "warmup": a.warmup, "windows": 3}}))
     ctx.close()
 
 
@@ -1290,7 +1366,7 @@ def commit_ht_rows(a, ctx, dev, stream, rng, B, hashes):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_msg_verify", "sig_msg_sign", "hash_slots", "digest_slots", "hmac_slots", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_msg_verify", "sig_msg_sign", "hash_slots", "digest_slots", "digest_msgs", "hmac_slots", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
     ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa",
                                                     "ed25519", "ed25519ctx", "ed25519ph", "ed448", "ed448ph"],
                     help="eddsa_sign: ed25519, ed25519ctx, ed25519ph, ed448, ed448ph; sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
@@ -1299,6 +1375,7 @@ def main():
                          "decdsa_sign: SHA-256 by default, 1 .. 4 through ec_decdsa_sign_batch, the rest through ec_decdsa_sign_ht_batch; digest_slots, hmac_slots: any of libecc's numbers but 0 and 16 (default 6, SHA3-256)")
     ap.add_argument("--hashes", default=None, help="sig_hashed_verify / sig_hashed_sign / schnorr_verify / schnorr_sign / bip0340_sign: a comma-separated list of the "
                     "hash numbers 5 .. 11, 13 .. 15, 17 .. 20, or 'new' for all fourteen, measured in one run through the _ht names (--hash N: one of them)")
+    ap.add_argument("--lens", default="32", choices=["32", "1024", "mixed"], help="digest_msgs: the message lengths (digest_msgs_lens documents `mixed`)")
     ap.add_argument("--secret", action="store_true", help="dbign_sign / bip0340_sign: the context in secret-scalar mode")
     ap.add_argument("--derive-pub", action="store_true", help="eddsa_sign: pubkeys = NULL, A = encode([a]B) derived on the device (a second comb multiplication per item)")
     ap.add_argument("--gpus", type=int, default=1)
@@ -1323,7 +1400,7 @@ def main():
             raise SystemExit("--workload %s: --hash / --hashes 5 .. 11, 13 .. 15 or 17 .. 20 (1 .. 4 are the workload without --hash)" % a.workload)
     if a.hash is None and a.workload in ("sig_msg_verify", "sig_msg_sign", "hash_slots"):
         a.hash = {"sm2": 11, "ecrdsa": 13, "ecgdsa": 2}.get(a.alg, 11)   # the hash each scheme is deployed with
-    if a.hash is None and a.workload in ("digest_slots", "hmac_slots"):
+    if a.hash is None and a.workload in ("digest_slots", "digest_msgs", "hmac_slots"):
         a.hash = 6
     if a.hash is None:
         a.hash = 2 if a.workload == "decdsa_sign" else 16
@@ -1372,6 +1449,8 @@ def main():
         return sig_msg_row(a, ctx, dev, stream, rng, B)
     if a.workload == "digest_slots":
         return digest_slots_row(a, ctx, dev, stream, rng, B)
+    if a.workload == "digest_msgs":
+        return digest_msgs_row(a, ctx, dev, stream, rng, B)
     if a.workload == "hmac_slots":
         return hmac_slots_row(a, ctx, dev, stream, rng, B)
     if commit_hashes is not None:
