@@ -397,7 +397,8 @@ int ec_digest_slots_batch_dev(ecamd_ctx *ctx, int hash_type, uint32_t n, const v
  *   ECKCDSA   item_prefix = z (the key's certificate data, BLOCK octets of the hash), then ec_sig_hashed_verify_ht_batch_dev /
  *             ec_sig_hashed_sign_ht_batch_dev with the digests as their input
  *   SM2       item_prefix = Z, then ec_sig_verify_batch_dev / ec_sig_sign_batch_dev
- *   Ed25519   call_prefix = dom2 (empty for pure Ed25519), item_prefix = R || A, hash_type 4, then ec_eddsa_verify_batch
+ * EdDSA needs no composition: ec_eddsa_verify_msgs_batch, ec_eddsa_verify_msgs_all_batch and ec_eddsa_sign_msgs_batch (below) take this
+ * format for all five variants, Ed448's SHAKE256 and the pre-hashed variants included.
  * Out of scope: the slot formats of ECSDSA, ECOSDSA, ECFSDSA and BIP0340 (their message sits behind a point that exists only inside
  * the call), SHAKE256 and belt-hash, HMAC over this format, the ecamd_multi_* wrappers and the libecc-typed layer.
  */
@@ -886,6 +887,50 @@ int ec_eddsa_sign_msg_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, u
 			    uint32_t msg_stride, uint8_t *sigs, uint8_t *pub_out, uint8_t *status);
 int ec_eddsa_pub_key_batch(ecamd_ctx *ctx, const ecamd_curve *curve, uint32_t n, const uint8_t *secret_keys, uint8_t *pub_out,
 			   uint8_t *status);
+
+/* EdDSA from keys, signatures, a context and messages of ANY length, all five variants, through one call: what eddsa_import_pub_key +
+ * ec_verify and _ec_sign take.  The messages lie in ec_digest_msgs_batch's packed array -- msgs, offsets (n + 1 uint64_t), msgs_len,
+ * alignment, pieces of the host forms ($ECAMD_MSGS_CHUNK_BYTES) and n = 0 exactly as documented there -- and every hash runs on the
+ * device, streamed over its segments: nothing is assembled, on the host or in device memory.
+ *   alg, adata, adata_len   as for ec_eddsa_sign_msg_batch: alg 9, 10, 11 on the WEI25519 handle, 12, 13 on the WEI448 handle, anything
+ *                else a call-level error (-1); ONE context per call, host memory in both forms, with the same call-level errors.
+ *   ec_eddsa_verify_msgs_batch      pubkeys n x klen, sigs n x 2 klen (klen 32 / 57).  Per item
+ *                hram = H(dom || R_i || A_i || M_i), or H(dom || R_i || A_i || PH(M_i)) for alg 11 and 13 (PH(M_i) never leaves the
+ *                registers), with R_i read from sigs + i * 2 klen and A_i from pubkeys + i * klen where they lie; then
+ *                ec_eddsa_verify_batch_dev's core on the same stream.  result[i] is that core's verdict; an unusable item is result 1.
+ *                A is hashed AS GIVEN: exact for Ed25519; for Ed448 exact whenever the key lies in the prime-order subgroup (libecc
+ *                stores [4^-1 mod q]A and hashes the key RE-ENCODED from it, which differs from the given octets when A has a torsion
+ *                component -- the note at ec_eddsa_verify_batch).
+ *   ec_eddsa_verify_msgs_all_batch  the same inputs, ec_verify_batch's one bit: the same hram launch in front of
+ *                ec_eddsa_verify_all_batch[_dev], whose rules (n = 0 is an error, which batches go through the combination) hold.
+ *                Host form: *all_valid, and first_rejected (may be NULL) as there.  _dev form: d_all_valid[0] = 1 when the combination
+ *                accepts and no item is unusable, else 0 ("not decided here / rejected"); it needs a handle the combination serves.  An
+ *                unusable item makes the batch rejected exactly as a bad signature does; in the host form it counts for first_rejected.
+ *   ec_eddsa_sign_msgs_batch        ec_eddsa_sign_msg_batch with msgs / offsets in place of slots: secret_keys, pubkeys (or NULL: derived),
+ *                sigs, pub_out (or NULL), status, the key expansion, [r]B, [a]B, the mod-q finish, the secret scratch and its wiping,
+ *                secret-scalar mode and chunking unchanged.  An unusable item is status 1 with zero signature bytes.
+ * An item is UNUSABLE when offsets[i] > offsets[i + 1], offsets[i + 1] > the array's length, or the longest input hashed for it exceeds
+ * 2^28 octets (dom || R || A || M; the message alone for alg 11 and 13).  Nothing of msgs is read for such an item, and for a usable
+ * one no octet outside [offsets[i], offsets[i + 1]) is read: 8-octet loads inside the message, single octets at its ends.
+ * The _dev forms only enqueue, in pieces of at most ecamd_ctx_set_max_chunk items.  Out of scope: the ecamd_multi_* wrappers, the
+ * libecc-typed layer and projective keys. */
+int ec_eddsa_verify_msgs_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const uint8_t *pubkeys, const uint8_t *sigs,
+			       const uint8_t *adata, uint32_t adata_len, const uint8_t *msgs, const uint64_t *offsets, uint8_t *result);
+int ec_eddsa_verify_msgs_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const void *d_pubkeys, const void *d_sigs,
+				   const uint8_t *adata, uint32_t adata_len, const void *d_msgs, uint64_t msgs_len, const void *d_offsets,
+				   void *d_result, void *hip_stream);
+int ec_eddsa_verify_msgs_all_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const uint8_t *pubkeys, const uint8_t *sigs,
+				   const uint8_t *adata, uint32_t adata_len, const uint8_t *msgs, const uint64_t *offsets, int *all_valid,
+				   uint32_t *first_rejected);
+int ec_eddsa_verify_msgs_all_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const void *d_pubkeys, const void *d_sigs,
+				       const uint8_t *adata, uint32_t adata_len, const void *d_msgs, uint64_t msgs_len, const void *d_offsets,
+				       void *d_all_valid, void *hip_stream);
+int ec_eddsa_sign_msgs_batch(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const uint8_t *secret_keys, const uint8_t *pubkeys,
+			     const uint8_t *adata, uint32_t adata_len, const uint8_t *msgs, const uint64_t *offsets, uint8_t *sigs,
+			     uint8_t *pub_out, uint8_t *status);
+int ec_eddsa_sign_msgs_batch_dev(ecamd_ctx *ctx, const ecamd_curve *curve, int alg, uint32_t n, const void *d_secret_keys, const void *d_pubkeys,
+				 const uint8_t *adata, uint32_t adata_len, const void *d_msgs, uint64_t msgs_len, const void *d_offsets,
+				 void *d_sigs, void *d_pub_out, void *d_status, void *hip_stream);
 
 /* Point wire formats (curves/prj_pt.c:462-624): affine X || Y (2*clen bytes, what the entry points above
  * use) and projective X || Y || Z (3*clen bytes: prj_pt_import_from_buf / prj_pt_export_to_buf, the format

@@ -47,6 +47,8 @@ EXPORTED_SYMBOLS = [
     "ec_bip0340_nonce_ht_batch", "ec_bip0340_nonce_ht_batch_dev", "ec_bip0340_sign_ht_batch", "ec_bip0340_sign_ht_batch_dev",
     "ec_digest_msgs_batch", "ec_digest_msgs_batch_dev", "ec_ecdsa_verify_msgs_batch", "ec_ecdsa_verify_msgs_batch_dev",
     "ec_decdsa_sign_msgs_batch", "ec_decdsa_sign_msgs_batch_dev",
+    "ec_eddsa_verify_msgs_batch", "ec_eddsa_verify_msgs_batch_dev", "ec_eddsa_verify_msgs_all_batch", "ec_eddsa_verify_msgs_all_batch_dev",
+    "ec_eddsa_sign_msgs_batch", "ec_eddsa_sign_msgs_batch_dev",
 ]
 
 # libecc's ec_alg_type numbers of the EdDSA variants ec_eddsa_sign_msg_batch serves (lib_ecc_types.h:49-55)
@@ -214,6 +216,12 @@ def load_library():
                 getattr(L, base + "_ht" + tail).argtypes = getattr(L, base + tail).argtypes
         L.ec_eddsa_sign_msg_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p, u32, u8p, u8p, u8p]
         L.ec_eddsa_sign_msg_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u8p, u32, vp, u32, vp, vp, vp, vp]
+        L.ec_eddsa_verify_msgs_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p, vp, u8p]
+        L.ec_eddsa_verify_msgs_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u8p, u32, vp, u64, vp, vp, vp]
+        L.ec_eddsa_verify_msgs_all_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p, vp, C.POINTER(C.c_int), C.POINTER(C.c_uint32)]
+        L.ec_eddsa_verify_msgs_all_batch_dev.argtypes = L.ec_eddsa_verify_msgs_batch_dev.argtypes
+        L.ec_eddsa_sign_msgs_batch.argtypes = [vp, vp, C.c_int, u32, u8p, u8p, u8p, u32, u8p, vp, u8p, u8p, u8p]
+        L.ec_eddsa_sign_msgs_batch_dev.argtypes = [vp, vp, C.c_int, u32, vp, vp, u8p, u32, vp, u64, vp, vp, vp, vp, vp]
         L.ec_eddsa_pub_key_batch.argtypes = [vp, vp, u32, u8p, u8p, u8p]
         L.ec_eddsa_pub_key_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp]
         L.ec_ecccdh_derive_batch_dev.argtypes = [vp, vp, u32, vp, vp, vp, vp, vp]
@@ -860,6 +868,36 @@ class Curve:
              "ec_eddsa_sign_msg_batch")
         return sigs.raw[:2 * kl * n], (pub.raw[:kl * n] if want_pub else None), st.raw[:n]
 
+    def eddsa_verify_msg_list(self, alg, pubkeys, sigs, msgs, adata=None):
+        """(eddsa_verify_msgs is the older call over host-assembled hash inputs in slots and keeps its name.)  EdDSA verification of
+        a list of `bytes` of any lengths, all five variants, every hash on the device: n result bytes"""
+        n = len(msgs)
+        packed, offs = pack_msgs(msgs)
+        res = C.create_string_buffer(max(1, n))
+        _chk(self.L, self.L.ec_eddsa_verify_msgs_batch(self.ctx.h, self.h, alg, n, pubkeys, sigs, adata, len(adata) if adata is not None else 0,
+                                                       packed, offs, res), "ec_eddsa_verify_msgs_batch")
+        return res.raw[:n]
+
+    def eddsa_verify_msg_list_all(self, alg, pubkeys, sigs, msgs, adata=None):
+        """ec_verify_batch's whole-batch predicate from the same inputs: (all_valid, index of the first rejected item or n)"""
+        n = len(msgs)
+        packed, offs = pack_msgs(msgs)
+        ok, first = C.c_int(0), C.c_uint32(0)
+        _chk(self.L, self.L.ec_eddsa_verify_msgs_all_batch(self.ctx.h, self.h, alg, n, pubkeys, sigs, adata, len(adata) if adata is not None else 0,
+                                                           packed, offs, C.byref(ok), C.byref(first)), "ec_eddsa_verify_msgs_all_batch")
+        return bool(ok.value), first.value
+
+    def eddsa_sign_msg_list(self, alg, secret_keys, pubkeys, msgs, adata=None, want_pub=True):
+        """eddsa_sign_msgs over a list of `bytes` of any lengths: (sigs n x 2 klen, pub_out n x klen or None, status)"""
+        kl = 57 if self.clen == 56 else 32
+        n = len(msgs)
+        packed, offs = pack_msgs(msgs)
+        sigs, st = C.create_string_buffer(max(1, 2 * kl * n)), C.create_string_buffer(max(1, n))
+        pub = C.create_string_buffer(max(1, kl * n)) if want_pub else None
+        _chk(self.L, self.L.ec_eddsa_sign_msgs_batch(self.ctx.h, self.h, alg, n, secret_keys, pubkeys, adata, len(adata) if adata is not None else 0,
+                                                     packed, offs, sigs, pub, st), "ec_eddsa_sign_msgs_batch")
+        return sigs.raw[:2 * kl * n], (pub.raw[:kl * n] if want_pub else None), st.raw[:n]
+
     def eddsa_pub_keys(self, secret_keys):
         """eddsa_import_key_pair_from_priv_key_buf + eddsa_export_pub_key in batch: (n x klen encodings of A, status)"""
         kl = 57 if self.clen == 56 else 32
@@ -1012,6 +1050,21 @@ class Curve:
         _chk(self.L, self.L.ec_eddsa_sign_msg_batch_dev(self.ctx.h, self.h, alg, n, d_secret_keys, d_pubkeys, adata,
                                                          len(adata) if adata is not None else 0, d_slots, stride, d_sigs, d_pub_out, d_status,
                                                          stream), "ec_eddsa_sign_msg_batch_dev")
+
+    def eddsa_verify_msg_list_dev(self, alg, n, d_pubs, d_sigs, adata, d_msgs, msgs_len, d_offsets, d_result, stream=None):
+        """ec_eddsa_verify_msgs_batch with device pointers (adata: host bytes or None)"""
+        _chk(self.L, self.L.ec_eddsa_verify_msgs_batch_dev(self.ctx.h, self.h, alg, n, d_pubs, d_sigs, adata, len(adata) if adata is not None else 0,
+                                                           d_msgs, msgs_len, d_offsets, d_result, stream), "ec_eddsa_verify_msgs_batch_dev")
+
+    def eddsa_verify_msg_list_all_dev(self, alg, n, d_pubs, d_sigs, adata, d_msgs, msgs_len, d_offsets, d_all_valid, stream=None):
+        """ec_eddsa_verify_msgs_all_batch with device pointers: d_all_valid[0] = 1 / 0"""
+        _chk(self.L, self.L.ec_eddsa_verify_msgs_all_batch_dev(self.ctx.h, self.h, alg, n, d_pubs, d_sigs, adata, len(adata) if adata is not None else 0,
+                                                               d_msgs, msgs_len, d_offsets, d_all_valid, stream), "ec_eddsa_verify_msgs_all_batch_dev")
+
+    def eddsa_sign_msg_list_dev(self, alg, n, d_secret_keys, d_pubkeys, adata, d_msgs, msgs_len, d_offsets, d_sigs, d_pub_out, d_status, stream=None):
+        """ec_eddsa_sign_msgs_batch with device pointers (d_pubkeys, d_pub_out: a pointer or None)"""
+        _chk(self.L, self.L.ec_eddsa_sign_msgs_batch_dev(self.ctx.h, self.h, alg, n, d_secret_keys, d_pubkeys, adata, len(adata) if adata is not None else 0,
+                                                         d_msgs, msgs_len, d_offsets, d_sigs, d_pub_out, d_status, stream), "ec_eddsa_sign_msgs_batch_dev")
 
     def eddsa_pub_keys_dev(self, n, d_secret_keys, d_pub_out, d_status, stream=None):
         _chk(self.L, self.L.ec_eddsa_pub_key_batch_dev(self.ctx.h, self.h, n, d_secret_keys, d_pub_out, d_status, stream),

@@ -5620,6 +5620,8 @@ extern "C" int ecamd_debug_schnorr_msm(ecamd_ctx *ctx, const ecamd_curve *cv, ui
 	return schnorr_msm_host_locked(ctx, cv, n, s, ne, keys_aff, r, r_fmt, seed, accept, z_out, sum_out);
 }
 
+static int eddsa_verify_all_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, const void *d_pubkeys, const void *d_sigs, const void *d_hram,
+				       const uint8_t seed[32], void *d_verdict, hipStream_t s);
 static int eddsa_verify_all_batch_dev_impl(ecamd_ctx *ctx, const ecamd_curve *cv_in, uint32_t n, const void *d_pubkeys,
 					     const void *d_sigs, const void *d_hram, uint32_t hram_len, void *d_verdict,
 					     void *hip_stream)
@@ -5643,6 +5645,14 @@ static int eddsa_verify_all_batch_dev_impl(ecamd_ctx *ctx, const ecamd_curve *cv
 	HIPCHK(hipSetDevice(ctx->device));
 	hipStream_t s = hip_stream ? (hipStream_t)hip_stream : ctx->stream;
 	StreamScope scope(ctx, s);
+	return eddsa_verify_all_dev_locked(ctx, cv, n, d_pubkeys, d_sigs, d_hram, seed, d_verdict, s);
+}
+
+// the combination behind the checks of ec_eddsa_verify_all_batch_dev (ctx->mu held, a StreamScope open): d_verdict[0] = 0 / 1
+static int eddsa_verify_all_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n, const void *d_pubkeys, const void *d_sigs, const void *d_hram,
+				       const uint8_t seed[32], void *d_verdict, hipStream_t s)
+{
+	const bool e448 = cv->pbits == 448;
 	HIPCHK(hipMemsetAsync(d_verdict, 0, 1, s));
 	uint32_t pc = 0;
 	for (uint32_t off = 0; off < n; off += ctx->max_chunk, pc++) {
@@ -5933,9 +5943,16 @@ static void eddsa_front_args(EcamdEddsaSignArgs *E, const eced::Dom &dom)
 	memcpy(E->dom, dom.b, sizeof(E->dom));
 }
 
+// the messages of a ragged call (ec_eddsa_*_msgs_*): the packed array and the n + 1 offsets, in place of slots
+struct EdRagged {
+	const uint8_t *d_msgs;
+	uint64_t msgs_len;
+	const uint64_t *d_offsets;
+};
+
 static int eddsa_sign_msg_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, const EcamdEdSignArgs &T, int alg, const eced::Dom &dom, uint32_t n,
 				     const uint8_t *d_sk, const uint8_t *d_pub, const uint8_t *d_slots, uint32_t stride, uint8_t *d_sigs,
-				     uint8_t *d_pub_out, uint8_t *d_status, hipStream_t s)
+				     uint8_t *d_pub_out, uint8_t *d_status, hipStream_t s, const EdRagged *rg = nullptr)
 {
 	const size_t kl = T.is448 ? 57 : 32, hl = 2 * kl;
 	const uint32_t chunk = n < ctx->max_chunk ? n : ctx->max_chunk;
@@ -5960,7 +5977,19 @@ static int eddsa_sign_msg_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, cons
 		E.hram = S[ES_HRAM];
 		E.bad = S[ES_BAD];
 		E.ph = ph ? S[ES_PH] : nullptr;
-		HIPCHK(ecamd_launch_eddsa_expand(alg, E, s));
+		EcamdEddsaMsgsArgs M;
+		if (rg) {   // k_eddsa_expand_r_msgs / k_eddsa_hram_msgs in place of the slot kernels; everything between them is the same
+			E.slots = nullptr;
+			E.stride = 0;
+			M.vsigs = nullptr;
+			M.msgs = rg->d_msgs;
+			M.msgs_len = rg->msgs_len;
+			M.offsets = rg->d_offsets + off;
+			M.e = E;
+			HIPCHK(ecamd_launch_eddsa_expand_msgs(alg, M, s));
+		} else {
+			HIPCHK(ecamd_launch_eddsa_expand(alg, E, s));
+		}
 		const uint8_t *A_enc = derive ? nullptr : d_pub + off * kl;
 		if (derive) {
 			uint8_t *dst = d_pub_out ? d_pub_out + off * kl : S[ES_AENC];
@@ -5977,7 +6006,12 @@ static int eddsa_sign_msg_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, cons
 		E.R = S[ES_R];
 		E.A = A_enc;
 		E.sigs = d_sigs + off * 2 * kl;
-		HIPCHK(ecamd_launch_eddsa_hram(alg, E, s));
+		if (rg) {
+			M.e = E;
+			HIPCHK(ecamd_launch_eddsa_hram_msgs(alg, M, s));
+		} else {
+			HIPCHK(ecamd_launch_eddsa_hram(alg, E, s));
+		}
 		EcamdEdSignArgs G = T;
 		G.n = m;
 		G.r_hash = S[ES_RHASH];
@@ -6022,10 +6056,9 @@ static int eddsa_pub_key_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, const
 	return 0;
 }
 
-// the call-level checks of ec_eddsa_sign_msg_batch[_dev]; fills T and dom
-static int eddsa_msg_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const void *sk, const uint8_t *adata,
-			     uint32_t adata_len, const void *slots, uint32_t stride, const void *sigs, const void *status, EcamdEdSignArgs *T,
-			     eced::Dom *dom)
+// the call-level checks every message-level EdDSA call shares (alg, its handle, the context); fills T and dom
+static int eddsa_alg_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, const uint8_t *adata, uint32_t adata_len,
+			     EcamdEdSignArgs *T, eced::Dom *dom)
 {
 	if (!eced::alg_ok(alg)) {
 		return fail(std::string(fn) + ": alg must be EDDSA25519 (9), EDDSA25519CTX (10), EDDSA25519PH (11), EDDSA448 (12) or EDDSA448PH (13)");
@@ -6047,13 +6080,24 @@ static int eddsa_msg_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *
 			return fail(std::string(fn) + ": adata_len must be at most 255 (sig/eddsa.c:64)");
 		}
 	}
+	eced::dom_build(alg, adata, adata_len, dom);
+	return 0;
+}
+
+// the call-level checks of ec_eddsa_sign_msg_batch[_dev]; fills T and dom
+static int eddsa_msg_args_ok(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const void *sk, const uint8_t *adata,
+			     uint32_t adata_len, const void *slots, uint32_t stride, const void *sigs, const void *status, EcamdEdSignArgs *T,
+			     eced::Dom *dom)
+{
+	if (eddsa_alg_args_ok(fn, ctx, cv, alg, adata, adata_len, T, dom)) {
+		return -1;
+	}
 	if (stride < 4 || (stride & 3u) || stride > 4096) {
 		return fail(std::string(fn) + ": msg_stride must be a multiple of 4 in 4 .. 4096");
 	}
 	if (n && (!sk || !slots || !sigs || !status)) {
 		return fail(std::string(fn) + ": bad argument");
 	}
-	eced::dom_build(alg, adata, adata_len, dom);
 	return 0;
 }
 
@@ -6146,6 +6190,273 @@ extern "C" int ec_eddsa_pub_key_batch(ecamd_ctx *ctx, const ecamd_curve *cv, uin
 	const std::vector<HostArr> arrs = {{secret_keys, nullptr, kl}, {nullptr, pub_out, kl}, {nullptr, status, 1}};
 	return host_pipeline(ctx, cv->pbits, n, arrs, [&](uint32_t m, const DevIn &ip, const DevOut &op, hipStream_t s, const Between &) {
 		return eddsa_pub_key_dev_locked(ctx, cv, T, m, ip[0], op[1], op[2], s);
+	});
+}
+
+// ------------------------------------------------------------------------------------------
+// EdDSA from the ragged message array (include/libecc_amd.h: ec_eddsa_verify_msgs_batch, ec_eddsa_verify_msgs_all_batch,
+// ec_eddsa_sign_msgs_batch; ecamd_eddsa_msgs.hip).  The kernels validate every item against the array's length themselves, so the
+// _dev forms only enqueue, per chunk of at most max_chunk items:
+//   verify      k_eddsa_vhram_msgs: hram into ST_DIGESTS, the unusable items into DM_BAD; eddsa_verify_dev_locked /
+//               eddsa448_verify_dev_locked unchanged; k_reject_where: DM_BAD's items are result 1
+//   verify all  k_eddsa_vhram_msgs over the whole batch: hram into EB_HRAM, DM_BAD (n octets and one more for the verdict);
+//               eddsa_verify_all_dev_locked unchanged, its verdict into DM_BAD[n]; k_eddsa_msgs_all_fin: the bit
+//   sign        eddsa_sign_msg_dev_locked with k_eddsa_expand_r_msgs / k_eddsa_hram_msgs in place of the slot kernels
+// The host forms stage pieces through msgs_host_call (ecamd_host_sigfam.cpp).  It takes ctx->mu itself: the checks, which run the
+// curve's one-time setup, take and drop the lock first.
+// ------------------------------------------------------------------------------------------
+static int eddsa_msgs_checks(const char *fn, ecamd_ctx *ctx, const ecamd_curve *cv, int alg, const uint8_t *adata, uint32_t adata_len,
+			     EcamdEdSignArgs *T, eced::Dom *dom)
+{
+	if (!ctx) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	std::lock_guard<std::mutex> lk(ctx->mu);
+	return eddsa_alg_args_ok(fn, ctx, cv, alg, adata, adata_len, T, dom);   // (runs the handle's one-time setup: the verification cores need it too)
+}
+
+static int eddsa_vhram_msgs_launch(int alg, const eced::Dom &dom, uint32_t m, const uint8_t *d_pub, const uint8_t *d_sig, const EdRagged &rg,
+				   uint32_t off, uint8_t *d_hram, uint8_t *d_bad, hipStream_t s)
+{
+	EcamdEddsaMsgsArgs M;
+	eddsa_front_args(&M.e, dom);
+	M.e.n = m;
+	M.e.A = d_pub;
+	M.e.hram = d_hram;
+	M.e.bad = d_bad;
+	M.vsigs = d_sig;
+	M.msgs = rg.d_msgs;
+	M.msgs_len = rg.msgs_len;
+	M.offsets = rg.d_offsets + off;
+	HIPCHK(ecamd_launch_eddsa_vhram_msgs(alg, M, s));
+	return 0;
+}
+
+static int eddsa_verify_msgs_dev_locked(ecamd_ctx *ctx, ecamd_curve *cv, int alg, const eced::Dom &dom, uint32_t n, const uint8_t *d_pub,
+					const uint8_t *d_sig, const EdRagged &rg, uint8_t *d_res, hipStream_t s)
+{
+	const bool e448 = eced::alg_is448(alg);
+	const size_t kl = e448 ? 57 : 32, hl = 2 * kl;
+	const uint32_t chunk = chunk_items(ctx, n);
+	if (stage_need(ctx, {{ST_DIGESTS, (size_t)chunk * hl}, {DM_BAD, chunk}})) {
+		return -1;
+	}
+	return for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+		uint8_t **S = ctx->stage;   // (read per chunk: the cores below grow their own frames)
+		if (eddsa_vhram_msgs_launch(alg, dom, m, d_pub + off * kl, d_sig + off * 2 * kl, rg, off, S[ST_DIGESTS], S[DM_BAD], s)) {
+			return -1;
+		}
+		if (e448 ? eddsa448_verify_dev_locked(ctx, cv, m, d_pub + off * kl, d_sig + off * 2 * kl, S[ST_DIGESTS], d_res + off, s)
+			 : eddsa_verify_dev_locked(ctx, cv, m, d_pub + off * kl, d_sig + off * 2 * kl, S[ST_DIGESTS], 64, d_res + off, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_reject_where(d_res + off, S[DM_BAD], m, s));
+		return 0;
+	});
+}
+
+extern "C" int ec_eddsa_verify_msgs_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const void *d_pubkeys, const void *d_sigs,
+					      const uint8_t *adata, uint32_t adata_len, const void *d_msgs, uint64_t msgs_len, const void *d_offsets,
+					      void *d_result, void *hip_stream)
+{
+	const char *fn = "ec_eddsa_verify_msgs_batch_dev";
+	EcamdEdSignArgs T;
+	eced::Dom dom;
+	if (eddsa_msgs_checks(fn, ctx, cv, alg, adata, adata_len, &T, &dom)) {
+		return -1;
+	}
+	if (n && (!d_pubkeys || !d_sigs || !d_offsets || !d_result)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (msgs_dev_ptr_ok(fn, d_msgs, msgs_len, d_offsets)) {
+		return -1;
+	}
+	const EdRagged rg = {(const uint8_t *)d_msgs, msgs_len, (const uint64_t *)d_offsets};
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return eddsa_verify_msgs_dev_locked(ctx, const_cast<ecamd_curve *>(cv), alg, dom, n, (const uint8_t *)d_pubkeys, (const uint8_t *)d_sigs, rg,
+						    (uint8_t *)d_result, s);
+	});
+}
+
+extern "C" int ec_eddsa_verify_msgs_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *pubkeys, const uint8_t *sigs,
+					  const uint8_t *adata, uint32_t adata_len, const uint8_t *msgs, const uint64_t *offsets, uint8_t *result)
+{
+	const char *fn = "ec_eddsa_verify_msgs_batch";
+	EcamdEdSignArgs T;
+	eced::Dom dom;
+	if (eddsa_msgs_checks(fn, ctx, cv, alg, adata, adata_len, &T, &dom)) {
+		return -1;
+	}
+	if (n && (!pubkeys || !sigs || !offsets || !result)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t kl = T.is448 ? 57 : 32;
+	const std::vector<MsgsArr> arrs = {{pubkeys, nullptr, kl, kl}, {sigs, nullptr, 2 * kl, 2 * kl}, {nullptr, result, 1, 1}};
+	return msgs_host_call(fn, ctx, n, msgs, offsets, arrs,
+			      [&](uint32_t m, const uint8_t *d_msgs, uint64_t len, const uint64_t *d_offs, const DevIn &ip, const DevOut &op, hipStream_t s) {
+		const EdRagged rg = {d_msgs, len, d_offs};
+		return eddsa_verify_msgs_dev_locked(ctx, const_cast<ecamd_curve *>(cv), alg, dom, m, ip[0], ip[1], rg, op[2], s);
+	});
+}
+
+static int eddsa_msgs_all_available(const char *fn, ecamd_curve *cv, uint32_t n)
+{
+	if (n == 0 || (cv->pbits == 448 ? !eddsa448_msm_available(cv) : !eddsa_msm_available(cv))) {
+		return fail(std::string(fn) + ": needs n > 0 and Ed25519 (the WEI25519 handle on the 2^255 - 19 unit) or Ed448 (WEI448 on the Goldilocks unit)");
+	}
+	return 0;
+}
+
+static int eddsa_verify_msgs_all_batch_dev_impl(ecamd_ctx *ctx, const ecamd_curve *cv_in, int alg, uint32_t n, const void *d_pubkeys, const void *d_sigs,
+						const uint8_t *adata, uint32_t adata_len, const void *d_msgs, uint64_t msgs_len, const void *d_offsets,
+						void *d_all_valid, void *hip_stream)
+{
+	const char *fn = "ec_eddsa_verify_msgs_all_batch_dev";
+	EcamdEdSignArgs T;
+	eced::Dom dom;
+	if (eddsa_msgs_checks(fn, ctx, cv_in, alg, adata, adata_len, &T, &dom)) {
+		return -1;
+	}
+	if (!d_pubkeys || !d_sigs || !d_offsets || !d_all_valid) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	ecamd_curve *cv = const_cast<ecamd_curve *>(cv_in);
+	if (eddsa_msgs_all_available(fn, cv, n) || msgs_dev_ptr_ok(fn, d_msgs, msgs_len, d_offsets)) {
+		return -1;
+	}
+	const EdRagged rg = {(const uint8_t *)d_msgs, msgs_len, (const uint64_t *)d_offsets};
+	const size_t kl = T.is448 ? 57 : 32, hl = 2 * kl;
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) -> int {
+		uint8_t seed[32];
+		if (msm_seed(ctx, seed) || stage_need(ctx, {{EB_HRAM, (size_t)n * hl}, {DM_BAD, (size_t)n + 1}})) {
+			return -1;
+		}
+		uint8_t *d_hram = ctx->stage[EB_HRAM], *d_bad = ctx->stage[DM_BAD];
+		if (for_chunks(ctx, n, [&](uint32_t off, uint32_t m) -> int {
+			    return eddsa_vhram_msgs_launch(alg, dom, m, (const uint8_t *)d_pubkeys + off * kl, (const uint8_t *)d_sigs + off * 2 * kl, rg, off,
+							   d_hram + off * hl, d_bad + off, s);
+		    }) ||
+		    eddsa_verify_all_dev_locked(ctx, cv, n, d_pubkeys, d_sigs, d_hram, seed, d_bad + n, s)) {
+			return -1;
+		}
+		HIPCHK(ecamd_launch_eddsa_msgs_all_fin(d_bad, n + 1, (uint8_t *)d_all_valid, s));
+		return 0;
+	});
+}
+
+extern "C" int ec_eddsa_verify_msgs_all_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const void *d_pubkeys, const void *d_sigs,
+						  const uint8_t *adata, uint32_t adata_len, const void *d_msgs, uint64_t msgs_len, const void *d_offsets,
+						  void *d_all_valid, void *hip_stream)
+{
+	const int r = eddsa_verify_msgs_all_batch_dev_impl(ctx, cv, alg, n, d_pubkeys, d_sigs, adata, adata_len, d_msgs, msgs_len, d_offsets, d_all_valid,
+							   hip_stream);
+	msm_seed_discard(ctx);
+	return r;
+}
+
+extern "C" int ec_eddsa_verify_msgs_all_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *pubkeys, const uint8_t *sigs,
+					      const uint8_t *adata, uint32_t adata_len, const uint8_t *msgs, const uint64_t *offsets, int *all_valid,
+					      uint32_t *first_rejected)
+{
+	const char *fn = "ec_eddsa_verify_msgs_all_batch";
+	EcamdEdSignArgs T;
+	eced::Dom dom;
+	if (eddsa_msgs_checks(fn, ctx, cv, alg, adata, adata_len, &T, &dom)) {
+		msm_seed_discard(ctx);
+		return -1;
+	}
+	if (n == 0 || !pubkeys || !sigs || !offsets || !all_valid) {
+		msm_seed_discard(ctx);
+		return fail(std::string(fn) + ": bad argument (the reference rejects num = 0 too)");
+	}
+	*all_valid = 0;
+	if (first_rejected) {
+		*first_rejected = n;
+	}
+	// the hram launch piece by piece, its output back on the host: what ec_eddsa_verify_all_batch takes
+	const size_t kl = T.is448 ? 57 : 32, hl = 2 * kl;
+	std::vector<uint8_t> hram((size_t)n * hl), bad(n);
+	const std::vector<MsgsArr> arrs = {{pubkeys, nullptr, kl, kl}, {sigs, nullptr, 2 * kl, 2 * kl}, {nullptr, hram.data(), hl, hl}, {nullptr, bad.data(), 1, 1}};
+	if (msgs_host_call(fn, ctx, n, msgs, offsets, arrs,
+			   [&](uint32_t m, const uint8_t *d_msgs, uint64_t len, const uint64_t *d_offs, const DevIn &ip, const DevOut &op, hipStream_t s) {
+		const EdRagged rg = {d_msgs, len, d_offs};
+		return eddsa_vhram_msgs_launch(alg, dom, m, ip[0], ip[1], rg, 0, op[2], op[3], s);
+	})) {
+		msm_seed_discard(ctx);
+		return -1;
+	}
+	uint32_t first_bad = 0;
+	while (first_bad < n && bad[first_bad] == 0) {
+		first_bad++;
+	}
+	int ok = 0;
+	uint32_t first = n;
+	if (ec_eddsa_verify_all_batch(ctx, cv, n, pubkeys, sigs, hram.data(), (uint32_t)hl, &ok, &first)) {   // (discards the seed itself)
+		return -1;
+	}
+	*all_valid = (ok && first_bad == n) ? 1 : 0;
+	if (first_rejected) {
+		*first_rejected = first < first_bad ? first : first_bad;
+	}
+	return 0;
+}
+
+extern "C" int ec_eddsa_sign_msgs_batch_dev(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const void *d_secret_keys, const void *d_pubkeys,
+					    const uint8_t *adata, uint32_t adata_len, const void *d_msgs, uint64_t msgs_len, const void *d_offsets,
+					    void *d_sigs, void *d_pub_out, void *d_status, void *hip_stream)
+{
+	const char *fn = "ec_eddsa_sign_msgs_batch_dev";
+	EcamdEdSignArgs T;
+	eced::Dom dom;
+	if (eddsa_msgs_checks(fn, ctx, cv, alg, adata, adata_len, &T, &dom)) {
+		return -1;
+	}
+	if (n && (!d_secret_keys || !d_offsets || !d_sigs || !d_status)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	if (msgs_dev_ptr_ok(fn, d_msgs, msgs_len, d_offsets)) {
+		return -1;
+	}
+	const EdRagged rg = {(const uint8_t *)d_msgs, msgs_len, (const uint64_t *)d_offsets};
+	return dev_call(ctx, hip_stream, [&](hipStream_t s) {
+		return eddsa_sign_msg_dev_locked(ctx, cv, T, alg, dom, n, (const uint8_t *)d_secret_keys, (const uint8_t *)d_pubkeys, nullptr, 0, (uint8_t *)d_sigs,
+						 (uint8_t *)d_pub_out, (uint8_t *)d_status, s, &rg);
+	});
+}
+
+extern "C" int ec_eddsa_sign_msgs_batch(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *secret_keys, const uint8_t *pubkeys,
+					const uint8_t *adata, uint32_t adata_len, const uint8_t *msgs, const uint64_t *offsets, uint8_t *sigs,
+					uint8_t *pub_out, uint8_t *status)
+{
+	const char *fn = "ec_eddsa_sign_msgs_batch";
+	EcamdEdSignArgs T;
+	eced::Dom dom;
+	if (eddsa_msgs_checks(fn, ctx, cv, alg, adata, adata_len, &T, &dom)) {
+		return -1;
+	}
+	if (n && (!secret_keys || !offsets || !sigs || !status)) {
+		return fail(std::string(fn) + ": bad argument");
+	}
+	if (n == 0) {
+		return 0;
+	}
+	const size_t kl = T.is448 ? 57 : 32;
+	// the optional arrays keep their places: an array with neither pointer is neither copied nor read
+	const std::vector<MsgsArr> arrs = {{secret_keys, nullptr, kl, kl}, {pubkeys, nullptr, pubkeys ? kl : 0, pubkeys ? kl : 0}, {nullptr, sigs, 2 * kl, 2 * kl},
+					   {nullptr, pub_out, pub_out ? kl : 0, pub_out ? kl : 0}, {nullptr, status, 1, 1}};
+	return msgs_host_call(fn, ctx, n, msgs, offsets, arrs,
+			      [&](uint32_t m, const uint8_t *d_msgs, uint64_t len, const uint64_t *d_offs, const DevIn &ip, const DevOut &op, hipStream_t s) {
+		const EdRagged rg = {d_msgs, len, d_offs};
+		return eddsa_sign_msg_dev_locked(ctx, cv, T, alg, dom, m, ip[0], ip[1], nullptr, 0, op[2], op[3], op[4], s, &rg);
 	});
 }
 

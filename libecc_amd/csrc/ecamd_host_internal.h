@@ -83,7 +83,7 @@ int fail(const std::string &m);   // files the thread's error string (ecamd_last
 //   ES_  one-call EdDSA sign  30..40        eddsa_sign_msg_dev_locked, eddsa_pub_key_dev_locked    SR_
 //   SM_  sig from messages    41, 42        sig_msg_verify_ / sig_msg_sign_dev_locked, which outlive the digest-level core they call   ST_, VP_, SG_, ST_SLOTS, ST_DIGESTS, ST_TARGET
 //   DM_  ragged messages      43..45        msgs_host_call (the staged piece of the message array and its rebased offsets), ecdsa_verify_msgs_ /
-//                                           decdsa_sign_msgs_dev_locked (DM_BAD), which outlive the core they call   ST_, VP_, SG_, ST_DIGESTS
+//                                           decdsa_sign_msgs_ / eddsa_verify_msgs_dev_locked (DM_BAD), which outlive the core they call   ST_, VP_, SG_, EV_, ST_DIGESTS
 //
 // smul_dev_locked itself takes no slot (ctx->tbl, ctx->tbl_fast); host_pipeline stages in ctx->hbuf.
 // ------------------------------------------------------------------------------------------
@@ -330,6 +330,21 @@ int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, c
 int ecdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
 			  const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s);
 int sig_alg_ok(const char *fn, int alg);
+
+// ---- the ragged message array (ecamd_host_sigfam.cpp), shared with EdDSA's ragged calls (ecamd_host.cpp) ----
+// a per-item array of a host form: `stride` octets from item to item, `len` octets used per item (the last item's stride is not read)
+struct MsgsArr {
+	const uint8_t *in;
+	uint8_t *out;
+	size_t stride, len;
+};
+using MsgsCore = std::function<int(uint32_t m, const uint8_t *d_msgs, uint64_t msgs_len, const uint64_t *d_offsets, const DevIn &ip, const DevOut &op, hipStream_t s)>;
+// The host form of a ragged call: takes ctx->mu, stages pieces of at most max_chunk items or MSGS_CHUNK_BYTES octets with offsets rebased
+// to the piece (DM_MSGS / DM_OFFS, the per-item arrays through ctx->hbuf[0]) and runs core on each; one piece at a time.
+int msgs_host_call(const char *fn, ecamd_ctx *ctx, uint32_t n, const uint8_t *msgs, const uint64_t *offsets, const std::vector<MsgsArr> &arrs,
+		   const MsgsCore &core);
+// the alignment of a _dev form's d_msgs (4) and d_offsets (8), and d_msgs != NULL with a positive length
+int msgs_dev_ptr_ok(const char *fn, const void *d_msgs, uint64_t msgs_len, const void *d_offsets);
 int sig_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, int alg, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
 			const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s);
 

@@ -2068,7 +2068,7 @@ static int msgs_prefix_ok(const char *fn, uint32_t n, const uint8_t *call_prefix
 	return 0;
 }
 
-static int msgs_dev_ptr_ok(const char *fn, const void *d_msgs, uint64_t msgs_len, const void *d_offsets)
+int ecamd_host::msgs_dev_ptr_ok(const char *fn, const void *d_msgs, uint64_t msgs_len, const void *d_offsets)
 {
 	if (((uintptr_t)d_msgs & 3u) || ((uintptr_t)d_offsets & 7u)) {
 		return fail(std::string(fn) + ": d_msgs must be 4-byte aligned and d_offsets 8-byte aligned");
@@ -2079,15 +2079,8 @@ static int msgs_dev_ptr_ok(const char *fn, const void *d_msgs, uint64_t msgs_len
 	return 0;
 }
 
-// a per-item array of a host form: `stride` octets from item to item, `len` octets used per item (the last item's stride is not read)
-struct MsgsArr {
-	const uint8_t *in;
-	uint8_t *out;
-	size_t stride, len;
-};
-using MsgsCore = std::function<int(uint32_t m, const uint8_t *d_msgs, uint64_t msgs_len, const uint64_t *d_offsets, const DevIn &ip, const DevOut &op, hipStream_t s)>;
-
-static int msgs_host_call(const char *fn, ecamd_ctx *ctx, uint32_t n, const uint8_t *msgs, const uint64_t *offsets, const std::vector<MsgsArr> &arrs,
+// (MsgsArr, MsgsCore: ecamd_host_internal.h -- EdDSA's ragged calls in ecamd_host.cpp stage their pieces through this too)
+int ecamd_host::msgs_host_call(const char *fn, ecamd_ctx *ctx, uint32_t n, const uint8_t *msgs, const uint64_t *offsets, const std::vector<MsgsArr> &arrs,
 			  const MsgsCore &core)
 {
 	const size_t na = arrs.size();

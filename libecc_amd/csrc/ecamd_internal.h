@@ -858,6 +858,25 @@ struct EcamdDigestMsgsArgs {
 	uint32_t call_prefix[64];      // zero behind its last octet
 };
 hipError_t ecamd_launch_digest_msgs(int hash_type, const EcamdDigestMsgsArgs &a, hipStream_t s);
+// EdDSA's hashes over the same packed array (ecamd_eddsa_msgs.h / ecamd_eddsa_msgs.hip); alg 9 .. 13.  An unusable item (offsets as
+// above; the input above 2^28 octets) sets bad[i] and reads nothing of msgs.
+//   vhram        (k_eddsa_vhram_msgs)     a verifier's hram: R_i = the first klen octets of vsigs + i * 2 klen, A_i = e.A + i * klen,
+//                                         -> e.hram (zeros for an unusable item), e.bad.  Reads e.n, e.dom, e.dom_len beside them.
+//   sign_expand  (k_eddsa_expand_r_msgs)  k_eddsa_expand_r with the message from the array: the same fields of e read and written
+//   sign_hram    (k_eddsa_hram_msgs)      k_eddsa_hram likewise
+// e.slots and e.stride are not used.
+struct EcamdEddsaMsgsArgs {
+	EcamdEddsaSignArgs e;
+	const uint8_t *vsigs;       // vhram: n x 2 klen signatures
+	const uint8_t *msgs;        // any alignment; only octets of an item's own message are read
+	uint64_t msgs_len;
+	const uint64_t *offsets;    // n + 1
+};
+hipError_t ecamd_launch_eddsa_vhram_msgs(int alg, const EcamdEddsaMsgsArgs &a, hipStream_t s);
+hipError_t ecamd_launch_eddsa_expand_msgs(int alg, const EcamdEddsaMsgsArgs &a, hipStream_t s);
+hipError_t ecamd_launch_eddsa_hram_msgs(int alg, const EcamdEddsaMsgsArgs &a, hipStream_t s);
+// all_valid[0] = 1 when no octet of flags[0 .. n) is set, else 0 (the whole-batch bit behind the combination's verdict and the bad items)
+hipError_t ecamd_launch_eddsa_msgs_all_fin(const uint8_t *flags, uint32_t n, uint8_t *all_valid, hipStream_t s);
 // SM2's Z per item from the call's prefix (ecamd_sm2z.h) and the keys' 2 clen octets, hsize octets each into z
 namespace ecsm2z { struct Prefix; }
 hipError_t ecamd_launch_sm2_z(const ecsm2z::Prefix &P, const uint8_t *keys, uint32_t klen, uint8_t *z, uint32_t hsize, uint32_t n, hipStream_t s);

@@ -7,7 +7,7 @@ bytes per step); not the driver's headline bench.  --workload ecdsa_recover is t
 verification of the same signatures in alternating windows (recover_row).  sig_hashed_verify / sig_hashed_sign / schnorr_verify /
 schnorr_sign / bip0340_sign with --hash 5 .. 11, 13 .. 15, 17 .. 20 or --hashes LIST|new go through the _ht entry points (commit_ht_rows).
 
-    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|sig_msg_verify|sig_msg_sign|hash_slots [--alg sm2|ecrdsa|ecgdsa --hash 11|13|14|2 --curve C]|digest_msgs [--hash N --lens 32|1024|mixed]|digest_slots|hmac_slots [--hash 1..11|13..15|17..20]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..11|13..15|17..20 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
+    python tools/bench_protocols.py --workload ecdsa_verify|ecdsa_recover|sig_verify|sig_sign [--alg ecgdsa|ecrdsa|sm2]|sig_msg_verify|sig_msg_sign|hash_slots [--alg sm2|ecrdsa|ecgdsa --hash 11|13|14|2 --curve C]|digest_msgs [--hash N --lens 32|1024|mixed]|eddsa_verify_msgs|eddsa_sign_msgs [--alg ed25519|.. --lens 32|1024|mixed]|digest_slots|hmac_slots [--hash 1..11|13..15|17..20]|bign_verify|bign_sign [--hash 0|16]|decdsa_sign [--hash 1..11|13..15|17..20 --curve C]|dbign_sign [--secret]|bip0340_sign [--secret]|eddsa_sign --alg ed25519|ed25519ctx|ed25519ph|ed448|ed448ph [--derive-pub]|ecdsa_sign|ecccdh|ed25519_verify|ed448_verify|x25519|x448|bip0340_msm|ed25519_msm [--gpus N --steps K --warmup W]
 """
 import argparse
 import hashlib
@@ -264,6 +264,136 @@ def digest_msgs_lens(kind, B):
     lens = np.where(u < 0.97, r.integers(16, 257, size=B), np.where(u < 0.999, r.integers(257, 2049, size=B), r.integers(2049, 4093, size=B)))
     lens[0] = 4092
     return lens.astype(np.int64)
+
+
+def eddsa_msgs_row(a, ctx, dev, stream, rng, B):
+    """--workload eddsa_verify_msgs | eddsa_sign_msgs (--alg ed25519 .. ed448ph, --lens 32 | 1024 | mixed, digest_msgs_lens): EdDSA from
+    the packed array, device-resident, beside its slot twin on the SAME content in alternating windows of a.steps calls.
+      eddsa_sign_msgs    ec_eddsa_sign_msgs_batch_dev beside ec_eddsa_sign_msg_batch_dev (message slots resident in HBM)
+      eddsa_verify_msgs  ec_eddsa_verify_msgs_batch_dev beside ec_eddsa_verify_msg_batch, the HOST form with host-assembled slots
+                         dom2 || R || A || PH(M) (it has no device form, so its time includes the upload of the slots; Ed25519 only --
+                         the Ed448 variants have no slot twin and run alone).  Every 10th signature is damaged.  `mixed` lengths are
+                         clipped so that the assembled input fits a slot.
+    Gates: the two paths give the same bytes for the whole batch; every signature made is accepted and every damaged one rejected.
+    One GPU only."""
+    if a.gpus != 1 or int(os.environ.get("WORLD_SIZE", "1")) != 1:
+        raise SystemExit("--workload %s measures one GPU: run it with --gpus 1, outside torch.distributed.run" % a.workload)
+    if not a.alg.startswith("ed"):
+        raise SystemExit("--workload %s: --alg ed25519 | ed25519ctx | ed25519ph | ed448 | ed448ph" % a.workload)
+    import ctypes as C
+    import eddsa_sign_ref as E
+    alg = {"ed25519": E.EDDSA25519, "ed25519ctx": E.EDDSA25519CTX, "ed25519ph": E.EDDSA25519PH, "ed448": E.EDDSA448, "ed448ph": E.EDDSA448PH}[a.alg]
+    verify = a.workload == "eddsa_verify_msgs"
+    cv = ctx.curve(E.curve_of(alg))
+    kl = E.klen(alg)
+    ad = b"bench" if E.takes_ctx(alg) else None
+    dom = E.dom(alg, ad or b"")
+    lens = digest_msgs_lens(a.lens, B)
+    twin = not (verify and E.is448(alg))
+    if verify and not E.is_ph(alg):
+        lens = np.minimum(lens, 4092 - len(dom) - 2 * kl)
+    offs = np.zeros(B + 1, dtype=np.int64)
+    np.cumsum(lens, out=offs[1:])
+    total = int(offs[B])
+    content = rng.integers(0, 256, size=(total + 3) & ~3, dtype=np.uint8)
+    d_msgs, d_offs = torch.from_numpy(content).to(dev), torch.from_numpy(offs).to(dev)
+    sp = stream.cuda_stream
+    d_sk = torch.from_numpy(rng.integers(0, 256, size=B * kl, dtype=np.uint8)).to(dev)
+    d_pub, d_st = torch.empty(B * kl, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+    d_sig, d_sig2 = torch.empty(B * 2 * kl, dtype=torch.uint8, device=dev), torch.empty(B * 2 * kl, dtype=torch.uint8, device=dev)
+    cv.eddsa_pub_keys_dev(B, d_sk.data_ptr(), d_pub.data_ptr(), d_st.data_ptr(), sp)
+    cv.eddsa_sign_msg_list_dev(alg, B, d_sk.data_ptr(), d_pub.data_ptr(), ad, d_msgs.data_ptr(), total, d_offs.data_ptr(), d_sig.data_ptr(), None,
+                               d_st.data_ptr(), sp)
+    torch.cuda.synchronize()
+    if int(d_st.max()) != 0:
+        raise SystemExit("PARITY FAILURE: an item was not signed")
+    if not verify:
+        # the message slots of the same content, laid out on the device
+        stride = (4 + int(lens.max()) + 3) & ~3
+        d_lens = torch.from_numpy(lens).to(dev)
+        d_sl = torch.zeros(B * stride, dtype=torch.uint8, device=dev)
+        d_sl.view(B, stride)[:, :4] = torch.stack([(d_lens >> (8 * k)) & 255 for k in range(4)], dim=1).to(torch.uint8)
+        item = torch.repeat_interleave(torch.arange(B, device=dev), d_lens)
+        d_sl[item * stride + 4 + (torch.arange(total, device=dev) - d_offs[item])] = d_msgs[:total]
+        del item
+        fns = [lambda: cv.eddsa_sign_msg_list_dev(alg, B, d_sk.data_ptr(), d_pub.data_ptr(), ad, d_msgs.data_ptr(), total, d_offs.data_ptr(),
+                                                  d_sig.data_ptr(), None, d_st.data_ptr(), sp),
+               lambda: cv.eddsa_sign_msgs_dev(alg, B, d_sk.data_ptr(), d_pub.data_ptr(), ad, d_sl.data_ptr(), stride, d_sig2.data_ptr(), None,
+                                              d_st.data_ptr(), sp)]
+        twin_name, twin_octets = "ec_eddsa_sign_msg_batch_dev", B * stride
+    else:
+        bad = np.zeros(B, dtype=np.uint8)
+        bad[::10] = 1
+        d_sig.view(B, 2 * kl)[::10, kl] ^= 1          # a bit of S of every 10th signature
+        expected = torch.from_numpy(bad).to(dev)
+        d_res, d_res2 = torch.empty(B, dtype=torch.uint8, device=dev), torch.empty(B, dtype=torch.uint8, device=dev)
+        fns = [lambda: cv.eddsa_verify_msg_list_dev(alg, B, d_pub.data_ptr(), d_sig.data_ptr(), ad, d_msgs.data_ptr(), total, d_offs.data_ptr(),
+                                                    d_res.data_ptr(), sp)]
+        twin_name, twin_octets, stride = None, 0, 0
+        if twin:
+            # dom2 || R || A || PH(M) per item, assembled on the host as a caller of ec_eddsa_verify_msg_batch has to
+            pubs, sigs = d_pub.cpu().numpy().reshape(B, kl), d_sig.cpu().numpy().reshape(B, 2 * kl)
+            tail = [E.PH(alg, content[offs[i]:offs[i + 1]].tobytes()) for i in range(B)] if E.is_ph(alg) else None
+            tl = np.full(B, 64, dtype=np.int64) if E.is_ph(alg) else lens
+            head = len(dom) + 2 * kl
+            stride = (4 + head + int(tl.max()) + 3) & ~3
+            slots = np.zeros((B, stride), dtype=np.uint8)
+            slots[:, :4] = np.stack([((head + tl) >> (8 * k)) & 255 for k in range(4)], axis=1).astype(np.uint8)
+            slots[:, 4:4 + len(dom)] = np.frombuffer(dom, dtype=np.uint8)
+            slots[:, 4 + len(dom):4 + len(dom) + kl] = sigs[:, :kl]
+            slots[:, 4 + len(dom) + kl:4 + head] = pubs
+            for i in range(B):
+                slots[i, 4 + head:4 + head + tl[i]] = np.frombuffer(tail[i], dtype=np.uint8) if tail else content[offs[i]:offs[i + 1]]
+            pubs_b, sigs_b, slots_b = pubs.tobytes(), sigs.tobytes(), slots.ctypes.data_as(C.c_char_p)   # (slots stays alive: no second copy)
+            res2 = C.create_string_buffer(B)
+
+            def slot_call():
+                if cv.L.ec_eddsa_verify_msg_batch(ctx.h, cv.h, B, pubs_b, sigs_b, slots_b, stride, res2) != 0:
+                    raise SystemExit("ec_eddsa_verify_msg_batch failed")
+            fns.append(slot_call)
+            twin_name, twin_octets = "ec_eddsa_verify_msg_batch (host form, upload included)", B * (stride + 3 * kl)
+    torch.cuda.synchronize()
+    for _ in range(max(1, a.warmup)):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    if verify:
+        if not torch.equal(d_res, expected):
+            raise SystemExit("PARITY FAILURE: the verdicts are not: every 10th item rejected")
+        if twin and res2.raw[:B] != bad.tobytes():
+            raise SystemExit("PARITY FAILURE: the slot twin's verdicts differ")
+        gate = "every 10th signature rejected, all others accepted" + (", by both paths" if twin else "")
+    else:
+        if not torch.equal(d_sig, d_sig2) or int(d_st.max()) != 0:
+            raise SystemExit("PARITY FAILURE: the two paths give different signatures")
+        d_res = torch.empty(B, dtype=torch.uint8, device=dev)
+        cv.eddsa_verify_msg_list_dev(alg, B, d_pub.data_ptr(), d_sig.data_ptr(), ad, d_msgs.data_ptr(), total, d_offs.data_ptr(), d_res.data_ptr(), sp)
+        torch.cuda.synchronize()
+        if int(d_res.max()) != 0:
+            raise SystemExit("PARITY FAILURE: a signature the device made was rejected")
+        gate = "both paths give the same 2^%d signatures; ec_eddsa_verify_msgs_batch_dev accepts all" % a.batch_log2
+    acc = [[] for _ in fns]
+    for _ in range(3):
+        for fn, ac in zip(fns, acc):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                fn()
+            torch.cuda.synchronize()
+            ac.append((time.perf_counter() - t0) / a.steps)
+    ma = float(np.median(acc[0]))
+    row = {"metric": "%s %s of 2^%d messages (--lens %s) from the packed array, ns per item (device-resident)" % (a.alg, a.workload, a.batch_log2, a.lens),
+           "value": 1e9 * ma / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[0]], "items_per_s": B / ma, "message_octets": total,
+           "octets_uploaded": total + 8 * (B + 1) + B * 3 * kl, "gate": gate,
+           "config": {"workload": a.workload, "alg": a.alg, "lens": a.lens, "steps": a.steps, "warmup": a.warmup, "windows": 3}}
+    if len(fns) == 2:
+        mb = float(np.median(acc[1]))
+        row["slot_twin_same_run"] = {"call": twin_name, "value": 1e9 * mb / B, "unit": "ns/item", "ms": [1e3 * x for x in acc[1]], "stride": stride,
+                                     "octets_uploaded": twin_octets + (0 if verify else B * 2 * kl)}
+        row["ratio_msgs_over_slots_time"] = ma / mb
+    else:
+        row["slot_twin_same_run"] = None
+    print(json.dumps(row))
+    ctx.close()
 
 
 def digest_msgs_row(a, ctx, dev, stream, rng, B):
@@ -1366,7 +1496,7 @@ def commit_ht_rows(a, ctx, dev, stream, rng, B, hashes):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_msg_verify", "sig_msg_sign", "hash_slots", "digest_slots", "digest_msgs", "hmac_slots", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
+    ap.add_argument("--workload", required=True, choices=["ecdsa_verify", "ecdsa_recover", "sig_verify", "sig_sign", "sig_msg_verify", "sig_msg_sign", "hash_slots", "digest_slots", "digest_msgs", "eddsa_verify_msgs", "eddsa_sign_msgs", "hmac_slots", "sig_hashed_verify", "sig_hashed_sign", "schnorr_verify", "schnorr_sign", "bign_verify", "bign_sign", "decdsa_sign", "dbign_sign", "bip0340_sign", "eddsa_sign", "ecdsa_sign", "ecccdh", "ed25519_verify", "ed448_verify", "x25519", "x448", "bip0340_msm", "ed25519_msm", "ed448_msm"])
     ap.add_argument("--alg", default="sm2", choices=["ecgdsa", "ecrdsa", "sm2", "eckcdsa", "ecsdsa", "ecosdsa", "bip0340", "ecfsdsa",
                                                     "ed25519", "ed25519ctx", "ed25519ph", "ed448", "ed448ph"],
                     help="eddsa_sign: ed25519, ed25519ctx, ed25519ph, ed448, ed448ph; sig_verify / sig_sign: ecgdsa, ecrdsa, sm2; sig_hashed_verify / sig_hashed_sign: eckcdsa, ecsdsa, ecosdsa; schnorr_verify / schnorr_sign: bip0340, ecfsdsa")
@@ -1375,7 +1505,7 @@ def main():
                          "decdsa_sign: SHA-256 by default, 1 .. 4 through ec_decdsa_sign_batch, the rest through ec_decdsa_sign_ht_batch; digest_slots, hmac_slots: any of libecc's numbers but 0 and 16 (default 6, SHA3-256)")
     ap.add_argument("--hashes", default=None, help="sig_hashed_verify / sig_hashed_sign / schnorr_verify / schnorr_sign / bip0340_sign: a comma-separated list of the "
                     "hash numbers 5 .. 11, 13 .. 15, 17 .. 20, or 'new' for all fourteen, measured in one run through the _ht names (--hash N: one of them)")
-    ap.add_argument("--lens", default="32", choices=["32", "1024", "mixed"], help="digest_msgs: the message lengths (digest_msgs_lens documents `mixed`)")
+    ap.add_argument("--lens", default="32", choices=["32", "1024", "mixed"], help="digest_msgs / eddsa_verify_msgs / eddsa_sign_msgs: the message lengths (digest_msgs_lens documents `mixed`)")
     ap.add_argument("--secret", action="store_true", help="dbign_sign / bip0340_sign: the context in secret-scalar mode")
     ap.add_argument("--derive-pub", action="store_true", help="eddsa_sign: pubkeys = NULL, A = encode([a]B) derived on the device (a second comb multiplication per item)")
     ap.add_argument("--gpus", type=int, default=1)
@@ -1451,6 +1581,8 @@ def main():
         return digest_slots_row(a, ctx, dev, stream, rng, B)
     if a.workload == "digest_msgs":
         return digest_msgs_row(a, ctx, dev, stream, rng, B)
+    if a.workload in ("eddsa_verify_msgs", "eddsa_sign_msgs"):
+        return eddsa_msgs_row(a, ctx, dev, stream, rng, B)
     if a.workload == "hmac_slots":
         return hmac_slots_row(a, ctx, dev, stream, rng, B)
     if commit_hashes is not None:
