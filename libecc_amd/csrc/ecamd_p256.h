@@ -1,7 +1,8 @@
 // libecc_amd/csrc/ecamd_p256.h -- secp256r1 group law on radix-2^29 lazy-reduced elements.
 //
 // Jacobian coordinates (x = X/Z^2, y = Y/Z^3), a = -3:
-//   doubling  4M + 4S   (dbl-2001-b with Z3 = 2YZ and 8 gamma^2 = 2 (2 gamma)^2)
+//   doubling  4M + 4S   (dbl-2001-b with Z3 = 2YZ and 8 gamma^2 = 2 (2 gamma)^2; 5M + 3S under one reduction fewer
+//                        with P256_FUSED_Y3_DBL, see below)
 //   addition 12M + 4S   (add-1998-cmo-2)
 // against 16 / 17 multiplications for the reference's complete projective formulas
 // (curves/prj_pt.c:892-950, 971-1071 in /root/reference/src).  Jacobian addition is NOT
@@ -278,6 +279,30 @@ U29_FN Fmul inv(const Fmul &x)
 #endif
 }
 
+// ---- Y3 as one two-product Montgomery reduction (u29::mul2) ----
+// Y3 is a difference of two products that nothing else reads, in dbl, madd and add_jac alike.  With one operand of the second
+// product negated against a multiple of p, both products go into the same column accumulators and are reduced ONCE: the second
+// reduction (36 MADs, 17 + 17 column-carry instructions) and the trailing sub() + carry() fall away.  One switch per site
+// (A/B builds: tools/build_variant.py); profiles/r24_p256_fused_y3.md has the measurements.  dbl's is on.  madd's (add_jac goes
+// with it) is off: built alone it met the acceptance rule of that note in one of two sessions only, so the formula stays the
+// parent's, 8M + 3S with two reductions for Y3.
+#ifndef P256_FUSED_Y3_DBL
+#define P256_FUSED_Y3_DBL 1
+#endif
+#ifndef P256_FUSED_Y3_MADD
+#define P256_FUSED_Y3_MADD 0
+#endif
+// 2^LOGC p - b: the operand that stands for -b in a fused product
+template <int LOGC, int S, class B> U29_FN auto neg(const B &b)
+{
+	F<0, 0, 0> zero;
+#pragma unroll
+	for (int i = 0; i < 9; i++) {
+		zero.l[i] = 0;
+	}
+	return sub<LOGC, S>(zero, b);
+}
+
 // ---- doubling: (X, Y, Z) -> 2 (X, Y, Z) ----
 U29_FN Jac dbl(const Jac &P)
 {
@@ -291,11 +316,22 @@ U29_FN Jac dbl(const Jac &P)
 	const auto a2 = sqr(alpha);
 	const auto beta8 = mul_small<2>(beta4);
 	const auto x3 = fold(sub<2, 1>(a2, beta8));          // alpha^2 - 8 beta
+	const auto t4 = sub<1, 1>(beta4, x3);                // 4 beta - X3
+#if P256_FUSED_Y3_DBL
+	// alpha t4 - 8 gamma^2 = alpha t4 + (2 gamma) (16p - 4 gamma).  The squaring form 2 (2 gamma)^2 is out of reach: a sum
+	// a b + c^2 cannot carry the minus sign (negating the alpha t4 side instead gives -Y3), so the 8 gamma^2 side costs 81
+	// products where the squaring took 45 and the MAD count of a doubling stays what it was; what goes is the second
+	// reduction's column carries and the trailing sub() + carry().  One carry() is needed whichever way 8 gamma^2 is split:
+	// t4's limbs reach 2^31, so alpha t4 takes 9 2^60 of a column and leaves (k gamma) (C p - (8 / k) gamma) 5 2^60, which no
+	// k in {1, 2, 4, 8} meets with uncarried bias limbs (2^61.3 at best, k = 2).  k = 2 with the negated side carried is 9 2^59.
+	const auto n4 = carry(neg<4, 2>(mul_small<4>(gamma)));  // 16p - 4 gamma
+	const auto y3 = mul2(alpha, t4, mul_small<2>(gamma), n4);
+#else
 	const auto g4 = sqr(mul_small<2>(gamma));            // 4 gamma^2
 	const auto g8 = mul_small<2>(g4);                    // 8 gamma^2
-	const auto t4 = sub<1, 1>(beta4, x3);                // 4 beta - X3
 	const auto y3a = mul(alpha, t4);
 	const auto y3 = carry(sub<2, 1>(y3a, g8));
+#endif
 	const auto z3 = mul_small<2>(mul(P.Y, P.Z));         // 2 Y Z
 	Jac R;
 	R.X = weaken<FX>(x3);
@@ -323,9 +359,13 @@ U29_FN Jac add_jac(const Jac &P, const FX2 &X2, const FY2 &Y2, const FZ2 &Z2, bo
 	const auto r2 = sqr(r);
 	const auto x3 = fold(sub<2, 2>(r2, add(hhh, mul_small<2>(v))));
 	const auto t5 = sub<1, 1>(v, x3);
+#if P256_FUSED_Y3_MADD
+	const auto y3 = mul2(r, t5, s1, neg<1, 0>(hhh));     // as in madd; no carry needed here either
+#else
 	const auto m1 = mul(r, t5);
 	const auto m2 = mul(s1, hhh);
 	const auto y3 = carry(sub<1, 0>(m1, m2));
+#endif
 	const auto z3 = mul(mul(P.Z, Z2), h);
 	h_is_zero = is_zero_mulout(z3);
 	Jac R;
@@ -351,7 +391,14 @@ template <class FY2> U29_FN Jac madd(const Jac &P, const Fcanon &X2, const FY2 &
 	const auto r2 = sqr(r);
 	const auto x3 = fold(sub<2, 2>(r2, add(hhh, mul_small<2>(v))));
 	const auto t5 = sub<1, 1>(v, x3);
+#if P256_FUSED_Y3_MADD
+	// r t5 - Y1 hhh = r t5 + Y1 (2p - hhh).  The negation goes on hhh and not on Y1: hhh is a multiplication result below
+	// 19/16 p with exact digits, so 2p dominates it limb by limb and the negated limbs stay below 2^30 -- Y1 hhh' takes 9 2^59 of
+	// a column beside r t5's 9 2^60 and no carry() is needed; Y1 (value < 6p, limbs above 2^29) would take 8p and a carry().
+	const auto y3 = mul2(r, t5, P.Y, neg<1, 0>(hhh));
+#else
 	const auto y3 = carry(sub<1, 0>(mul(r, t5), mul(P.Y, hhh)));
+#endif
 	const auto z3 = mul(P.Z, h);
 	h_is_zero = is_zero_mulout(z3);
 	Jac R;

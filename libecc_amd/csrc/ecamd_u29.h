@@ -147,31 +147,42 @@ template <u64 VBO> struct MulOut {
 // raw kernels on plain arrays (bounds are checked by the typed wrappers below).  Columns are compile-time
 // indexed so that each one's products and reduction terms go out as asm statements of up to twelve MADs
 // (ecamd_madchain.h: one padding s_nop per statement instead of one per MAD).
-template <bool SQR, int K_> struct Col9 {
+// SECOND: a second product summed into the same columns ahead of the ONE reduction (mul2 / mulsqr below): 0 none, 1 c * d, 2 c * c
+template <bool SQR, int K_, int SECOND = 0> struct Col9 {
 	static constexpr int LO = (K_ < 9) ? 0 : (K_ - 8);
 	static constexpr int HI = (K_ < 9) ? K_ : 8;
 	static constexpr int HALF = K_ / 2;
-	static constexpr int NPROD = SQR ? ((HALF >= LO) ? (HALF - LO + 1) : 0) : (HI - LO + 1);
+	static constexpr int NFULL = HI - LO + 1, NHALF = (HALF >= LO) ? (HALF - LO + 1) : 0;
+	static constexpr int NPROD = SQR ? NHALF : NFULL;
+	static constexpr int NPROD2 = (SECOND == 1) ? NFULL : ((SECOND == 2) ? NHALF : 0);
 	// reduction products m_i * q_j, i + j = k, j in {3, 6, 7, 8}, 0 <= i <= 8
 	static constexpr bool R3 = (K_ - 3 >= 0 && K_ - 3 <= 8), R6 = (K_ - 6 >= 0 && K_ - 6 <= 8);
 	static constexpr bool R7 = (K_ - 7 >= 0 && K_ - 7 <= 8), R8 = (K_ - 8 >= 0 && K_ - 8 <= 8);
 	static constexpr int NRED = (R3 ? 1 : 0) + (R6 ? 1 : 0) + (R7 ? 1 : 0) + (R8 ? 1 : 0);
 };
 
-template <bool SQR, int K_>
-U29_FN void mul_col9(u64 &acc, u32 *m, u32 *r, const u32 *a, const u32 *b, const u32 *a2, u32 q3, u32 q6, u32 q7, u32 q8)
+// second product (SECOND != 0): c * d, or c * c with c2 = the doubled limbs of c; its terms follow the first product's on the same chain
+template <bool SQR, int K_, int SECOND = 0>
+U29_FN void mul_col9(u64 &acc, u32 *m, u32 *r, const u32 *a, const u32 *b, const u32 *a2, u32 q3, u32 q6, u32 q7, u32 q8,
+		     const u32 *c = nullptr, const u32 *d = nullptr, const u32 *c2 = nullptr)
 {
-	typedef Col9<SQR, K_> C;
+	typedef Col9<SQR, K_, SECOND> C;
 	u64 unused = 0;
-	if constexpr (C::NPROD > 0) {
-		u32 x[C::NPROD], y[C::NPROD];
+	if constexpr (C::NPROD + C::NPROD2 > 0) {
+		u32 x[C::NPROD + C::NPROD2], y[C::NPROD + C::NPROD2];
 #pragma unroll
 		for (int n = 0; n < C::NPROD; n++) {
 			const int i = C::LO + n, j = K_ - i;
 			x[n] = a[i];
 			y[n] = !SQR ? b[j] : (i < j ? a2[j] : a[i]);
 		}
-		ecamd_mad_chain<C::NPROD, false, false>(acc, unused, x, y);
+#pragma unroll
+		for (int n = 0; n < C::NPROD2; n++) {
+			const int i = C::LO + n, j = K_ - i;
+			x[C::NPROD + n] = c[i];
+			y[C::NPROD + n] = (SECOND == 1) ? d[j] : (i < j ? c2[j] : c[i]);
+		}
+		ecamd_mad_chain<C::NPROD + C::NPROD2, false, false>(acc, unused, x, y);
 	}
 	if constexpr (C::NRED > 0) {
 		u32 x[C::NRED], y[C::NRED];
@@ -202,11 +213,11 @@ U29_FN void mul_col9(u64 &acc, u32 *m, u32 *r, const u32 *a, const u32 *b, const
 	// (no pin needed: the next column starts with an asm statement that takes acc as an operand)
 }
 
-template <bool SQR, int... Ks>
+template <bool SQR, int SECOND = 0, int... Ks>
 U29_FN void mul_cols9(u64 &acc, u32 *m, u32 *r, const u32 *a, const u32 *b, const u32 *a2, u32 q3, u32 q6, u32 q7, u32 q8,
-		      std::integer_sequence<int, Ks...>)
+		      std::integer_sequence<int, Ks...>, const u32 *c = nullptr, const u32 *d = nullptr, const u32 *c2 = nullptr)
 {
-	(mul_col9<SQR, Ks>(acc, m, r, a, b, a2, q3, q6, q7, q8), ...);
+	(mul_col9<SQR, Ks, SECOND>(acc, m, r, a, b, a2, q3, q6, q7, q8, c, d, c2), ...);
 }
 
 U29_FN void mul_raw(u32 *r, const u32 *a, const u32 *b)
@@ -228,6 +239,29 @@ U29_FN void sqr_raw(u32 *r, const u32 *a)
 	}
 	u64 acc = 0;
 	mul_cols9<true>(acc, m, r, a, a, a2, q3, q6, q7, q8, std::make_integer_sequence<int, 17>());
+	r[8] = (u32)acc;
+}
+
+// a * b + c * d and a * b + c * c: both products in the same 17 column accumulators, one reduction
+U29_FN void mul2_raw(u32 *r, const u32 *a, const u32 *b, const u32 *c, const u32 *d)
+{
+	u32 m[9];
+	U29_OPAQUE_Q();
+	u64 acc = 0;
+	mul_cols9<false, 1>(acc, m, r, a, b, a, q3, q6, q7, q8, std::make_integer_sequence<int, 17>(), c, d, c);
+	r[8] = (u32)acc;
+}
+
+U29_FN void mulsqr_raw(u32 *r, const u32 *a, const u32 *b, const u32 *c)
+{
+	u32 m[9], c2[9];
+	U29_OPAQUE_Q();
+#pragma unroll
+	for (int i = 0; i < 9; i++) {
+		c2[i] = c[i] << 1;
+	}
+	u64 acc = 0;
+	mul_cols9<false, 2>(acc, m, r, a, b, a, q3, q6, q7, q8, std::make_integer_sequence<int, 17>(), c, c, c2);
 	r[8] = (u32)acc;
 }
 
@@ -307,6 +341,47 @@ template <class A> U29_FN typename MulOut<mul_vb(A::VB, A::VB)>::type sqr(const 
 		r.l[i] = z.l[i];
 	}
 #endif
+	return r;
+}
+
+// Two products under ONE reduction: a b + c d (mul2) and a b + c^2 (mulsqr), for the places where two products are only ever
+// used as their sum -- or, with one operand negated against a multiple of p beforehand, as their difference.  It saves the 36
+// reduction MADs and the 17 + 17 column-carry instructions of the second product, and the result has exact low digits where
+// the sum of two multiplication results would need a carry().
+// column bound: 18 products (9 + 9; a squaring's column is worth at most 9 of its limb products too: 4 doubled + 1) + 4 reduction
+// products + carry-in must fit 64 bits.  Each product is first checked alone (mul_fits), so that the sum below cannot wrap.
+constexpr bool mul2_fits(u64 la, u64 lb, u64 lc, u64 ld)
+{
+	// 9*(la*lb + lc*ld) + 4*2^58 + 2^36 < 2^64
+	return mul_fits(la, lb) && mul_fits(lc, ld) && la * lb + lc * ld <= (0xFFFFFFFFFFFFFFFFull - (1ull << 60) - (1ull << 36)) / 9;
+}
+constexpr u64 mul2_vb(u64 va, u64 vb, u64 vc, u64 vd)
+{
+	// out < (A*B + C*D)/R + p, as mul_vb
+	return (va * vb + vc * vd + 511) / 512 + 16;
+}
+
+// always inline (the out-of-line U29_CALL_MUL build keeps its calls for mul and sqr only)
+template <class A, class B, class C, class D>
+U29_FN typename MulOut<mul2_vb(A::VB, B::VB, C::VB, D::VB)>::type mul2(const A &a, const B &b, const C &c, const D &d)
+{
+	static_assert(mul2_fits(cmax(A::LB, A::TB), cmax(B::LB, B::TB), cmax(C::LB, C::TB), cmax(D::LB, D::TB)),
+		      "mul2: column accumulator could overflow");
+	static_assert(mul2_vb(A::VB, B::VB, C::VB, D::VB) <= 16 * 31, "mul2: result value too large for the top limb");
+	typename MulOut<mul2_vb(A::VB, B::VB, C::VB, D::VB)>::type r;
+	mul2_raw(r.l, a.l, b.l, c.l, d.l);
+	return r;
+}
+
+template <class A, class B, class C>
+U29_FN typename MulOut<mul2_vb(A::VB, B::VB, C::VB, C::VB)>::type mulsqr(const A &a, const B &b, const C &c)
+{
+	static_assert(mul2_fits(cmax(A::LB, A::TB), cmax(B::LB, B::TB), cmax(C::LB, C::TB), cmax(C::LB, C::TB)),
+		      "mulsqr: column accumulator could overflow");
+	static_assert(2 * cmax(C::LB, C::TB) < (1ull << 32), "mulsqr: doubled limb does not fit 32 bits");
+	static_assert(mul2_vb(A::VB, B::VB, C::VB, C::VB) <= 16 * 31, "mulsqr: result value too large for the top limb");
+	typename MulOut<mul2_vb(A::VB, B::VB, C::VB, C::VB)>::type r;
+	mulsqr_raw(r.l, a.l, b.l, c.l);
 	return r;
 }
 
