@@ -13,7 +13,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libecc_amd.so")
 SOURCES = ["ecamd_kernels.hip", "ecamd_p256_kernel.hip", "ecamd_hash.hip", "ecamd_hash2.hip", "ecamd_hash3.hip", "ecamd_rfc6979.hip", "ecamd_hmac.hip", "ecamd_digest_msgs.hip", "ecamd_detnonce.hip", "ecamd_bip0340_nonce_ht.hip", "ecamd_eddsa_sign.hip", "ecamd_eddsa_msgs.hip",
-           "ecamd_host.cpp", "ecamd_host_sigfam.cpp", "ecamd_multi.cpp"]
+           "ecamd_host.cpp", "ecamd_host_eddsa.cpp", "ecamd_host_msm.cpp", "ecamd_host_sigfam.cpp", "ecamd_multi.cpp"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-bitwise-instead-of-logical", "-DU29_ASM_MAD"]

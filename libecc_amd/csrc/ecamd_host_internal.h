@@ -2,7 +2,10 @@
 //
 // The units:
 //   ecamd_host.cpp         errors, host big integers, the context, curve handles, scratch sizing, host_pipeline and the heads of the entry
-//                          points, scalar multiplication and point operations, ECDSA and its relatives, XDH, EdDSA, the whole-batch forms
+//                          points, scalar multiplication and point operations, ECDSA and its relatives, XDH
+//   ecamd_host_eddsa.cpp   EdDSA on the WEI25519 and WEI448 handles: verification, the Ed25519 whole-batch evaluation (buckets and Straus) and
+//                          Ed448's, which runs the Schnorr-type one, signing, one-call signing, the ragged-message forms (ec_eddsa_*_msgs_*)
+//   ecamd_host_msm.cpp     the Schnorr-type whole-batch evaluation (ec_schnorr_verify_*all_*) and the seed of a whole-batch call's z_i
 //   ecamd_host_sigfam.cpp  ECKCDSA / ECSDSA / ECOSDSA, BIGN / DBIGN, BIP0340 / ECFSDSA, message-level ECGDSA / ECRDSA / SM2, ec_hash_slots_*,
 //                          ec_digest_slots_*, HMAC and deterministic ECDSA over the whole hash table (ec_hmac_slots_*, ec_*_ht_*),
 //                          the ragged message array (ec_digest_msgs_*, ec_ecdsa_verify_msgs_*, ec_decdsa_sign_msgs_*)
@@ -31,6 +34,7 @@
 
 // small host big integers (little-endian 32-bit words); only used to derive constants
 typedef std::vector<uint32_t> Big;
+struct SchnorrStreamStep;   // ecamd_host_msm.cpp: which part of the evaluation a call of schnorr_msm_dev_locked runs
 
 namespace ecamd_host {
 int fail(const std::string &m);   // files the thread's error string (ecamd_last_error) and returns -1
@@ -233,6 +237,19 @@ namespace ecamd_host {
 // the host big integers
 int big_bitlen(const Big &a);
 void big_to_be(uint8_t *dst, int len, const Big &a);
+void big_trim(Big &a);
+Big big_from_be(const uint8_t *b, size_t len);
+int big_cmp(const Big &a, const Big &b);
+Big big_add(const Big &a, const Big &b);
+Big big_sub(const Big &a, const Big &b);  // a >= b
+Big big_mul(const Big &a, const Big &b);
+Big big_mod(const Big &a, const Big &m);
+Big big_pow2(int e);
+Big big_mulmod(const Big &a, const Big &b, const Big &m);
+Big big_powmod(const Big &a, const Big &e, const Big &m);
+void big_store(uint32_t *dst, int nw, const Big &a);
+void big_digits29(uint32_t *dst, int nl, const Big &a, int w = 29);   // w-bit digits, nl of them
+Big big_sqrt_m1(const Big &p);  // 2^((p-1)/4) mod p, a square root of -1 when p = 5 mod 8
 
 // Every call works in the context's shared scratch (window tables, stage[] buffers).  A call enqueued on another
 // stream than the previous one therefore first makes its stream wait for the previous call's last kernel, and
@@ -270,7 +287,9 @@ int stage_need(ecamd_ctx *ctx, StageSlot slot, size_t bytes);
 
 // The one way a device core bounds its scratch: pieces of at most ctx->max_chunk items, in order on the stream.  body(off, m) enqueues
 // the items [off, off + m); the first non-zero result ends the walk and is returned.  A core that sizes its frame once does so before
-// the walk, for chunk_items() items.
+// the walk, for chunk_items() items.  (Three whole-batch loops number their pieces for the z_i and so walk by hand:
+// eddsa_verify_msg_prj_impl and ec_schnorr_verify_msg_all_batch, which also skip the walk after a streamed batch, and
+// eddsa_verify_all_dev_locked.)
 static inline uint32_t chunk_items(const ecamd_ctx *ctx, uint32_t n) { return n < ctx->max_chunk ? n : ctx->max_chunk; }
 template <class Body>
 static int for_chunks(const ecamd_ctx *ctx, uint32_t n, Body body)
@@ -313,6 +332,8 @@ static int dev_call(ecamd_ctx *ctx, void *hip_stream, Body body)
 	return body(s);
 }
 int host_call(ecamd_ctx *ctx, int pbits, uint32_t n, const std::vector<HostArr> &arrs, const HostCore &core);
+// the pipeline itself, for the heads that already hold ctx->mu and have set the device (even_chunk: see its definition)
+int host_pipeline(ecamd_ctx *ctx, int pbits, uint32_t n, const std::vector<HostArr> &arrs, const HostCore &core, uint32_t even_chunk = 0);
 
 // ---- the cores of ecamd_host.cpp that the other families build on (ctx->mu held; only enqueue) ----
 hipError_t launch_prj_import(const ecamd_curve *cv, const EcamdPrjInArgs &I, hipStream_t s);
@@ -330,8 +351,22 @@ int ecdsa_verify_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, c
 int ecdsa_sign_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_privs, const uint8_t *d_nonces,
 			  const uint8_t *d_digests, uint32_t hlen, uint8_t *d_sigs, uint8_t *d_status, hipStream_t s);
 int sig_alg_ok(const char *fn, int alg);
+// the generator's 16-bit comb table, built on the first fixed-base batch of comb_min_batch items; the digests of staged message slots into ST_DIGESTS
+void maybe_build_comb(ecamd_ctx *ctx, ecamd_curve *cv, uint32_t n);
+int ecdsa_hash_stage(ecamd_ctx *ctx, int hash_type, uint32_t m, const uint8_t *d_slots, uint32_t stride, uint32_t dlen, hipStream_t s);
 
-// ---- the ragged message array (ecamd_host_sigfam.cpp), shared with EdDSA's ragged calls (ecamd_host.cpp) ----
+// ---- the whole-batch evaluation of ecamd_host_msm.cpp that Ed448's whole-batch form runs too, and the seed of the z_i (ctx->mu held) ----
+int msm_seed(ecamd_ctx *ctx, uint8_t seed[32]);
+void msm_seed_discard(ecamd_ctx *ctx);   // (takes ctx->mu itself)
+static inline size_t msm_align(size_t x) { return (x + 255) & ~(size_t)255; }
+bool schnorr_msm_unit(const ecamd_curve *cv, int *pbits, int *flavour, int *slot);
+int schnorr_msm_dev_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *d_s, const uint8_t *d_ne, const uint8_t *d_keys,
+			   const uint8_t *d_r, int r_fmt, const uint8_t seed[32], uint32_t piece, uint8_t *d_verdict, uint8_t *d_z_dump,
+			   uint32_t *d_sum_dump, hipStream_t s, uint32_t cof_dbl = 0, const SchnorrStreamStep *step = nullptr);
+int schnorr_msm_host_locked(ecamd_ctx *ctx, const ecamd_curve *cv, uint32_t n, const uint8_t *sv, const uint8_t *ne, const uint8_t *keys,
+			    const uint8_t *r, int r_fmt, const uint8_t *fixed_seed, int *accept, uint8_t *z_out, uint32_t *sum_out);
+
+// ---- the ragged message array (ecamd_host_sigfam.cpp), shared with EdDSA's ragged calls (ecamd_host_eddsa.cpp) ----
 // a per-item array of a host form: `stride` octets from item to item, `len` octets used per item (the last item's stride is not read)
 struct MsgsArr {
 	const uint8_t *in;

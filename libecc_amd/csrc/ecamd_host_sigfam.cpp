@@ -2079,7 +2079,7 @@ int ecamd_host::msgs_dev_ptr_ok(const char *fn, const void *d_msgs, uint64_t msg
 	return 0;
 }
 
-// (MsgsArr, MsgsCore: ecamd_host_internal.h -- EdDSA's ragged calls in ecamd_host.cpp stage their pieces through this too)
+// (MsgsArr, MsgsCore: ecamd_host_internal.h -- EdDSA's ragged calls in ecamd_host_eddsa.cpp stage their pieces through this too)
 int ecamd_host::msgs_host_call(const char *fn, ecamd_ctx *ctx, uint32_t n, const uint8_t *msgs, const uint64_t *offsets, const std::vector<MsgsArr> &arrs,
 			  const MsgsCore &core)
 {

@@ -278,3 +278,53 @@ def test_group_law_and_unprotected_mult(gpu_ctx, curve):
         assert cv.pt_op_fmt(0, b"", b"", 1, 1) == (b"", b"")
     finally:
         cv.free()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("curve", ["SECP256R1", "WEI25519"])
+def test_group_law_and_unprotected_mult_in_pieces_of_max_chunk(gpu_ctx, curve):
+    """ec_prj_pt_op_batch_fmt and ec_prj_pt_unprotected_mult_batch stage by hand, a piece of at most max_chunk items at a time: max_chunk 64
+    and n = 130 (three pieces, the last of two items, n a multiple of neither 8 nor 64) give the bytes and status of the one-piece call
+    and of the oracle -- the addition in the projective format both ways, a predicate with its one-byte output stride, the public-scalar
+    multiplication with per-item scalars and with ONE scalar for every item (its offset stays 0 in every piece) -- with an item every
+    operation rejects at 63, 64 (the two sides of a boundary) and 129 (last)"""
+    from test_oracle import group_law_cases
+    from oracles import clen
+    rng = np.random.default_rng(62)
+    o = Oracle(curve)
+    cl = clen(curve)
+    b1, b2, bs, slen = group_law_cases(curve, rng, n=40)
+    m = len(b1) // (3 * cl)
+    base = [o.pt_op_fmt(0, b1, b2, 1, 1)[1], o.pt_op_fmt(4, b1, b2, 1, 1)[1], o.unprotected_mult(bs, slen, b1, 1, 1)[1]]
+    bad = next(i for i in range(m) if all(s[i] == 1 for s in base))       # status 1: rejected (2: the result is the point at infinity)
+    good = [i for i in range(m) if all(s[i] == 0 for s in base)]
+    assert len(good) >= 8
+    n, at = 130, (63, 64, 129)
+    idx = [good[i % len(good)] for i in range(n)]
+    for k in at:
+        idx[k] = bad
+    p1 = b"".join(b1[3 * cl * i:3 * cl * (i + 1)] for i in idx)
+    p2 = b"".join(b2[3 * cl * i:3 * cl * (i + 1)] for i in idx)
+    sc = b"".join(bs[slen * i:slen * (i + 1)] for i in idx)
+    one = CURVES[curve]["q"].to_bytes(slen, "big")       # check_prj_pt_order's use: [q]P for every item
+    cv = gpu_ctx.curve(curve)
+    try:
+        calls = [(lambda h: h.pt_op_fmt(0, p1, p2, 1, 1)), (lambda h: h.pt_op_fmt(4, p1, p2, 1, 1)),
+                 (lambda h: h.unprotected_mult(sc, slen, p1, 1, 1)), (lambda h: h.unprotected_mult(one, slen, p1, 1, 0, broadcast=True))]
+        exp = [c(o) for c in calls]
+        whole = [c(cv) for c in calls]
+        gpu_ctx.set_max_chunk(64)
+        try:
+            pieces = [c(cv) for c in calls]
+        finally:
+            gpu_ctx.set_max_chunk(1 << 20)
+        for k, name in enumerate(("add", "cmp", "unprotected_mult", "unprotected_mult, one scalar")):
+            assert whole[k] == exp[k], (curve, name, "one piece against the oracle")
+            assert pieces[k] == whole[k], (curve, name, "three pieces against one")
+            assert len(pieces[k][1]) == n
+        assert len(pieces[1][0]) == n and len(pieces[0][0]) == 3 * cl * n
+        for k in range(3):
+            assert [i for i in range(n) if pieces[k][1][i] != 0] == list(at), (curve, k)
+        assert [i for i in range(n) if pieces[3][1][i] == 1] == list(at), curve     # [q]P: every other item is at infinity or, off the subgroup, 0
+    finally:
+        cv.free()

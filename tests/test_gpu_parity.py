@@ -1173,6 +1173,38 @@ def test_eddsa25519_sign_steps(gpu_ctx):
         cv.free()
 
 
+@pytest.mark.parametrize("curve", ["WEI25519", "WEI448"])
+def test_eddsa_sign_R_in_pieces_of_max_chunk(gpu_ctx, curve):
+    """ec_eddsa_sign_R_batch with n above max_chunk: max_chunk 64 and n = 130 (three pieces, the last of two items, n a multiple of
+    neither 8 nor 64) give the bytes and status of the one-piece call and of the oracle (Ed448: Python integers).  The step rejects nothing, so the
+    items at 63, 64 (the two sides of a boundary) and 129 (last) are its one exceptional input: r = 0 mod q, whose R is the neutral point"""
+    rng = np.random.default_rng(77)
+    n, at = 130, (63, 64, 129)
+    hl, kl = (64, 32) if curve == "WEI25519" else (114, 57)
+    rh = [rand_bytes(rng, hl) for _ in range(n)]
+    for k in at:
+        rh[k] = CURVES[curve]["q"].to_bytes(hl, "little")
+    rh = b"".join(rh)
+    cv = gpu_ctx.curve(curve)
+    try:
+        whole = cv.eddsa_sign_R(rh)
+        gpu_ctx.set_max_chunk(64)
+        try:
+            pieces = cv.eddsa_sign_R(rh)
+        finally:
+            gpu_ctx.set_max_chunk(1 << 20)
+        if curve == "WEI25519":
+            assert whole == Oracle(curve).eddsa_sign_R(rh)
+        else:
+            import oracles as O
+            assert whole[0] == b"".join(O.e4_encode(O.e4_mul(int.from_bytes(rh[hl * i:hl * (i + 1)], "little") % O.E4_Q, O.E4_B)) for i in range(n))
+        assert pieces == whole and whole[1] == bytes(n) and len(whole[0]) == kl * n
+        enc = [whole[0][kl * i:kl * (i + 1)] for i in range(n)]
+        assert [i for i in range(n) if enc[i] == (1).to_bytes(kl, "little")] == list(at)
+    finally:
+        cv.free()
+
+
 LIBDIR = os.path.join(os.path.dirname(GOLDEN), "..", "libecc_amd", "lib")
 
 

@@ -315,3 +315,36 @@ def test_argument_errors_and_empty_batches(gpu_ctx):
                 cv.sig_sign(alg, bytes(32), bytes(32), bytes(32), 32)
     finally:
         cv.free()
+
+
+@pytest.mark.parametrize("curve", ["SECP256K1"])
+def test_sign_in_pieces_of_max_chunk(gpu_ctx, curve):
+    """ec_sig_sign_batch and its _dev form with n above max_chunk: max_chunk 64 and n = 130 (three pieces, the last of two items, n a
+    multiple of neither 8 nor 64) give the bytes and status of the one-piece call, which are the reference's recorded answers, with an
+    item the reference refuses to sign at 63, 64 (the two sides of a boundary) and 129 (last)"""
+    cv = gpu_ctx.curve(curve)
+    fx = load(curve)
+    n, at = 130, (63, 64, 129)
+    try:
+        for name, alg in ALGS:
+            hlen, group = max(sorted(by_digest_len(fx[name]["sign"]).items()), key=lambda g: len(g[1]))
+            good = [i for i in group if i["ret"] == 0]
+            bad = next(i for i in group if i["ret"] != 0)
+            assert len(good) >= 2
+            items = [good[i % len(good)] for i in range(n)]
+            for k in at:
+                items[k] = bad
+            xs, ks, dgs, sigs, st = sign_arrays(curve, items)
+            assert [i for i in range(n) if st[i] != 0] == list(at)
+            whole = cv.sig_sign(alg, xs, ks, dgs, hlen)
+            gpu_ctx.set_max_chunk(64)
+            try:
+                pieces = cv.sig_sign(alg, xs, ks, dgs, hlen)
+                pdev = sign_dev(cv, alg, xs, ks, dgs, hlen)
+            finally:
+                gpu_ctx.set_max_chunk(1 << 20)
+            assert whole == (sigs, st), (curve, name, "one piece against the recorded reference answers")
+            assert pieces == whole, (curve, name, "three pieces against one")
+            assert pdev == whole, (curve, name, "three pieces against one, dev")
+    finally:
+        cv.free()

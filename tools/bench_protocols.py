@@ -1837,7 +1837,7 @@ def main():
             qb = O.CURVES[curve]["q"].bit_length()
             algo = os.environ.get("ECAMD_SCHNORR_MSM_ALGO") or ("bucket" if B >= (1 << 17) else "straus")
             if algo == "bucket" and qb - 16 * ((qb - 1) // 16) >= 12:
-                # round 6, the bucket evaluation (ecamd_host.cpp:schnorr_msm_use_buckets): per item 8 ql / 16 windows of the key's scalar and 8 of
+                # round 6, the bucket evaluation (ecamd_host_msm.cpp:schnorr_msm_use_buckets): per item 8 ql / 16 windows of the key's scalar and 8 of
                 # z_i, one complete addition with an affine operand each (add_aff: 10M + 3S) in k_bkt_accum_g, the dominant kernel; the step
                 # adds the import of the two points (the key: on-curve check; r: a square root), and the bucket reduction -- 2^16 buckets
                 # per window, 2 Jacobian additions (12M + 4S) each, whatever the batch size
@@ -1987,7 +1987,7 @@ def main():
             how = "Straus, K = %d items per lane" % K
             algo = os.environ.get("ECAMD_ED_MSM_ALGO") or ("bucket" if B >= (1 << 18) else "straus")
             if algo == "bucket":
-                # round 6, the bucket evaluation (ecamd_host.cpp:eddsa_bkt_dev_locked): 16 windows of z h mod q, 8 of z, and a copy of B per 64
+                # round 6, the bucket evaluation (ecamd_host_eddsa.cpp:eddsa_bkt_dev_locked): 16 windows of z h mod q, 8 of z, and a copy of B per 64
                 # items with 16 windows: one addition with an affine precomputed operand (ed_madd: 7M) per pair in k_edbkt_accum; the step adds
                 # the decoding (two square roots, the key's cofactor doublings, two precomputed entries of 3M), and the reduction -- 2^16
                 # buckets per window, 2 unified additions (8M + the operand's conversion 1M) each, whatever the batch size
