@@ -41,8 +41,8 @@ G29_SIZES = [192, 224, 255, 256, 320, 384, 448, 511, 512, 521]
 
 
 def _jobs():
-    """(source, object, extra flags): ecamd_g29_kernel.hip is compiled once per field size and once
-    more as the dispatcher, so that the big template instantiations build in parallel."""
+    """(source, object, extra flags): ecamd_g29_kernel.hip is compiled once per field size and prime flavour, so that
+    the big template instantiations build in parallel; ecamd_g29_dispatch.cpp routes the host layer to them."""
     jobs = [(src, os.path.splitext(src)[0] + ".o", []) for src in SOURCES]
     # the 19-limb dense units need two registers too many for two waves per SIMD; pinned there the window loop fits without a
     # spill: brainpoolP512r1 6.0 -> 7.1 M/s (profiles/r2s_waves_per_simd.md; three waves on the 384 / 521-bit units: no gain / worse)
@@ -60,7 +60,7 @@ def _jobs():
     jobs.append(("ecamd_g29_kernel.hip", "ecamd_g29_384n.o", ["-DG29_PB=384", "-DG29_P384S"]))
     jobs.append(("ecamd_g29_kernel.hip", "ecamd_g29_224s.o", ["-DG29_PB=224", "-DG29_P224S"]))
     jobs.append(("ecamd_g29_kernel.hip", "ecamd_g29_192s.o", ["-DG29_PB=192", "-DG29_P192S"]))
-    jobs.append(("ecamd_g29_kernel.hip", "ecamd_g29_dispatch.o", ["-DG29_DISPATCH"]))
+    jobs.append(("ecamd_g29_dispatch.cpp", "ecamd_g29_dispatch.o", []))
     return jobs
 
 

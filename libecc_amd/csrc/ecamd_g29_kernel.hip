@@ -15,13 +15,14 @@
 #include "ecamd_rcbg.h"
 #endif
 #include "ecamd_internal.h"
+#include "ecamd_g29_geom.h"
 
 using namespace jacg;
 typedef uint8_t u8;
 
-// This file is compiled once per field size (-DG29_PB=<bits>: the kernels of that size plus its own
-// copy of the constant table) and once more with -DG29_DISPATCH (the size -> launcher switch), so
-// that the instantiations build in parallel (libecc_amd/build.py).
+// This file is compiled once per unit (-DG29_PB=<bits> and at most one flavour switch: the kernels of that
+// size or prime plus its own copy of the constant table), so that the instantiations build in parallel
+// (libecc_amd/build.py).  The (size, flavour) -> unit routing is ecamd_g29_dispatch.cpp.
 #define G29_SLOTS 8
 template <int NL> struct SlotsG { CurveG<NL> s[G29_SLOTS]; };
 
@@ -5064,279 +5065,20 @@ hipError_t G29_CAT(ecamd_g29_comb_build_, G29_TAG)(int gslot, const uint8_t *pts
 	hipLaunchKernelGGL((k_comb_build_g<G29_PB, G29_FLAV>), dim3((n + 63) / 64), dim3(64), 0, s, pts, n, clen, table, gslot);
 	return hipGetLastError();
 }
-#endif
 
-#ifdef G29_DISPATCH
-// ---- host-side dispatch on |p| ----
-#define G29_FOR_PB(X) X(192) X(224) X(255) X(256) X(320) X(384) X(448) X(511) X(512) X(521)
-#define X(PB) \
-	hipError_t ecamd_g29_upload_##PB(int slot, const void *img, size_t bytes); \
-	hipError_t ecamd_g29_launch_##PB(int gslot, const EcamdSmulArgs &a, hipStream_t s, hipEvent_t *ev); \
-	hipError_t ecamd_g29_comb_build_##PB(int gslot, const uint8_t *pts, uint32_t n, uint32_t clen, uint32_t *table, hipStream_t s);
-G29_FOR_PB(X)
-X(521m)
-X(255c)
-X(384n)
-X(224s)
-X(192s)
-X(256k)
-X(448g)
-#undef X
-hipError_t ecamd_g29_ed_fin_255c(int gslot, const EcamdEdFinArgs &a, hipStream_t s);
-hipError_t ecamd_g29_ed_fin_448g(int gslot, const EcamdEdFinArgs &a, hipStream_t s);
-
-// the tail of an EdDSA verification on the 2^255 - 19 (flavour 2) or the Goldilocks (flavour 5) unit
-hipError_t ecamd_launch_ed_fin_g29(int flavour, int gslot, const EcamdEdFinArgs &a, hipStream_t s)
-{
-	if (flavour == 2) {
-		return ecamd_g29_ed_fin_255c(gslot, a, s);
-	}
-	if (flavour == 5) {
-		return ecamd_g29_ed_fin_448g(gslot, a, s);
-	}
-	return hipErrorInvalidValue;
-}
-
-int ecamd_g29_supported(int pbits)
-{
-	switch (pbits) {
-#define X(PB) case PB: return 1;
-		G29_FOR_PB(X)
-#undef X
-	default: return 0;
-	}
-}
-int ecamd_g29_nl(int pbits, int flavour) { return g29::nl_for_flavour(pbits, flavour); }
-int ecamd_g29_slots(void) { return G29_SLOTS; }
-uint32_t ecamd_g29_table_words(int pbits, int flavour)
-{
-	const uint32_t nw = (uint32_t)((pbits + 31) / 32);
-	return 8u * (uint32_t)(((3 * g29::nl_for_flavour(pbits, flavour) + 3) / 4) * 4) + ((2u * nw + 2u + 3u) / 4u) * 4u;   // Lay<PB>::ITEMW
-}
-// affine window table of the mixed-addition pipeline: 8 entries of 2 NL digits, padded to 16 bytes (LayA<PB>::AITEMW)
-uint32_t ecamd_g29_affine_words(int pbits, int flavour)
-{
-	return 8u * (uint32_t)(((2 * g29::nl_for_flavour(pbits, flavour) + 3) / 4) * 4);
-}
-uint32_t ecamd_g29_max_slen(int pbits) { return 8u * (uint32_t)((pbits + 31) / 32) + 4u; }
-uint32_t ecamd_g29_comb_max_slen(int pbits) { return 4u * (uint32_t)((pbits + 31) / 32); }
-size_t ecamd_g29_image_bytes(int pbits, int flavour)
-{
-	return (size_t)((10 + g29::NBIAS) * g29::nl_for_flavour(pbits, flavour) + 4) * 4;
-}
-
-// 'flavour' 1 selects the secp521r1 (p = 2^521 - 1) instantiation, 2 the p = 2^255 - 19 one, 3 secp384r1's, 4 secp256k1's, 5 WEI448's,
-// 6 secp224r1's, 7 secp192r1's
-hipError_t ecamd_g29_upload(int pbits, int slot, const void *img, size_t bytes, int flavour)
-{
-	if (pbits == 521 && flavour == 1) {
-		return ecamd_g29_upload_521m(slot, img, bytes);
-	}
-	if (pbits == 255 && flavour == 2) {
-		return ecamd_g29_upload_255c(slot, img, bytes);
-	}
-	if (pbits == 384 && flavour == 3) {
-		return ecamd_g29_upload_384n(slot, img, bytes);
-	}
-	if (pbits == 224 && flavour == 6) {
-		return ecamd_g29_upload_224s(slot, img, bytes);
-	}
-	if (pbits == 192 && flavour == 7) {
-		return ecamd_g29_upload_192s(slot, img, bytes);
-	}
-	if (pbits == 256 && flavour == 4) {
-		return ecamd_g29_upload_256k(slot, img, bytes);
-	}
-	if (pbits == 448 && flavour == 5) {
-		return ecamd_g29_upload_448g(slot, img, bytes);
-	}
-	switch (pbits) {
-#define X(PB) case PB: return ecamd_g29_upload_##PB(slot, img, bytes);
-		G29_FOR_PB(X)
-#undef X
-	default: return hipErrorInvalidValue;
-	}
-}
-
-hipError_t ecamd_launch_smul_g29(int pbits, int gslot, const EcamdSmulArgs &a, hipStream_t s, hipEvent_t *ev, int flavour)
-{
-	if (a.n == 0) {
-		return hipSuccess;
-	}
-	if (pbits == 521 && flavour == 1) {
-		return ecamd_g29_launch_521m(gslot, a, s, ev);
-	}
-	if (pbits == 255 && flavour == 2) {
-		return ecamd_g29_launch_255c(gslot, a, s, ev);
-	}
-	if (pbits == 384 && flavour == 3) {
-		return ecamd_g29_launch_384n(gslot, a, s, ev);
-	}
-	if (pbits == 224 && flavour == 6) {
-		return ecamd_g29_launch_224s(gslot, a, s, ev);
-	}
-	if (pbits == 192 && flavour == 7) {
-		return ecamd_g29_launch_192s(gslot, a, s, ev);
-	}
-	if (pbits == 256 && flavour == 4) {
-		return ecamd_g29_launch_256k(gslot, a, s, ev);
-	}
-	if (pbits == 448 && flavour == 5) {
-		return ecamd_g29_launch_448g(gslot, a, s, ev);
-	}
-	switch (pbits) {
-#define X(PB) case PB: return ecamd_g29_launch_##PB(gslot, a, s, ev);
-		G29_FOR_PB(X)
-#undef X
-	default: return hipErrorInvalidValue;
-	}
-}
-#endif
-
-#ifdef G29_DISPATCH
-// comb table geometry: 2 NW windows of 32768 entries + 1, entry = 2 NL digits padded to 4 words
-uint32_t ecamd_g29_comb_entries(int pbits) { return (uint32_t)(2 * ((pbits + 31) / 32)) * 32768u + 1u; }
-uint32_t ecamd_g29_comb_entry_words(int pbits, int flavour)
-{
-	return (uint32_t)(((2 * g29::nl_for_flavour(pbits, flavour) + 3) / 4) * 4);
-}
-#define X(PB) hipError_t ecamd_g29_ecdsa_prep_##PB(int qgslot, const EcamdEcdsaPrepArgs &a, uint32_t *scratch, int kp, hipStream_t s);
-G29_FOR_PB(X)
-#undef X
-// k_ecdsa_prep_g on the dense unit of qbits bits (the order q in constant slot qgslot of that unit); scratch: n x ecamd_g29_nl(qbits, 0) words
-hipError_t ecamd_g29_ecdsa_prep(int qbits, int qgslot, const EcamdEcdsaPrepArgs &a, uint32_t *scratch, int kp, hipStream_t s)
-{
-	switch (qbits) {
-#define X(PB) case PB: return ecamd_g29_ecdsa_prep_##PB(qgslot, a, scratch, kp, s);
-		G29_FOR_PB(X)
-#undef X
-	default: return hipErrorInvalidValue;
-	}
-}
-
-#define X(PB) hipError_t ecamd_g29_msm_##PB(int gslot, int phase, const EcamdMsmArgs &a, uint32_t *tmp, const uint8_t *gen, const uint8_t *gen_status, \
-					   uint8_t *verdict, uint32_t *sum_out, hipStream_t s);
-G29_FOR_PB(X)
-X(521m)
-X(255c)
-X(384n)
-X(224s)
-X(192s)
-X(256k)
-X(448g)
-#undef X
-uint32_t ecamd_g29_bkt_point_words(int pbits, int flavour)   // BktLay<PB>::PSTRIDE
-{
-	const uint32_t w = (uint32_t)(((2 * g29::nl_for_flavour(pbits, flavour) + 3) / 4) * 4);
-	return w <= 16 ? 16u : (w <= 32 ? 32u : (w <= 64 ? 64u : 128u));
-}
-uint32_t ecamd_g29_msm_rec_words(int pbits, int flavour) { return (uint32_t)(((3 * g29::nl_for_flavour(pbits, flavour) + 3) / 4) * 4) + 4u; }   // MsmLay<PB>::RECW
-// the Schnorr-type multi-scalar multiplication on the unit (pbits, flavour)
-hipError_t ecamd_launch_msm_g29(int pbits, int gslot, int flavour, int phase, const EcamdMsmArgs &a, uint32_t *tmp, const uint8_t *gen,
-				const uint8_t *gen_status, uint8_t *verdict, uint32_t *sum_out, hipStream_t s)
-{
-#define Y(TAG) return ecamd_g29_msm_##TAG(gslot, phase, a, tmp, gen, gen_status, verdict, sum_out, s)
-	if (pbits == 521 && flavour == 1) {
-		Y(521m);
-	}
-	if (pbits == 255 && flavour == 2) {
-		Y(255c);
-	}
-	if (pbits == 384 && flavour == 3) {
-		Y(384n);
-	}
-	if (pbits == 224 && flavour == 6) {
-		Y(224s);
-	}
-	if (pbits == 192 && flavour == 7) {
-		Y(192s);
-	}
-	if (pbits == 256 && flavour == 4) {
-		Y(256k);
-	}
-	if (pbits == 448 && flavour == 5) {
-		Y(448g);
-	}
-	switch (pbits) {
-#define X(PB) case PB: Y(PB);
-		G29_FOR_PB(X)
-#undef X
-	default: return hipErrorInvalidValue;
-	}
-#undef Y
-}
-
-#define X(PB) hipError_t ecamd_g29_prj_import_##PB(int gslot, const EcamdPrjInArgs &a, hipStream_t s);
-G29_FOR_PB(X)
-X(521m)
-X(255c)
-X(384n)
-X(224s)
-X(192s)
-X(256k)
-X(448g)
-#undef X
-// k_prj_import_g on the unit (pbits, flavour)
-hipError_t ecamd_g29_prj_import(int pbits, int gslot, const EcamdPrjInArgs &a, hipStream_t s, int flavour)
-{
-	if (pbits == 521 && flavour == 1) {
-		return ecamd_g29_prj_import_521m(gslot, a, s);
-	}
-	if (pbits == 255 && flavour == 2) {
-		return ecamd_g29_prj_import_255c(gslot, a, s);
-	}
-	if (pbits == 384 && flavour == 3) {
-		return ecamd_g29_prj_import_384n(gslot, a, s);
-	}
-	if (pbits == 224 && flavour == 6) {
-		return ecamd_g29_prj_import_224s(gslot, a, s);
-	}
-	if (pbits == 192 && flavour == 7) {
-		return ecamd_g29_prj_import_192s(gslot, a, s);
-	}
-	if (pbits == 256 && flavour == 4) {
-		return ecamd_g29_prj_import_256k(gslot, a, s);
-	}
-	if (pbits == 448 && flavour == 5) {
-		return ecamd_g29_prj_import_448g(gslot, a, s);
-	}
-	switch (pbits) {
-#define X(PB) case PB: return ecamd_g29_prj_import_##PB(gslot, a, s);
-		G29_FOR_PB(X)
-#undef X
-	default: return hipErrorInvalidValue;
-	}
-}
-
-hipError_t ecamd_g29_comb_build(int pbits, int gslot, const uint8_t *pts, uint32_t n, uint32_t clen, uint32_t *table,
-				hipStream_t s, int flavour)
-{
-	if (pbits == 521 && flavour == 1) {
-		return ecamd_g29_comb_build_521m(gslot, pts, n, clen, table, s);
-	}
-	if (pbits == 255 && flavour == 2) {
-		return ecamd_g29_comb_build_255c(gslot, pts, n, clen, table, s);
-	}
-	if (pbits == 384 && flavour == 3) {
-		return ecamd_g29_comb_build_384n(gslot, pts, n, clen, table, s);
-	}
-	if (pbits == 224 && flavour == 6) {
-		return ecamd_g29_comb_build_224s(gslot, pts, n, clen, table, s);
-	}
-	if (pbits == 192 && flavour == 7) {
-		return ecamd_g29_comb_build_192s(gslot, pts, n, clen, table, s);
-	}
-	if (pbits == 256 && flavour == 4) {
-		return ecamd_g29_comb_build_256k(gslot, pts, n, clen, table, s);
-	}
-	if (pbits == 448 && flavour == 5) {
-		return ecamd_g29_comb_build_448g(gslot, pts, n, clen, table, s);
-	}
-	switch (pbits) {
-#define X(PB) case PB: return ecamd_g29_comb_build_##PB(gslot, pts, n, clen, table, s);
-		G29_FOR_PB(X)
-#undef X
-	default: return hipErrorInvalidValue;
-	}
-}
+// What the host sizes its buffers with (ecamd_g29_geom.h, returned by ecamd_g29_dispatch.cpp) is what this unit's kernels index with.
+namespace g29 {
+static_assert(nl_for_flavour(G29_PB, G29_FLAV) == Lay<G29_PB>::NL, "limbs");
+static_assert(geom_slots() == G29_SLOTS, "constant slots");
+static_assert(geom_table_words(G29_PB, G29_FLAV) == (uint32_t)Lay<G29_PB>::ITEMW, "table words");
+static_assert(geom_affine_words(G29_PB, G29_FLAV) == (uint32_t)LayA<G29_PB>::AITEMW, "affine table words");
+static_assert(geom_comb_entry_words(G29_PB, G29_FLAV) == (uint32_t)CombLay<G29_PB>::CENTW, "comb entry words");
+static_assert(geom_comb_entries(G29_PB) == (uint32_t)CombLay<G29_PB>::NWIN * COMB_PER_WIN + 1u, "comb entries");
+static_assert(geom_bkt_point_words(G29_PB, G29_FLAV) == (uint32_t)BktLay<G29_PB>::PSTRIDE, "bucket point words");
+static_assert(geom_msm_rec_words(G29_PB, G29_FLAV) == (uint32_t)MsmLay<G29_PB>::RECW, "multi-scalar record words");
+static_assert(geom_image_bytes(G29_PB, G29_FLAV) == sizeof(CurveG<Lay<G29_PB>::NL>), "constant image");
+// recode_scalar: the scalar's words, then the carry in word KRECW - 1
+static_assert(geom_max_slen(G29_PB) <= 4u * (uint32_t)Lay<G29_PB>::KRECW - 4u, "longest scalar of the window kernels");
+static_assert(geom_comb_max_slen(G29_PB) == 4u * (uint32_t)Lay<G29_PB>::KW - 4u, "longest scalar of the comb");
+}  // namespace g29
 #endif

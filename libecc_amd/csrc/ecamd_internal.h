@@ -803,7 +803,7 @@ hipError_t ecamd_launch_status_or(uint8_t *status, const uint8_t *bad, uint8_t *
 hipError_t ecamd_launch_prj_import(int nw, const EcamdPrjInArgs &a, hipStream_t s);
 hipError_t ecamd_launch_prj_export(const EcamdPrjOutArgs &a, hipStream_t s);
 
-// radix-2^29 Jacobian fast path for every field size (ecamd_g29_kernel.hip)
+// radix-2^29 Jacobian fast path for every field size (ecamd_g29_dispatch.cpp routes to the units of ecamd_g29_kernel.hip; geometry: ecamd_g29_geom.h)
 int ecamd_g29_supported(int pbits);
 int ecamd_g29_nl(int pbits, int flavour);
 int ecamd_g29_slots(void);
